@@ -19,10 +19,19 @@ re-executes under torch.distributed.run on 127.0.0.1.  With fewer visible GPUs
 than ranks the ranks share the GPUs and exchange through host memory (gloo): a
 functional run of the sharded path, flagged as such in the JSON line.
 
-Prints ONE JSON line (rank 0), the last line of stdout.  `roofline` is for the
-dominant hand-written kernel, from HIP events on the stream the kernels run
-on; `cpu_baseline` is the C oracle (oracle/, a port of the reference's
+Prints ONE JSON line (rank 0), the last line of stdout.  A plain run sets up,
+warms up, times the --steps steps and prints the headline figures (with the
+per-phase times the timed steps' own HIP events give).  --full adds what takes
+work of its own: `roofline` for the dominant hand-written kernel (the FFT
+passes timed by extra solves after the timed region), the untimed `verify`
+replay, the other configurations of the default line (`configs`, `timeloop`)
+and `cpu_baseline`, the C oracle (oracle/, a port of the reference's
 algorithm) timed on a bounded sample on this host's cores.
+
+--dump-outputs DIR: after the timed steps, the particles the last step left
+(DIR/pos.npy, DIR/mom.npy: a fixed sample in a canonical order; DIR/totals.npy)
+for comparing two builds output for output; the inputs are a function of the
+arguments only.
 """
 import argparse
 import json
@@ -501,6 +510,47 @@ def global_particles(torch, args, n_p, L, cell, mass, dt, dev, rank=0, world=1, 
     return torch.cat(P).contiguous(), torch.cat(M).contiguous(), torch.cat(I).contiguous()
 
 
+DUMP_SAMPLE = 1 << 19   # particles --dump-outputs writes: 2 x 24 B each, 24 MB at most
+
+
+def dump_outputs(torch, out_dir, pos, mom, n_p, regions=None):
+    """--dump-outputs: what the timed path's last step left for its caller — the particles'
+    positions and momenta (float64) — as DIR/pos.npy and DIR/mom.npy, [k, 3] each.  The path
+    carries no identifiers and the order inside a tile is the order of device atomics, so the
+    particles are put in a canonical order first (by x, then y, then z); of more than
+    DUMP_SAMPLE particles, a fixed seeded sample of places in that order is written.
+    DIR/totals.npy: [particles, Σ pos (3), Σ mom (3), Σ mom²] over all of them.  regions: the
+    (start, count) table of particles kept in tile regions with gaps, None for n_p rows."""
+    import numpy as np
+    if regions is not None:
+        start, count = regions
+        count = count.long()
+        n = int(count.sum())
+        # row of the j-th particle of region k: start[k] + j - (particles before region k)
+        base = start[:count.numel()].long() - (torch.cumsum(count, 0) - count)
+        rows = torch.repeat_interleave(base, count, output_size=n)
+        rows += torch.arange(n, dtype=torch.int64, device=rows.device)
+        p, m = pos[rows], mom[rows]
+        del rows, base
+    else:
+        n = n_p
+        p, m = pos[:n_p], mom[:n_p]
+    if n != n_p:
+        sys.exit(f'bench.py --dump-outputs: {n} of {n_p} particles after the timed steps')
+    order = torch.argsort(p[:, 2], stable=True)
+    for d in (1, 0):
+        order = order[torch.argsort(p[order, d], stable=True)]
+    if n > DUMP_SAMPLE:
+        places = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+        order = order[torch.as_tensor(places, device=order.device)]
+    totals = torch.cat([torch.tensor([float(n)], dtype=torch.float64, device=p.device),
+                        p.sum(0), m.sum(0), m.square().sum().reshape(1)])
+    os.makedirs(out_dir, exist_ok=True)
+    for fname, a in (('pos', p[order]), ('mom', m[order]), ('totals', totals)):
+        np.save(os.path.join(out_dir, fname + '.npy'), a.cpu().numpy().astype(np.float64))
+    del p, m, order
+
+
 def verify_key(args, name, steps_total):
     return f'{name}_seed{args.seed}_thermal{args.thermal:g}_steps{steps_total}'
 
@@ -739,7 +789,7 @@ def main_distributed(args, name, n_p, N, L, dev, rank, world, backend):
     # The check this line carries: the same step sequence once more, untimed,
     # with the identifiers travelling, and its id-keyed sample against the 1-rank values
     verify = None
-    if not args.no_verify and not args.weak and fused and not args.dry_links:
+    if args.full and not args.no_verify and not args.weak and fused and not args.dry_links:
         import numpy as np
         del parts
         torch.cuda.empty_cache()
@@ -922,8 +972,8 @@ def main():
                          '(configs.c2_p3m_rungs of the default line), --steps base steps')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra-configs', action='store_true',
-                    help='default run only: skip the other configurations timed after the '
-                         'north-star region (the `configs` block of the JSON line)')
+                    help='--full default run only: skip the other configurations timed after '
+                         'the north-star region (the `configs` block of the JSON line)')
     ap.add_argument('--split-poisson', action='store_true',
                     help='time FFT forward / k-space kernel / FFT backward separately (unfused)')
     ap.add_argument('--weak', action='store_true',
@@ -957,7 +1007,19 @@ def main():
                     help='do not fuse the next drift\'s tile histogram into the gather-kick')
     ap.add_argument('--no-sort', action='store_true',
                     help='direct (untiled) kernels on unsorted particles, for A/B')
+    ap.add_argument('--full', action='store_true',
+                    help='also everything beyond the headline figure: per-kernel and roofline '
+                         'figures (extra solves after the timed region), the untimed verify '
+                         'replay, the other configurations of the default line and the CPU '
+                         'baseline (each can still be switched off by its --no-* option)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the particles the last step left as '
+                         'DIR/pos.npy, DIR/mom.npy (a fixed sample in a canonical order) and '
+                         'DIR/totals.npy, float64 (single-GPU PM / P3M runs)')
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.rung_loop or args.workload in C4_SIZES
+                              or os.environ.get('CONCEPT_BENCH_FORCE_DIST') == '1'):
+        sys.exit('bench.py --dump-outputs: single-GPU runs of the PM / P3M step only')
 
     if args.link_model:
         n_p, N = WORKLOADS[args.workload or 'ns_256M_1024']
@@ -1041,15 +1103,16 @@ def main():
         return main_distributed(args, name, n_p, N, L, dev, rank, world, backend)
     result = run_single(args, torch, dev, rank)
     torch.cuda.empty_cache()
-    if args.workload is None and not args.no_extra_configs and not args.p3m and not args.weak \
-            and args.dist == 'uniform' and not (args.no_fused or args.no_sort or args.no_prepare
-                                                or args.split_poisson):
+    if args.full and args.workload is None and not args.no_extra_configs and not args.p3m \
+            and not args.weak and args.dist == 'uniform' \
+            and not (args.no_fused or args.no_sort or args.no_prepare or args.split_poisson):
         # The other configurations under the same clock: after the timed
         # north-star region, 20 steps each of BASELINE configs[1] as a PM and as a P3M step and
         # of the north-star size on the clustered, the displaced-lattice and the Zel'dovich-like
         #  distributions and with the seeds 2 and 3.  The headline fields
         # above are untouched.
         import copy
+        args.dump_outputs = None   # (what the headline's steps left is written already)
         result['configs'] = {}
         for cname, over in (('c2_256c_512_pm', dict(workload='c2_256c_512')),
                             ('c2_256c_512_p3m', dict(workload='c2_256c_512', p3m=True)),
@@ -1106,7 +1169,7 @@ def main():
         # the same workload through the drop-in API
         result['timeloop'] = timeloop_leg(torch, dev, result['ms_per_step'])
         result['timeloop_ms_per_step'] = result['timeloop']['ms_per_base_step']
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(name)
     print(json.dumps(result))
 
@@ -1690,7 +1753,11 @@ def run_single(args, torch, dev, rank=0):
         kept = int(reg['count'].long().sum().item())
         if kept != n_p:
             sys.exit(f'bench.py: {kept} of {n_p} particles after the timed steps')
-        timed_m2 = mesh.measure_momentum_regions(mom, reg['start'], reg['count'])[0]
+        if args.full:   # (what the verify replay below is held against)
+            timed_m2 = mesh.measure_momentum_regions(mom, reg['start'], reg['count'])[0]
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, pos, mom, n_p,
+                     (reg['start'], reg['count']) if fused else None)
 
     n_g = N**3
     mv, sv = moved_bytes(n_p, n_g), survey_bytes(n_p, n_g)
@@ -1714,29 +1781,6 @@ def run_single(args, torch, dev, rank=0):
             e['survey_8d_GB'] = round(sv[key]/1e9, 3)  # the unfused reference phases' bytes
         return e
     phases = {ph: entry(ph, phase_ms[ph]) for ph in PHASES}
-    # single kernels: the phases that are one launch, plus the five FFT passes timed by
-    # HIP events inside the library (a few extra solves after the timed region)
-    kernels = {ph: phase_ms[ph] for ph in ('deposit', 'gather_kick', 'kick_drift_sort', 'drift',
-                                           'sr_sweep')
-               if ph in phase_ms}  # (drift_sort is two kernels + a scan: reported under phases)
-    if not args.split_poisson:
-        pass_ms = [0.0]*5
-        reps = 3
-        lr, E = (True, sr['E']) if sr else (False, 0.0)
-        for _ in range(reps):
-            for k, v in enumerate(mesh.poisson_solve_timed(4, C, lr, E)):
-                pass_ms[k] += v/reps
-        names = ('fft_z_forward', 'fft_y_forward', 'fft_x_fused_kspace', 'fft_y_backward',
-                 'fft_z_backward')
-        if pass_ms[1] < 0.05*pass_ms[0]:
-            # the z and y passes run interleaved over cache-sized chunks of layers (cg_fft.hip):
-            # they are timed together; the second pass of a chunk is served by the infinity
-            # cache (its bytes still cross L2 <-> fabric, which is what `moved` counts)
-            names = ('fft_zy_forward_chunked', 'fft_x_fused_kspace', 'fft_yz_backward_chunked')
-            pass_ms = [pass_ms[0] + pass_ms[1], pass_ms[2], pass_ms[3] + pass_ms[4]]
-        for nm, v in zip(names, pass_ms):
-            kernels[nm] = v
-    dom = max(kernels, key=lambda k: kernels[k])
     ms_per_step = elapsed/args.steps*1e3
     result = {
         'metric': ('P3M' if args.p3m else 'PM') + ' particle-updates/sec',
@@ -1760,33 +1804,63 @@ def run_single(args, torch, dev, rank=0):
                    'particles': n_p, 'gridsize': N, 'parallelism': 'domains1'},
         'emigrants_per_step': 0,
     }
-    if dom == 'sr_sweep':
-        # FP64 VALU-bound: EXECUTED pair tests/s against the FP64 vector issue rate.  The tests
-        # are counted by the sweeps themselves (cg_shortrange_stats: counting instantiations of
-        # the two kernels, one extra sweep over the last step's cell list after the timed
-        # region, on a scratch copy of the momenta): a lane that holds a receiver against a
-        # supplier of its range is one test, a test with r2 <= r2_max one hit.
-        scratch = mom.clone()
-        mesh.shortrange_stats(True)
-        mesh.shortrange_sweep_cells(sr['cells'], scratch, sr['cells'], sr['nt'], sr['table'],
-                                    sr['scaling'], sr['r2_max'], sr['factor'])
-        st = mesh.shortrange_stats(False)
-        del scratch
-        result['roofline'] = pair_sweep_roofline(st, kernels[dom], dom, sr['cells'][1], sr['nt'])
-    else:
-        ach = mv[dom]/(kernels[dom]*1e-3)/1e9
-        traffic, traffic_source = pmc_traffic(dom, name)
-        result['roofline'] = {
-            'bound': 'hbm', 'kernel': dom, 'achieved': round(ach, 1), 'peak': HBM_PEAK_GBS,
-            'unit': 'GB/s', 'frac': round(ach/HBM_PEAK_GBS, 4), 'traffic': traffic,
-            'algorithmic_bytes': mv[dom], 'kernel_ms': round(kernels[dom], 4),
-            'hbm_rate_GBps': (round(traffic/(kernels[dom]*1e-3)/1e9, 1) if traffic else None),
-            'survey_8d_bytes': sv.get(dom),
-            'note': ('algorithmic bytes = what this fused kernel must move (DESIGN.md §4); '
-                     'survey_8d_bytes = SURVEY.md §8(d)\'s figure for the unfused reference '
-                     'phases it replaces, given for comparison only'),
-            'traffic_source': traffic_source}
-    result['kernels'] = {k: entry(k, ms) for k, ms in kernels.items()}
+    if args.full:
+        # single kernels: the phases that are one launch, plus the five FFT passes timed by
+        # HIP events inside the library (a few extra solves after the timed region)
+        # (drift_sort is two kernels + a scan: reported under phases)
+        kernels = {ph: phase_ms[ph] for ph in ('deposit', 'gather_kick', 'kick_drift_sort',
+                                               'drift', 'sr_sweep')
+                   if ph in phase_ms}
+        if not args.split_poisson:
+            pass_ms = [0.0]*5
+            reps = 3
+            lr, E = (True, sr['E']) if sr else (False, 0.0)
+            for _ in range(reps):
+                for k, v in enumerate(mesh.poisson_solve_timed(4, C, lr, E)):
+                    pass_ms[k] += v/reps
+            names = ('fft_z_forward', 'fft_y_forward', 'fft_x_fused_kspace', 'fft_y_backward',
+                     'fft_z_backward')
+            if pass_ms[1] < 0.05*pass_ms[0]:
+                # the z and y passes run interleaved over cache-sized chunks of layers
+                # (cg_fft.hip): they are timed together; the second pass of a chunk is served by
+                # the infinity cache (its bytes still cross L2 <-> fabric, which is what `moved`
+                # counts)
+                names = ('fft_zy_forward_chunked', 'fft_x_fused_kspace',
+                         'fft_yz_backward_chunked')
+                pass_ms = [pass_ms[0] + pass_ms[1], pass_ms[2], pass_ms[3] + pass_ms[4]]
+            for nm, v in zip(names, pass_ms):
+                kernels[nm] = v
+        dom = max(kernels, key=lambda k: kernels[k])
+        if dom == 'sr_sweep':
+            # FP64 VALU-bound: EXECUTED pair tests/s against the FP64 vector issue rate.  The
+            # tests are counted by the sweeps themselves (cg_shortrange_stats: counting
+            # instantiations of the two kernels, one extra sweep over the last step's cell list
+            # after the timed region, on a scratch copy of the momenta): a lane that holds a
+            # receiver against a supplier of its range is one test, a test with r2 <= r2_max one
+            # hit.
+            scratch = mom.clone()
+            mesh.shortrange_stats(True)
+            mesh.shortrange_sweep_cells(sr['cells'], scratch, sr['cells'], sr['nt'],
+                                        sr['table'], sr['scaling'], sr['r2_max'], sr['factor'])
+            st = mesh.shortrange_stats(False)
+            del scratch
+            result['roofline'] = pair_sweep_roofline(st, kernels[dom], dom, sr['cells'][1],
+                                                     sr['nt'])
+        else:
+            ach = mv[dom]/(kernels[dom]*1e-3)/1e9
+            traffic, traffic_source = pmc_traffic(dom, name)
+            result['roofline'] = {
+                'bound': 'hbm', 'kernel': dom, 'achieved': round(ach, 1), 'peak': HBM_PEAK_GBS,
+                'unit': 'GB/s', 'frac': round(ach/HBM_PEAK_GBS, 4), 'traffic': traffic,
+                'algorithmic_bytes': mv[dom], 'kernel_ms': round(kernels[dom], 4),
+                'hbm_rate_GBps': (round(traffic/(kernels[dom]*1e-3)/1e9, 1) if traffic
+                                  else None),
+                'survey_8d_bytes': sv.get(dom),
+                'note': ('algorithmic bytes = what this fused kernel must move (DESIGN.md §4); '
+                         'survey_8d_bytes = SURVEY.md §8(d)\'s figure for the unfused reference '
+                         'phases it replaces, given for comparison only'),
+                'traffic_source': traffic_source}
+        result['kernels'] = {k: entry(k, ms) for k, ms in kernels.items()}
     interp = 'kick_drift_sort' if fused else 'gather_kick'
     groups = {'deposit+interp': (['deposit', interp], phase_ms['deposit'] + phase_ms[interp]),
               'poisson_solve': (['poisson'] if not args.split_poisson else
@@ -1804,7 +1878,7 @@ def run_single(args, torch, dev, rank=0):
             'survey_8d_GB': round(credit/1e9, 2)}
     result['phases'] = phases
     del pos, mom, pos2, mom2
-    if fused and args.dist == 'uniform' and not args.no_verify and not args.weak \
+    if args.full and fused and args.dist == 'uniform' and not args.no_verify and not args.weak \
             and n_p <= 2**29:   # (the replay keeps the identifiers in two stores: ~300 B per particle)
         # the values an N-rank run of this command is checked against (its `verify` block):
         # the same step sequence once more, untimed, with the identifiers travelling

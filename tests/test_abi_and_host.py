@@ -326,3 +326,50 @@ def test_bench_box_is_a_function_of_seed_and_identifier(tmp_path, monkeypatch):
     assert np.array_equal(got['pos'], one[0][sel].numpy())
     assert np.array_equal(got['mom'], one[1][sel].numpy())
     assert bench.verify_load('no such key') is None
+
+
+def test_bench_dump_outputs_canonical_order_and_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the particles of tile regions with gaps come out in the canonical
+    order (x, then y, then z) whatever order they were stored in, a larger set as the same seeded
+    sample of places in that order, float64; totals over every particle."""
+    import sys
+    import numpy as np
+    import torch
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    rng = np.random.default_rng(5)
+    n = 1000
+    pos = rng.uniform(0, 8.0, (n, 3))
+    pos[:10, 0] = pos[10:20, 0]          # equal x: y decides
+    pos[20:25, :2] = pos[25:30, :2]      # equal x and y: z decides
+    mom = rng.normal(0, 1.0, (n, 3))
+    # regions with gaps: region k keeps count[k] rows from start[k]; the stored order scrambled
+    count = torch.tensor([0, 300, 1, 0, 450, 249], dtype=torch.int32)
+    gap = 7
+    start = torch.zeros(count.numel() + 1, dtype=torch.int32)
+    start[1:] = torch.cumsum(count + gap, 0)
+    cap = int(start[-1])
+    rows = torch.cat([torch.arange(int(s), int(s) + int(c)) for s, c in zip(start[:-1], count)])
+    perm = torch.as_tensor(rng.permutation(n))
+    P = torch.full((cap, 3), np.nan, dtype=torch.float64)
+    M = torch.full((cap, 3), np.nan, dtype=torch.float64)
+    P[rows], M[rows] = torch.as_tensor(pos)[perm], torch.as_tensor(mom)[perm]
+    order = np.lexsort((pos[:, 2], pos[:, 1], pos[:, 0]))
+    bench.dump_outputs(torch, str(tmp_path/'all'), P, M, n, (start, count))
+    got = {k: np.load(tmp_path/'all'/(k + '.npy')) for k in ('pos', 'mom', 'totals')}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got['pos'], pos[order]) and np.array_equal(got['mom'], mom[order])
+    assert got['totals'][0] == n
+    assert np.allclose(got['totals'][1:4], pos.sum(0), rtol=1e-13)
+    assert np.allclose(got['totals'][4:7], mom.sum(0), rtol=1e-13, atol=1e-12)
+    assert np.isclose(got['totals'][7], (mom**2).sum(), rtol=1e-13)
+    # plain rows, more particles than the sample: the same places each time, still in order
+    monkeypatch.setattr(bench, 'DUMP_SAMPLE', 64)
+    for d in ('a', 'b'):
+        bench.dump_outputs(torch, str(tmp_path/d), torch.as_tensor(pos), torch.as_tensor(mom), n)
+    a, b = (np.load(tmp_path/d/'pos.npy') for d in ('a', 'b'))
+    assert a.shape == (64, 3) and np.array_equal(a, b)
+    place_of = {tuple(r): i for i, r in enumerate(pos[order])}
+    places = np.array([place_of[tuple(r)] for r in a])
+    assert np.all(np.diff(places) > 0)
+    assert np.array_equal(np.load(tmp_path/'a'/'mom.npy'), mom[order][places])

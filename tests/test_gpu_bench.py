@@ -1,10 +1,12 @@
 """bench.py keeps its contract under every flag it documents: one JSON line on stdout with the
-driver's keys, `roofline` and (unless switched off) `cpu_baseline`."""
+driver's keys; with --full also `roofline` and (unless switched off) `cpu_baseline`.  A plain run
+carries the headline figures only and --dump-outputs writes what its last step left."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -15,7 +17,7 @@ KEYS = {'metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', '
 
 def run(*flags, env=None):
     p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--workload', 'tiny',
-                        '--steps', '2', '--warmup', '1'] + list(flags),
+                        '--steps', '2', '--warmup', '1', '--full'] + list(flags),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900,
                        env=dict(os.environ, **(env or {})))
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -59,7 +61,7 @@ def test_bench_cpu_baseline_and_sharded_paths():
 
 def run_workload(workload, *flags, steps=2, warmup=1, timeout=1500):
     p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--steps', str(steps),
-                        '--warmup', str(warmup), '--no-cpu-baseline']
+                        '--warmup', str(warmup), '--no-cpu-baseline', '--full']
                        + (['--workload', workload] if workload else []) + list(flags),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=timeout,
                        env=dict(os.environ))
@@ -164,3 +166,36 @@ def test_bench_rung_loop_leg():
     assert {'drift_flag_nullify', 'apply_convert_jumps_populations', 'long_range_kick'} <= set(g)
     assert sum(d['rung_populations_at_the_end']) == 32**3
     assert d['gpu_ms_per_base_step_in_calls'] <= 1.05*d['ms_per_base_step_min_max'][1]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run (no --full) times --steps steps and prints the headline figures only; with
+    --dump-outputs it writes the particles its last step left, float64, and two runs of the same
+    command start from the same particles: their outputs agree to the last bits the order of
+    the device atomics leaves open."""
+    out = {}
+    for tag in ('a', 'b'):
+        p = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1',
+                            '--workload', 'tiny', '--steps', '3', '--warmup', '1',
+                            '--dump-outputs', str(tmp_path/tag)],
+                           stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert {'metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'} <= set(d)
+        assert d['steps'] == 3 and d['warmup'] == 1 and d['value'] > 0 and d['ms_per_step'] > 0
+        assert d['metric'] == 'PM particle-updates/sec' and d['unit'] == 'particle-updates/s'
+        assert d['higher_is_better'] is True and d['dtype'] == 'f64'
+        assert d['value'] == pytest.approx(32**3/(d['ms_per_step']*1e-3), rel=1e-9)
+        assert not {'roofline', 'kernels', 'verify', 'configs', 'cpu_baseline'} & set(d)
+        out[tag] = {k: np.load(tmp_path/tag/(k + '.npy')) for k in ('pos', 'mom', 'totals')}
+        assert all(a.dtype == np.float64 for a in out[tag].values())
+        assert sum(os.path.getsize(tmp_path/tag/f) for f in os.listdir(tmp_path/tag)) <= 64 << 20
+    a, b = out['a'], out['b']
+    assert a['pos'].shape == a['mom'].shape == (32**3, 3) and a['totals'][0] == 32**3
+    L = 64.0
+    assert np.all((a['pos'] >= 0) & (a['pos'] < L))
+    assert np.abs(a['pos'] - b['pos']).max() <= 1e-12*L
+    assert np.abs(a['mom'] - b['mom']).max() <= 1e-12*np.sqrt((a['mom']**2).mean())
+    assert np.allclose(a['totals'], b['totals'], rtol=1e-12)
