@@ -453,3 +453,19 @@ def upload(values, device, dtype=None):
     if torch.device(device).type != 'cuda':
         return h.clone()
     return h.pin_memory().to(device, non_blocking=True)
+
+
+def sparse_rows(mask, max_rows):
+    """The rows of `mask` (1-D bool tensor) that are set, for the sweep without a cell list
+    (cg_shortrange_sparse): max_rows + 1 slots, the set rows first in ascending order, the
+    slots beyond them -1 — found without the host learning how many there are (torch.nonzero()
+    would wait for the stream).  The sweep skips the slots below 0 and reports more than
+    max_rows set rows (a valid row in the last slot) as CG_ERR_ACTIVE_OVERFLOW, so that the
+    rung populations, which choose this form, never decide which receivers are kicked."""
+    import torch
+    if mask.dim() != 1 or mask.dtype != torch.bool:
+        raise ValueError('sparse_rows: mask must be a 1-D bool tensor')
+    if hasattr(torch, 'nonzero_static'):
+        return torch.nonzero_static(mask, size=max_rows + 1, fill_value=-1).flatten()
+    rows = torch.nonzero(mask).flatten()[:max_rows + 1]
+    return torch.cat([rows, rows.new_full((max_rows + 1 - rows.numel(),), -1)])

@@ -163,10 +163,13 @@ struct cg_ctx {
         i64 nt = 0;
         int min_pop = 0;
         hipEvent_t ev = nullptr;
-        bool harvested = true;   // its result has been counted in srd_quiet
+        bool harvested = true;   // its result is known to be in srd_host
     } srd_look[4];
-    int srd_look_next = 0, srd_idle = 0;
-    int srd_quiet = 0;   // completed looks in a row that found no dense tile
+    // looks taken (look k sits in slot k % 4 until look k + 4 takes it over), and how many of
+    // them, in the order taken, have been counted in srd_quiet
+    unsigned long long srd_looks = 0, srd_counted = 0;
+    int srd_idle = 0;
+    int srd_quiet = 0;   // counted looks in a row that found no dense tile
     bool srd_hilbert_done = false;
     unsigned *srd_host = nullptr;
     void *srd_small = nullptr, *srd_buf = nullptr, *srd_rung = nullptr;

@@ -10,9 +10,11 @@
 // sums over all its partners itself — twice the arithmetic, but no atomics, no
 // write conflicts (the order of partners inside a cell follows the cell list's
 // atomics, so sums are reproducible to rounding, not bit for bit).  The pair
-// vector, r2 and the table index are evaluated with the reference's expression
-// and operation order ((xi - xj) + offset; x*x + y*y + z*z; int(r2*scaling)):
-// exact negation symmetry makes the two directions of a pair bit-consistent.
+// vector and the table index follow the reference's expression and operation order
+// ((xi - xj) + offset; int(r2*scaling)); r2 is one product and two fused multiply-adds
+// (sr_r2), within 1 ulp of the reference's x*x + y*y + z*z, so that a pair at the range or
+// at a table entry's boundary may fall on the other side of it.  Exact negation symmetry
+// makes the two directions of a pair bit-consistent.
 // (The tiles of 64 particles and more go to cg_shortrange_dense.hip; earlier forms of the
 // sweep — one wavefront per tile, a single-precision pre-test, a matrix-core range filter —
 // were measured slower and are gone: profiles/README.md keeps their numbers.)
@@ -85,8 +87,10 @@ struct SrCount {
 //    0 * table[0] = 0, as would two distinct particles at one position (the reference skips
 //    i == j by index, interactions.py:1722; the sums are the same);
 //  * the accumulation a += x_ji * f is a fused multiply-add (the order of partners already
-//    differs from the reference's, Δmom is compared to 1e-12); x_ji, r2 and the table index
-//    keep the reference's operation order and are bit-identical.
+//    differs from the reference's, Δmom is compared to 1e-12); x_ji keeps the reference's
+//    operation order and is bit-identical, r2 is one product and two fused multiply-adds
+//    (sr_r2) and lies within 1 ulp of the reference's sum, so that a pair right at the range
+//    or at a boundary between table entries may fall on the other side of it.
 // Periodic images: the tiles on the box faces are swept in blocks that reach across the face,
 // the offset added as the reference does, (xi - xj) + offset (SrWrapSeg below).
 // ===========================================================================
@@ -1085,17 +1089,40 @@ k_sr_sweep_blocks(const double *__restrict__ pos_r, const unsigned *__restrict__
 // the sweep's pair arithmetic, and reduces its sums in a fixed tree; a second kernel adds the
 // slices' partials in order and applies the receiver's rung factor.  Bit-reproducible; equal to
 // the cells sweep up to the order of the additions.
+// The rows come in `slots` slots (at most kSrSparseMax + 1); a slot below 0 is empty (the caller
+// asks for the rows on active rungs without learning how many there are: torch.nonzero_static
+// pads with -1), and a row in a slot beyond the kSrSparseMax-th means more receivers than this
+// sweep takes: CG_ERR_ACTIVE_OVERFLOW, they are not swept.
 // ===========================================================================
 constexpr int kSrSparseMax = 8, kSrSparseBlocks = 1024;
+// How many of the first kSrSparseMax slots hold a row (K), and the t-th of those rows in slot
+// order (0 for t >= K).  (Every thread of the caller finds the same K: the slots are only read.)
+__device__ __forceinline__ int sr_sparse_row(const i64 *__restrict__ active, int slots, int t,
+                                             i64 *row) {
+    int k = 0;
+    i64 mine = 0;
+#pragma unroll
+    for (int s = 0; s < kSrSparseMax; s++) {
+        const i64 i = s < slots ? active[s] : -1;
+        if (i >= 0) {
+            if (k == t) mine = i;
+            k++;
+        }
+    }
+    *row = mine;
+    return k;
+}
 __global__ __launch_bounds__(256) void k_sr_sparse(const double *__restrict__ pos_r,
-                                                   const i64 *__restrict__ active, int K,
+                                                   const i64 *__restrict__ active, int slots,
                                                    const double *__restrict__ pos_s, i64 n_s,
                                                    const double *__restrict__ table,
                                                    SrParams P, double *__restrict__ partial) {
     __shared__ double rx[kSrSparseMax], ry[kSrSparseMax], rz[kSrSparseMax];
     __shared__ double red[4][3 * kSrSparseMax];
+    i64 i;
+    const int K = sr_sparse_row(active, slots, (int)threadIdx.x, &i);   // (uniform)
+    if (K == 0) return;
     if (threadIdx.x < (unsigned)K) {
-        const i64 i = active[threadIdx.x];
         rx[threadIdx.x] = pos_r[3 * i];
         ry[threadIdx.x] = pos_r[3 * i + 1];
         rz[threadIdx.x] = pos_r[3 * i + 2];
@@ -1141,14 +1168,19 @@ __global__ __launch_bounds__(256) void k_sr_sparse(const double *__restrict__ po
     }
 }
 __global__ __launch_bounds__(64) void k_sr_sparse_final(const double *__restrict__ partial, int nb,
-                                                        const i64 *__restrict__ active, int K,
-                                                        SrParams P, double *__restrict__ dmom_r) {
+                                                        const i64 *__restrict__ active, int slots,
+                                                        SrParams P, double *__restrict__ dmom_r,
+                                                        unsigned *__restrict__ err_flags) {
     // one wave: lane e < 3K adds the nb partials of its entry in index order
     const int e = threadIdx.x;
-    if (e >= 3 * K) return;
+    if (e == 0)
+        for (int s = kSrSparseMax; s < slots; s++)
+            if (active[s] >= 0) atomicOr(err_flags, (unsigned)CG_ERR_ACTIVE_OVERFLOW);
+    i64 i;
+    const int K = sr_sparse_row(active, slots, e / 3, &i);
+    if (e >= 3 * K || nb == 0) return;
     double sum = 0;
     for (int b = 0; b < nb; b++) sum += partial[(i64)e * nb + b];
-    const i64 i = active[e / 3];
     const double factor = P.rung ? P.factors[P.rung_jumped[i]] : P.factor;
     dmom_r[3 * i + e % 3] += sum * factor;   // gravity.py:321-349 (factors[rung] * x * f)
 }
@@ -1156,11 +1188,11 @@ int cgk_shortrange_sparse(cg_ctx *c, const double *pos_r, const i64 *active, int
                           const double *pos_s, i64 n_s, const double *table,
                           double r2_index_scaling, double r2_max, double factor,
                           const double *factors, const signed char *rung_jumped) {
-    if (K < 1 || K > kSrSparseMax) {
-        cg_set_error("cg_shortrange_sparse: %d active receivers (1..%d)", K, kSrSparseMax);
+    if (K < 1 || K > kSrSparseMax + 1) {
+        cg_set_error("cg_shortrange_sparse: %d slots for active receivers (1..%d)", K,
+                     kSrSparseMax + 1);
         return 1;
     }
-    if (n_s == 0) return 0;
     SrParams P{c->p.boxsize, r2_index_scaling, r2_max, factor, 0,
                factors,      rung_jumped /* non-null = rungs in use */, rung_jumped, 0, nullptr,
                nullptr,      0};
@@ -1168,13 +1200,16 @@ int cgk_shortrange_sparse(cg_ctx *c, const double *pos_r, const i64 *active, int
     if (!c->sr_sparse_partial)
         CG_HIP(hipMalloc((void **)&c->sr_sparse_partial,
                          sizeof(double) * 3 * kSrSparseMax * kSrSparseBlocks));
+    // (no suppliers: the final kernel alone, which adds nothing and still checks the slots)
     i64 nbl = (n_s + 255) / 256;
     const int nb = (int)(nbl < kSrSparseBlocks ? nbl : kSrSparseBlocks);
-    hipLaunchKernelGGL(k_sr_sparse, dim3(nb), dim3(256), 0, c->stream, pos_r, active, K, pos_s, n_s,
-                       table, P, c->sr_sparse_partial);
-    CG_LAUNCH_CHECK();
+    if (nb > 0) {
+        hipLaunchKernelGGL(k_sr_sparse, dim3(nb), dim3(256), 0, c->stream, pos_r, active, K, pos_s,
+                           n_s, table, P, c->sr_sparse_partial);
+        CG_LAUNCH_CHECK();
+    }
     hipLaunchKernelGGL(k_sr_sparse_final, dim3(1), dim3(64), 0, c->stream, c->sr_sparse_partial, nb,
-                       active, K, P, dmom_r);
+                       active, K, P, dmom_r, c->err_flags);
     CG_LAUNCH_CHECK();
     return 0;
 }
@@ -1188,9 +1223,9 @@ int cgk_shortrange_sparse(cg_ctx *c, const double *pos_r, const i64 *active, int
 // every one gets a wavefront of its own — a cell in a clump may hold hundreds of them: the 5 x 5
 // columns x 5 cells around the cell are 25 runs of the suppliers' list (50 where the z range
 // wraps around the box) read where they are — 16 lanes per run, four runs per trip, nothing
-// staged, no barrier.  Same pair arithmetic ((xi - xj) + offset, r2, table
-// index bit-identical to the reference's); a receiver's sum is reduced over the wave in a fixed
-// order.
+// staged, no barrier.  Same pair arithmetic as the blocks ((xi - xj) + offset bit-identical to
+// the reference's, r2 within 1 ulp of it: sr_r2); a receiver's sum is reduced over the wave in a
+// fixed order.
 // ===========================================================================
 constexpr int kSaRuns = 52;  // 25 columns x 2 pieces, rounded up to whole trips of 4
 // (one atomic on the list's counter per 4096 cells: an atomic per wavefront — 94,000 of them on
@@ -1242,6 +1277,14 @@ __global__ __launch_bounds__(256) void k_sr_active_cells(const unsigned *__restr
     }
 }
 
+// The wave's own LDS stores before its lanes read each other's entries: a wave-scope release /
+// acquire around a wave barrier (no instruction of its own on gfx950, where a wave's LDS accesses
+// complete in order — it keeps the compiler from moving the loads above the stores).
+__device__ __forceinline__ void sr_wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 template <bool STATS>
 __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
     const double *__restrict__ pos_r, const unsigned *__restrict__ order_r,
@@ -1302,6 +1345,7 @@ __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
         r_cnt[wave][lane] = cnt;
         r_img[wave][lane] = img;
     }
+    sr_wave_lds_sync();   // (the lanes read each other's runs below)
     // The runs as ONE sequence of suppliers: r_pre[s] = suppliers in the runs before s (the
     // wave's own scan of the counts it has just written: lanes 0..51 hold them).  A lane takes
     // supplier t = trip * 64 + lane and finds its run by bisection of the 64 prefix sums (six
@@ -1312,6 +1356,7 @@ __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
         const unsigned incl = sr_wave_scan(mine);
         r_pre[wave][lane] = incl - mine;   // (lanes >= 52: the total)
     }
+    sr_wave_lds_sync();
     const unsigned total = r_pre[wave][63];
     const double L = P.boxsize;
     SrCount cnt;
@@ -1509,12 +1554,13 @@ int cgk_shortrange_sweep_cells(cg_ctx *c, const double *pos_r_sorted, const unsi
         }
         unsigned *count = c->sr_active, *list = c->sr_active + 64, *rows = list + n_active_max;
         CG_HIP(hipMemsetAsync(count, 0, 4, c->stream));
+        // (a bound of 0 lists nobody, but an active receiver still raises the flag)
+        hipLaunchKernelGGL(k_sr_active_cells,
+                           dim3((unsigned)((ncells + 256 * kSaPerThread - 1) / (256 * kSaPerThread))), dim3(256),
+                           0, c->stream, nact_r, off_r, (unsigned)ncells, list, rows, count,
+                           (unsigned)n_active_max, c->err_flags);
+        CG_LAUNCH_CHECK();
         if (n_active_max > 0) {
-            hipLaunchKernelGGL(k_sr_active_cells,
-                               dim3((unsigned)((ncells + 256 * kSaPerThread - 1) / (256 * kSaPerThread))), dim3(256),
-                               0, c->stream, nact_r, off_r, (unsigned)ncells, list, rows, count,
-                               (unsigned)n_active_max, c->err_flags);
-            CG_LAUNCH_CHECK();
             hipLaunchKernelGGL(P.stats ? k_sr_sweep_active_cells<true> : k_sr_sweep_active_cells<false>,
                                dim3((unsigned)(((n_active_max + 3) / 4 + 7) / 8 * 8)), dim3(256), 0,
                                c->stream, pos_r_sorted, order_r, off_r, dmom_r, pos_s_sorted, off_s, table, P,

@@ -21,7 +21,8 @@
 //  * the quads that are left are evaluated exactly as the cells sweep evaluates a row of
 //    suppliers — 16 receivers x 4 suppliers per trip, (xi - xj) + offset, r2, the range test,
 //    table[int(r2*scaling)], three multiply-adds in FP64 — every contribution bit-identical to the
-//    cells sweep's, only the order of the additions differs.  All 64 lanes work in every trip:
+//    cells sweep's (r2 by the same sr_r2, within 1 ulp of the reference's: a table index may
+//    differ from the reference's at a boundary), only the order of the additions differs.  All 64 lanes work in every trip:
 //    no per-lane candidate lists.
 // Measured on a Gaussian blob of the bench's clustered box (profiles/HISTORY_design_r1_r5.md §16b): 2.1-2.6 pair
 // tests per pair in range in tiles of 256 particles and more, 3.2 at 128-256, 4.1 at 64-128
@@ -775,6 +776,21 @@ int srd_look_slot(cg_ctx *c, const unsigned *off, i64 nt, int min_pop) {
             return i;
     return -1;
 }
+// The streak (srd_quiet) counts the looks in the order they were taken, up to look `upto`
+// (exclusive), waiting for the ones whose result is not known yet — so that it depends on the
+// sequence of calls alone, never on whether an event happens to have completed.
+int srd_count_looks(cg_ctx *c, unsigned long long upto) {
+    for (; c->srd_counted < upto; c->srd_counted++) {
+        const int i = (int)(c->srd_counted % kdLooks);
+        cg_ctx::SrdLook &K = c->srd_look[i];
+        if (!K.harvested) {
+            CG_HIP(hipEventSynchronize(K.ev));
+            K.harvested = true;
+        }
+        c->srd_quiet = c->srd_host[16 + 8 * i] == 0 ? c->srd_quiet + 1 : 0;
+    }
+    return 0;
+}
 }  // namespace
 int cgk_shortrange_dense_look(cg_ctx *c, const unsigned *off_cells, i64 nt) {
     for (int i = 0; i < kdLooks; i++)   // whatever was known about this address is stale now
@@ -784,8 +800,10 @@ int cgk_shortrange_dense_look(cg_ctx *c, const unsigned *off_cells, i64 nt) {
     const i64 ntiles = nt * nt * nt, ncells = 8 * ntiles;
     if (!c->srd_host) CG_HIP(hipHostMalloc((void **)&c->srd_host, 256));
     if (srd_reserve(c, (void **)&c->srd_small, &c->srd_small_bytes, 256)) return 1;
-    const int slot = c->srd_look_next;
-    c->srd_look_next = (slot + 1) % kdLooks;
+    // (the slot's look, taken kdLooks looks ago, is counted before it is replaced)
+    if (c->srd_looks >= kdLooks && srd_count_looks(c, c->srd_looks - kdLooks + 1)) return 1;
+    const int slot = (int)(c->srd_looks % kdLooks);
+    c->srd_looks++;
     cg_ctx::SrdLook &L = c->srd_look[slot];
     if (!L.ev) CG_HIP(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
     // device words 16 + 8 slot: [0] particles in dense tiles, [1] dense tiles, [4..5] sum pop^2
@@ -832,24 +850,20 @@ int cgk_shortrange_dense(cg_ctx *c, const double *pos_r_sorted, const unsigned *
         if (cgk_shortrange_dense_look(c, off_r, nt)) return 1;
         lr = srd_look_slot(c, off_r, nt, min_pop);
     }
-    // The looks that have completed since the last call: how many in a row found nothing dense.
-    // While that has been so for a while (a box without clumps: every sub-step of a rung loop)
-    // a look that is still on its way is not waited for — its sweep goes without the dense
-    // tiles' form, which is a matter of speed alone, and the host keeps queueing (the wait had
-    // the GPU idle once per sub-step until the sweep's launch arrived).  A look that finds
-    // dense tiles ends the streak; the sweeps after it wait again.
-    for (int i = 0; i < kdLooks; i++) {
-        cg_ctx::SrdLook &K = c->srd_look[i];
-        if (K.ev && !K.harvested && hipEventQuery(K.ev) == hipSuccess) {
-            K.harvested = true;
-            c->srd_quiet = c->srd_host[16 + 8 * i] == 0 ? c->srd_quiet + 1 : 0;
-        }
-    }
+    // How many looks in a row found nothing dense, counted up to the one taken kdLooks - 1
+    // looks before the newest (long finished: waiting for it costs nothing).  While that has
+    // been so for a while (a box without clumps: every sub-step of a rung loop) a look whose
+    // result is not known yet is not waited for — its sweep goes without the dense tiles' form,
+    // which is a matter of speed alone, and the host keeps queueing (the wait had the GPU idle
+    // once per sub-step until the sweep's launch arrived).  A look that finds dense tiles ends
+    // the streak; once it is counted, the sweeps wait again.  The choice depends on the sequence
+    // of calls alone, not on host timing (the two forms add in different orders).
+    if (c->srd_looks >= kdLooks - 1 && srd_count_looks(c, c->srd_looks - (kdLooks - 1)))
+        return 1;
     if (!c->srd_look[lr].harvested) {
         if (c->srd_quiet >= 2 * kdLooks && !by_threshold) return 0;
         CG_HIP(hipEventSynchronize(c->srd_look[lr].ev));
         c->srd_look[lr].harvested = true;
-        c->srd_quiet = c->srd_host[16 + 8 * lr] == 0 ? c->srd_quiet + 1 : 0;
     }
     const unsigned *hr = c->srd_host + 16 + 8 * lr;
     const i64 ndense = hr[0], tdense = hr[1], n_r = hr[2];

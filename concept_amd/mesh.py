@@ -580,9 +580,9 @@ class PotentialMesh:
                 'on the exact path')
         if flags & lib.CG_ERR_ACTIVE_OVERFLOW:
             raise lib.ConceptGPUError(
-                'cg_shortrange_sweep_cells_active: more receivers on active rungs than the bound '
-                'it was given (the rung populations lag behind the rung array); the receivers '
-                'beyond it got no short-range kick')
+                'cg_shortrange_sweep_cells_active / cg_shortrange_sparse: more receivers on '
+                'active rungs than the bound it was given (the rung populations lag behind the '
+                'rung array); the receivers beyond it got no short-range kick')
         if flags & lib.CG_ERR_BUCKET_OVERFLOW:
             raise lib.ConceptGPUError(
                 'cg_gather_kick_drift_scatter: a (tile, bucket) outgrew its predicted region; '
@@ -772,15 +772,21 @@ class PotentialMesh:
     SHORTRANGE_BY_CELL_MAX = 0.16
 
     def shortrange_sparse(self, pos_r, active, dmom_r, pos_s, table, r2_index_scaling, r2_max,
-                          factor, rungs=None):
+                          factor, rungs=None, overflow_slot=False):
         """The short-range sums of the receivers in rows `active` (int64 CUDA tensor, at most
-        SHORTRANGE_SPARSE_MAX of them) against all suppliers, without a cell list
-        (cg_shortrange_sparse).  rungs: (factors, rung_jumped) or None with `factor`."""
+        SHORTRANGE_SPARSE_MAX of them; a row below 0 is an empty slot and skipped) against all
+        suppliers, without a cell list (cg_shortrange_sparse).  rungs: (factors, rung_jumped)
+        or None with `factor`.  overflow_slot: `active` may hold one slot more
+        (commons.sparse_rows); a row in it is not swept and raises CG_ERR_ACTIVE_OVERFLOW."""
         self._check_particles(pos_r, dmom_r)
         self._check_particles(pos_s)
         k = active.numel()
         if active.dtype != torch.int64 or not active.is_cuda:
             raise lib.ConceptGPUError('active rows must be an int64 CUDA tensor')
+        if not 1 <= k <= self.SHORTRANGE_SPARSE_MAX + bool(overflow_slot):
+            raise lib.ConceptGPUError(
+                f'shortrange_sparse: {k} active receivers (1..{self.SHORTRANGE_SPARSE_MAX}'
+                + (', and the overflow slot)' if overflow_slot else ')'))
         factors, rung_jumped = rungs if rungs is not None else (None, None)
         check(_L.cg_shortrange_sparse(
             self._ctx, _ptr(pos_r), _ptr(active), int(k), _ptr(dmom_r), _ptr(pos_s),

@@ -7,6 +7,7 @@ cg_shortrange_sweep_rungs), and of pairing_level='domain' with gravity_pairwise 
 gravity_pairwise_nonperiodic (direct summation with and without the Ewald
 correction, component_component_pp below).  The pair loops run in
 libconcept_gpu.so (cg_shortrange.hip, cg_pp.hip)."""
+import contextlib
 import math
 import os
 
@@ -90,7 +91,25 @@ def _pair_integrals(ᔑdt_rungs, rec, sup):
 
 
 sparse_sweeps = 0   # sweeps taken without a cell list (a handful of active receivers)
-by_receiver_meshes = {}   # meshes that took a sweep by active receiver since the time loop looked
+# meshes that took a sweep bounded by the rung populations (without a cell list, or by active
+# receiver) since their CG_ERR_ACTIVE_OVERFLOW was looked at
+by_receiver_meshes = {}
+_deferred_checks = 0
+
+
+@contextlib.contextmanager
+def deferred_active_checks():
+    """The sweeps inside leave CG_ERR_ACTIVE_OVERFLOW (more receivers on active rungs than the
+    rung populations said: some of them got no kick) to the caller, who looks at the meshes
+    of by_receiver_meshes later (the rung loop: once per base step, RungStepper._check_sweeps,
+    so that its sub-steps do not wait for the GPU).  Outside, component_component() looks
+    itself before it returns."""
+    global _deferred_checks
+    _deferred_checks += 1
+    try:
+        yield
+    finally:
+        _deferred_checks -= 1
 
 
 def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
@@ -165,8 +184,11 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
             supp_cells[id(c)] = build(supp_pos[id(c)], nt, tile_extent)
 
     def active_rows(rec):
-        """rows of the receiver's particles on active rungs when they are few (one domain:
-        rungs_N counts them without looking), else None"""
+        """rows of the receiver's particles on active rungs when the populations say they are
+        few (one domain: rungs_N counts them without looking), else None.  What the rows are is
+        found on the GPU (commons.sparse_rows), not trusted to the populations: every row on an
+        active rung is swept, however many the populations claim, and more than the sweep can
+        take raise CG_ERR_ACTIVE_OVERFLOW"""
         if multi or not rec.use_rungs or rec.lowest_active_rung <= 0:
             return None
         n_active = sum(rec.rungs_N[rec.lowest_active_rung:])
@@ -174,18 +196,9 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
             return None
         key_ = (id(rec), rec.lowest_active_rung)
         if key_ not in sparse_rows:
-            # (the populations say how many there are: the rows are found without the host
-            # waiting for their number — torch.nonzero() would drain the stream, the sweep of
-            # the sub-step before included, once per such sub-step)
-            mask = rec.rung_indices >= rec.lowest_active_rung
-            if hasattr(torch, 'nonzero_static'):
-                sparse_rows[key_] = torch.nonzero_static(mask, size=n_active).flatten()
-            else:
-                sparse_rows[key_] = torch.nonzero(mask).flatten()
-        rows_ = sparse_rows[key_]
-        # (the populations are bookkeeping of the time loop: should they lag behind the rung
-        # array, the cells sweep takes over)
-        return rows_ if rows_.numel() <= mesh.SHORTRANGE_SPARSE_MAX else None
+            sparse_rows[key_] = commons.sparse_rows(rec.rung_indices >= rec.lowest_active_rung,
+                                                    mesh.SHORTRANGE_SPARSE_MAX)
+        return sparse_rows[key_]
     sparse_rows = {}
     key = 'a**(-3*w_eff₀-3*w_eff₁-1)'
     done = set()
@@ -211,15 +224,18 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
                     if rows is not None:
                         # the sub-steps for the highest rungs (main.py:1347-1624): a handful
                         # of receivers against all suppliers, no cell list
+                        # (launched when the populations claim none too: the kernels leave at
+                        # once when no row is valid)
                         global sparse_sweeps
                         sparse_sweeps += 1
-                        if rows.numel():
-                            rec.flush_begin()
-                            sup.flush_begin()
-                            mesh.shortrange_sparse(rec.pos, rows, rec.Δmom,
-                                                   supp_pos[id(sup)] if multi else sup.pos,
-                                                   table, scaling, r2_max, 0.0,
-                                                   (factors, rec.rung_indices_jumped))
+                        rec.flush_begin()
+                        sup.flush_begin()
+                        by_receiver_meshes[id(mesh)] = mesh
+                        mesh.shortrange_sparse(rec.pos, rows, rec.Δmom,
+                                               supp_pos[id(sup)] if multi else sup.pos,
+                                               table, scaling, r2_max, 0.0,
+                                               (factors, rec.rung_indices_jumped),
+                                               overflow_slot=True)
                         return
                     get_cells(sup)
                     rc = get_cells(rec)
@@ -247,6 +263,10 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
             if not same and s in receivers:
                 # the reference kicks both partners of a pair (Δmom_s -= ..., gravity.py:341-349)
                 sweep(s, r, False)
+    # a sweep bounded by the populations met more active receivers than they said: an error,
+    # not a kick silently lost (one wait for the GPU; the rung loop defers it)
+    if not _deferred_checks and by_receiver_meshes.pop(id(mesh), None) is not None:
+        mesh.check_errors()
 
 
 _ewald_grids = {}

@@ -351,11 +351,14 @@ class RungStepper:
     def _gravity_short(self):
         """every short-range interaction once (main.py:1249-1262, 1559-1576); returns the
         receivers"""
+        from . import shortrange
         receivers_all = []
-        for force, method, receivers, suppliers in self._shortrange_interactions():
-            getattr(interactions, force)(method, receivers, suppliers, self.ᔑdt_rungs,
-                                         'short-range', False)
-            receivers_all += [r for r in receivers if r not in receivers_all]
+        # (the sweeps' CG_ERR_ACTIVE_OVERFLOW is looked at once per base step, _check_sweeps)
+        with shortrange.deferred_active_checks():
+            for force, method, receivers, suppliers in self._shortrange_interactions():
+                getattr(interactions, force)(method, receivers, suppliers, self.ᔑdt_rungs,
+                                             'short-range', False)
+                receivers_all += [r for r in receivers if r not in receivers_all]
         return receivers_all
 
     # -- main.kick_long (main.py:1104-1144) -----------------------------------
@@ -398,6 +401,7 @@ class RungStepper:
             for c in receivers_all:
                 c.apply_Δmom()
                 c.convert_Δmom_to_acc(self.ᔑdt_rungs)
+        self._check_sweeps()
 
     # -- main.initialize_rung_populations (main.py:1639-1659) -----------------
     def initialize_rung_populations(self, Δt):
@@ -496,12 +500,15 @@ class RungStepper:
         self._check_sweeps()
 
     def _check_sweeps(self):
-        """once per base step: did a sweep by active receiver meet more of them than the rung
-        populations said (cg_error_flags of the meshes that took such sweeps)?"""
+        """once per base step: did a sweep bounded by the rung populations (without a cell
+        list, or by active receiver) meet more active receivers than they said (cg_error_flags
+        of the meshes that took such sweeps)?"""
         from . import shortrange
-        for mesh in list(shortrange.by_receiver_meshes.values()):
-            mesh.check_errors()
-        shortrange.by_receiver_meshes.clear()
+        try:
+            for mesh in list(shortrange.by_receiver_meshes.values()):
+                mesh.check_errors()
+        finally:
+            shortrange.by_receiver_meshes.clear()
 
     def _rung_integral_times(self, driftkick_index, rung_index, Δt, sync_time):
         """(index into ᔑdt_rungs, t_start, t_end) of the integrals rung `rung_index` needs in

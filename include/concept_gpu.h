@@ -316,8 +316,9 @@ int cg_tile_info(const cg_ctx *ctx, int64_t info[3]);
  * their positions (the sweep stages supplier runs with plain coalesced loads), offset_out[
  * (2 nt)^3 + 1] = first entry of each cell.  tile_extent must be boxsize/nt (species.py:607-609)
  * to within 4 ulp (the sweeps take boxsize/nt themselves; any other extent is refused).
- * cg_shortrange_sweep_cells[_rungs]: x_ji, r2 and the table index bit-identical to the
- * reference's, a receiver only meeting supplier cells at most two away:
+ * cg_shortrange_sweep_cells[_rungs]: x_ji bit-identical to the reference's, r2 within 1 ulp
+ * of it (fused multiply-adds: the range test and the table index may flip at a boundary), a
+ * receiver only meeting supplier cells at most two away:
  * dmom_r[order_r[q]] += ... for every receiver row q.  The force range
  * must not exceed the tile extent (the reference requires tilesize >= range,
  * species.py:3943-3983).  Receivers and suppliers may be different particle sets (two
@@ -411,11 +412,13 @@ int cg_shortrange_tiles(cg_ctx *ctx, const double *pos /*DEV 3n*/, int64_t n, in
  * sweep; out[6..7] unused. */
 int cg_shortrange_stats(cg_ctx *ctx, int enable, uint64_t *out /*HOST 8, or null*/);
 
-/* The same sums for k <= 8 receivers (rows active[0..k) of pos_r / dmom_r) against ALL n_s
- * suppliers, without a cell list: the sub-steps of driftkick_short (main.py:1347-1624) that kick
- * only the few particles of the highest rungs.  Nearest periodic image; the range must stay
- * below a quarter of the box (it does: >= 4 tiles of at least the range, species.py:3971).
- * factors / rung_jumped as in cg_shortrange_sweep_cells_rungs, or both null with `factor`. */
+/* The same sums for up to 8 receivers (rows active[0..k) of pos_r / dmom_r, k <= 9 slots; a
+ * slot below 0 is empty and skipped, a row in the ninth slot sets CG_ERR_ACTIVE_OVERFLOW and is
+ * not swept) against ALL n_s suppliers, without a cell list: the sub-steps of driftkick_short
+ * (main.py:1347-1624) that kick only the few particles of the highest rungs.  Nearest periodic
+ * image; the range must stay below a quarter of the box (it does: >= 4 tiles of at least the
+ * range, species.py:3971).  factors / rung_jumped as in cg_shortrange_sweep_cells_rungs, or
+ * both null with `factor`. */
 int cg_shortrange_sparse(cg_ctx *ctx, const double *pos_r /*DEV*/, const int64_t *active /*DEV k*/,
                          int k, double *dmom_r /*DEV, accumulated*/, const double *pos_s /*DEV*/,
                          int64_t n_s, const double *table /*DEV*/, int64_t tablesize,

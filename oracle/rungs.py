@@ -120,8 +120,13 @@ class Particles:
         self.set_rungs_N()
 
 
-def shortrange_kick_rungs(p, sr, G_Newton, dt_rungs):
-    """gravity('p3m', [c], [c], ᔑdt_rungs, 'short-range') with rungs: accumulates into p.dmom."""
+def shortrange_sweep_rungs(pos, rung, rung_jumped, lowest_active_rung, factors, *, boxsize, nt,
+                           table, maxr2, range_, dmom=None):
+    """The rung-weighted short-range sweep of one component on itself (orc_shortrange_sweep_rungs:
+    every pair once, both partners kicked when active, factors[rung_jumped[i]]), accumulated
+    into `dmom` (zeros when None) and returned.  factors = G*m*m*ᔑdt_rungs[pair][k] per rung
+    index k; table, maxr2 as oracle.shortrange_table() gives them.  Plain arrays only, so that
+    it serves any caller (a GPU test of one sub-step, a domain's worker)."""
     L = oracle.lib()
     if not hasattr(L, '_p3m_rungs'):
         dp, i64, dbl = oracle._dp, ctypes.c_int64, ctypes.c_double
@@ -130,14 +135,37 @@ def shortrange_kick_rungs(p, sr, G_Newton, dt_rungs):
                                                  bp, bp, ctypes.c_int]
         L.orc_shortrange_sweep_rungs.restype = ctypes.c_int
         L._p3m_rungs = True
-    factors = np.ascontiguousarray(G_Newton*p.mass*p.mass*dt_rungs[KEY_PAIR])  # gravity.py:63
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    n = pos.shape[0]
+    rung = np.ascontiguousarray(rung, dtype=np.int8)
+    rung_jumped = np.ascontiguousarray(rung_jumped, dtype=np.int8)
+    factors = np.ascontiguousarray(factors, dtype=np.float64)
+    table = np.ascontiguousarray(table, dtype=np.float64)
+    if rung.shape != (n,) or rung_jumped.shape != (n,):
+        raise ValueError('rung arrays must hold one entry per particle')
+    if n and int(rung_jumped.max()) >= factors.size:
+        raise ValueError('a jumped rung index beyond the factors')
+    if dmom is None:
+        dmom = np.zeros((n, 3), dtype=np.float64)
+    if dmom.dtype != np.float64 or dmom.shape != (n, 3) or not dmom.flags.c_contiguous:
+        raise ValueError('dmom must be a contiguous float64 (N, 3) array')
     rc = L.orc_shortrange_sweep_rungs(
-        oracle._p(p.pos), p.N, oracle._p(p.dmom), sr['boxsize'], sr['nt'], sr['boxsize']/sr['nt'],
-        machine_eps, oracle._p(sr['table']), (sr['tablesize'] - 1)/sr['maxr2'], sr['range']**2,
-        oracle._p(factors), p.rung.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
-        p.rung_jumped.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), int(p.lowest_active_rung))
+        oracle._p(pos), n, oracle._p(dmom), boxsize, nt, boxsize/nt, machine_eps,
+        oracle._p(table), (table.size - 1)/maxr2, range_**2, oracle._p(factors),
+        rung.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)),
+        rung_jumped.ctypes.data_as(ctypes.POINTER(ctypes.c_int8)), int(lowest_active_rung))
     if rc:
         raise RuntimeError(f'orc_shortrange_sweep_rungs failed ({rc})')
+    return dmom
+
+
+def shortrange_kick_rungs(p, sr, G_Newton, dt_rungs):
+    """gravity('p3m', [c], [c], ᔑdt_rungs, 'short-range') with rungs: accumulates into p.dmom."""
+    assert sr['table'].size == sr['tablesize']
+    factors = G_Newton*p.mass*p.mass*np.asarray(dt_rungs[KEY_PAIR])  # gravity.py:63
+    shortrange_sweep_rungs(p.pos, p.rung, p.rung_jumped, p.lowest_active_rung, factors,
+                           boxsize=sr['boxsize'], nt=sr['nt'], table=sr['table'],
+                           maxr2=sr['maxr2'], range_=sr['range'], dmom=p.dmom)
 
 
 def new_dt_rungs(N_rungs):

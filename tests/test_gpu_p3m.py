@@ -2,7 +2,8 @@
 gravity('p3m', ...) end to end, against the reference-generated goldens and the
 CPU oracle.  Bars: tile index of every particle bit-exact; Δmom <= 1e-12 of the
 largest kick (pairs are summed in a different order than the reference's
-tile/subtile/rung walk; r2 and the table index of a pair are bit-identical)."""
+tile/subtile/rung walk; r2 of a pair is within 1 ulp of the reference's, so that its table
+index may flip at an entry boundary)."""
 import numpy as np
 import pytest
 

@@ -1,0 +1,569 @@
+"""The rung-weighted short-range sweeps of a sub-step (lowest active rung > 0) against the CPU
+rung oracle (oracle/rungs.shortrange_sweep_rungs: orc_shortrange_sweep_rungs, every pair once,
+factors by the JUMPED rung index, pinned to the reference by test_oracle_golden.py).
+
+  * every form the dispatch can take, called directly on the mesh: the plain list with rungs
+    (mode 1), the active-first list in blocks (mode 2: 2 x 2 blocks below 6 tiles a side, 4 x 2
+    with the table in LDS or read from memory), by active receiver, without a cell list, and the
+    dense tiles' form taking the tiles dense with active receivers;
+  * the dispatch of interactions.gravity() at the thresholds of the rung populations, with one
+    and with two receiver components, the form taken recorded by a spy;
+  * rung populations that disagree with the rung array: the oracle's answer or an error,
+    never a silent loss, never a row outside the particles touched;
+  * the dense tiles' decision after a quiet streak: the same form in every sweep whether the
+    host waits before every sweep or never.
+
+Bars: |got - ref| <= 1e-12 * s on the active rows, s = max(|ref|, max(factors)/scale^2); the
+inactive rows bit-equal to a random nonzero starting buffer.  Every case also checks that the
+data tell a wrong rung index apart: the oracle with rung_jumped := rung, and with the lowest
+active rung one off, differs from the reference by far more than the bar."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+RANGE = 1.0
+SCALE = RANGE/4.5
+SPARSE_MAX = 8
+TOL = 1e-12
+
+
+# ----------------------------------------------------------------------------------------------
+# cases: positions, rungs, factors, and the oracle's answers (cached per case)
+# ----------------------------------------------------------------------------------------------
+def _positions(rng, n, L, layout, blob=0.25, sigma=0.6):
+    pos = rng.uniform(0, L, (n, 3))
+    if layout == 'clustered':
+        # a blob wrapped around the box corner
+        k = int(blob*n)
+        pos[6:6 + k] = np.mod(rng.normal(0, sigma*RANGE, (k, 3)), L)
+    # receivers exactly on faces, edges and corners
+    pos[:6] = [[1e-9, L - 1e-9, 0.0], [L - 1e-9, 0.0, L/2], [0.0, 0.0, 0.0],
+               [L - 1e-9, L - 1e-9, L - 1e-9], [L/2, 1e-9, L - 1e-9], [1e-9, L/3, 0.0]]
+    return np.ascontiguousarray(np.minimum(pos, np.nextafter(L, 0)))
+
+
+def _rungs(rng, n, N_rungs, top_rows=(0, 1, 2), next_rows=(3, 4, 5, 6)):
+    """rungs 0 .. N_rungs-1, every one populated: the top rung 3 particles and the one below 4
+    (the sweep without a cell list for the two highest lowest-active-rungs), the rest falling
+    off geometrically; about a fifth of the particles on rungs >= 1 flagged to jump up
+    (+2 N_rungs) or down (+N_rungs), at least one of them on every rung >= 1"""
+    top = N_rungs - 1
+    rung = np.minimum(rng.geometric(0.45, n) - 1, top - 2).astype(np.int8)
+    rung[list(top_rows)] = top
+    rung[list(next_rows)] = top - 1
+    for r in range(1, top - 1):   # (at least a few on every rung below)
+        rows = rng.choice(np.arange(8, n), 4, replace=False)
+        rung[rows] = r
+    jumped = rung.copy()
+    flag = (rng.random(n) < 0.2) & (rung >= 1)
+    for r in range(1, top + 1):   # at least one flagged per rung >= 1
+        flag[np.flatnonzero(rung == r)[0]] = True
+    up = flag & (rng.random(n) < 0.5) & (rung < top)
+    down = flag & ~up
+    jumped[up] += 2*N_rungs
+    jumped[down] += N_rungs
+    return rung, jumped
+
+
+class Case:
+    """One box: positions (receivers = suppliers, or two sets), rungs, factors, tables."""
+
+    def __init__(self, nt, layout, N_rungs, tablesize, two=False, seed=0, n=None, blob=0.25,
+                 sigma=0.6, blob_rungs=None):
+        from oracle import oracle
+        rng = np.random.default_rng([nt, N_rungs, tablesize, int(two), seed])
+        self.nt, self.N_rungs, self.tablesize, self.two = nt, N_rungs, tablesize, two
+        self.L = L = nt*RANGE*1.03
+        n = n or {4: 2500, 5: 4500, 6: 7000, 7: 11000}.get(nt, 28000)
+        self.pos = _positions(rng, n, L, layout, blob, sigma)
+        self.rung, self.jumped = _rungs(rng, n, N_rungs)
+        if blob_rungs is not None:   # the blob's particles on the upper rungs
+            k = int(blob*n)
+            self.rung[6:6 + k] = rng.integers(blob_rungs[0], blob_rungs[1] + 1, k)
+            self.jumped[6:6 + k] = self.rung[6:6 + k]
+            f = rng.choice(np.arange(6, 6 + k), k//10, replace=False)
+            self.jumped[f] += N_rungs
+        self.pos_s = _positions(rng, int(0.8*n), L, layout, blob, sigma) if two else None
+        self.factors = rng.uniform(0.5, 2.0, 3*N_rungs - 1)
+        self.softening = 0.03*L/np.cbrt(n)
+        self.table, self.maxr2 = oracle.shortrange_table(self.softening, SCALE, RANGE, tablesize)
+        self.scaling = (tablesize - 1)/self.maxr2
+        self.s_pair = self.factors.max()/SCALE**2
+        self._ref = {}
+
+    def oracle(self, lowest, jumped=None):
+        """the oracle's Δmom of the receivers for this lowest active rung (cached); jumped:
+        another rung_jumped array (the check that a wrong index would show)"""
+        from oracle import rungs as orungs
+        key = (lowest, None if jumped is None else jumped.tobytes())
+        if key in self._ref:
+            return self._ref[key]
+        rj = self.jumped if jumped is None else jumped
+        kw = dict(boxsize=self.L, nt=self.nt, table=self.table, maxr2=self.maxr2,
+                  range_=RANGE)
+        if not self.two:
+            out = orungs.shortrange_sweep_rungs(self.pos, self.rung, rj, lowest, self.factors,
+                                                **kw)
+        else:
+            # receivers that are not the suppliers: the union with equal masses, less the
+            # receivers among themselves (the sums are linear in the suppliers); the suppliers
+            # sit on rung 0, below every lowest active rung, so that they receive nothing
+            n, m = len(self.pos), len(self.pos_s)
+            both = orungs.shortrange_sweep_rungs(
+                np.concatenate([self.pos, self.pos_s]),
+                np.concatenate([self.rung, np.zeros(m, np.int8)]),
+                np.concatenate([rj, np.zeros(m, np.int8)]), lowest, self.factors, **kw)[:n]
+            alone = orungs.shortrange_sweep_rungs(self.pos, self.rung, rj, lowest, self.factors,
+                                                  **kw)
+            out = both - alone
+        self._ref[key] = out
+        return out
+
+    def check_distinct(self, lowest, ref, tol):
+        """the data tell a wrong jumped index and a wrong lowest active rung apart"""
+        active = self.rung >= lowest
+        flagged = active & (self.jumped != self.rung)
+        assert flagged.any()
+        wrong = self.oracle(lowest, jumped=self.rung.copy())
+        assert np.abs(wrong - ref)[flagged].max() > 1e4*tol, 'a wrong jumped index would pass'
+        for other in (lowest - 1, lowest + 1):
+            assert np.abs(self.oracle(other) - ref).max() > 1e4*tol, \
+                f'lowest active rung {other} would pass for {lowest}'
+
+
+_cases = {}
+
+
+def get_case(*args, **kw):
+    key = (args, tuple(sorted(kw.items())))
+    if key not in _cases:
+        _cases[key] = Case(*args, **kw)
+    return _cases[key]
+
+
+def _check(case, lowest, got, base, what):
+    """got (CUDA) against base + the oracle's kick: active rows to the bar, the others bit-equal
+    to the starting buffer, the kick nonzero"""
+    got, base = got.cpu().numpy(), base.cpu().numpy()
+    ref = case.oracle(lowest)
+    s = max(np.abs(ref).max(), case.s_pair)
+    active = case.rung >= lowest
+    assert np.array_equal(got[~active], base[~active]), f'{what}: an inactive row was touched'
+    err = np.abs(got[active] - (base[active] + ref[active])).max()
+    assert err <= TOL*s, f'{what}: lowest active rung {lowest}: error {err:.3e} of {s:.3e}'
+    assert np.abs(got[active] - base[active]).max() > 0, f'{what}: no kick'
+    return ref, s
+
+
+# ----------------------------------------------------------------------------------------------
+# 1. every form against the oracle, every lowest active rung
+# ----------------------------------------------------------------------------------------------
+CASES = [
+    (4, 'uniform', 8, 4096, False),      # m < 4: the small-box kernels
+    (5, 'clustered', 10, 4096, False),   # m < 4, a blob around the corner
+    (6, 'uniform', 10, 2**13, True),     # 4 x 2 blocks, the table read from memory, two sets
+    (7, 'clustered', 8, 4096, False),    # odd: the last 4 x 2 block cut short
+    (10, 'uniform', 10, 4096, False),    # 4 x 2 blocks with the table in LDS
+    (10, 'clustered', 8, 2**13, True),
+]
+
+
+def _ids(c):
+    return f'nt{c[0]}-{c[1]}-r{c[2]}-t{c[3]}' + ('-two' if c[4] else '')
+
+
+@pytest.mark.parametrize('dense', ['default', '3'])
+@pytest.mark.parametrize('spec', CASES, ids=[_ids(c) for c in CASES])
+def test_every_sweep_form_against_the_rung_oracle(spec, dense, monkeypatch):
+    import torch
+    from concept_amd import commons
+    from concept_amd.mesh import PotentialMesh
+    if dense == '3':
+        monkeypatch.setenv('CONCEPT_GPU_SR_DENSE_MIN', '3')
+    else:
+        monkeypatch.delenv('CONCEPT_GPU_SR_DENSE_MIN', raising=False)
+    case = get_case(*spec)
+    nt, L, N_rungs = case.nt, case.L, case.N_rungs
+    mesh = PotentialMesh(32, L)
+    dev = 'cuda'
+    pos = torch.as_tensor(case.pos, device=dev)
+    pos_s = torch.as_tensor(case.pos_s, device=dev) if case.two else pos
+    rung = torch.as_tensor(case.rung, device=dev)
+    jumped = torch.as_tensor(case.jumped, device=dev)
+    factors = torch.as_tensor(case.factors, device=dev)
+    table = torch.as_tensor(case.table, device=dev)
+    rng = np.random.default_rng(7)
+    base = torch.as_tensor(rng.normal(0, 1e-3*case.s_pair, case.pos.shape), device=dev)
+    ext = L/nt
+    plain = mesh.shortrange_cells(pos, nt, ext)
+    cs = mesh.shortrange_cells(pos_s, nt, ext) if case.two else None
+    args = (table, case.scaling, RANGE**2, 0.0)
+    for lowest in range(1, N_rungs):
+        rungs = (factors, rung, jumped, lowest)
+        n_active = int((case.rung >= lowest).sum())
+        in_blocks = mesh.shortrange_cells(pos, nt, ext, (rung, jumped, lowest), True)
+        by_cell = mesh.shortrange_cells(pos, nt, ext, (rung, jumped, lowest))
+        forms = {
+            'plain list (mode 1)': (plain, None),
+            'active-first in blocks': (in_blocks, None),
+            'by active receiver': (by_cell, n_active),
+            'by active receiver, jumps in list order': (in_blocks, n_active),
+        }
+        for what, (cells, bound) in forms.items():
+            got = base.clone()
+            # (the suppliers' list: the receivers' own one, as component_component passes it)
+            mesh.shortrange_sweep_cells(cells, got, cs if case.two else cells, nt, *args[:3],
+                                        0.0, rungs, bound)
+            ref, s = _check(case, lowest, got, base, what)
+        if n_active <= SPARSE_MAX:
+            got = base.clone()
+            rows = commons.sparse_rows(rung >= lowest, SPARSE_MAX)
+            mesh.shortrange_sparse(pos, rows, got, pos_s, *args[:3], 0.0, (factors, jumped),
+                                   overflow_slot=True)
+            _check(case, lowest, got, base, 'without a cell list')
+        assert mesh.error_flags() == 0
+        case.check_distinct(lowest, ref, TOL*s)
+    mesh.close()
+
+
+def test_sparse_sweep_slots():
+    """The rows of the sweep without a cell list as commons.sparse_rows hands them on: empty
+    slots (-1) anywhere are skipped and touch nothing; a row in the overflow slot is not swept
+    and raises CG_ERR_ACTIVE_OVERFLOW; without overflow_slot more than 8 rows, and with it
+    more than 9, are refused at once."""
+    import torch
+    from concept_amd.lib import ConceptGPUError
+    from concept_amd.mesh import PotentialMesh
+    case = get_case(7, 'clustered', 8, 4096, False)
+    L, dev = case.L, 'cuda'
+    mesh = PotentialMesh(32, L)
+    pos = torch.as_tensor(case.pos, device=dev)
+    jumped = torch.as_tensor(case.jumped, device=dev)
+    factors = torch.as_tensor(case.factors, device=dev)
+    table = torch.as_tensor(case.table, device=dev)
+    base = torch.as_tensor(np.random.default_rng(3).normal(0, 1e-3, case.pos.shape), device=dev)
+    lowest = case.N_rungs - 2            # 7 active receivers
+    active = np.flatnonzero(case.rung >= lowest)
+    assert active.size == 7
+    args = (table, case.scaling, RANGE**2, 0.0, (factors, jumped))
+
+    def sweep(slots, **kw):
+        got = base.clone()
+        mesh.shortrange_sparse(pos, torch.as_tensor(np.asarray(slots, np.int64), device=dev), got,
+                               pos, *args, **kw)
+        return got
+    # empty slots between and after the rows: the same as the rows alone
+    packed = sweep(active)
+    _check(case, lowest, packed, base, 'rows alone')
+    holes = [-1, active[0], -1, *active[1:4], -1, *active[4:]]
+    assert len(holes) == 10
+    with pytest.raises(ConceptGPUError, match='active receivers'):
+        sweep(holes, overflow_slot=True)
+    gappy = sweep([active[0], -1, *active[1:], -1], overflow_slot=True)
+    _check(case, lowest, gappy, base, 'rows with empty slots')
+    assert mesh.error_flags() == 0
+    # nothing but empty slots: nothing touched, nothing flagged
+    assert bool((sweep([-1]*9, overflow_slot=True) == base).all())
+    assert mesh.error_flags() == 0
+    # a row in the overflow slot: flagged, and the row itself is not swept
+    extra = int(np.flatnonzero(case.rung < lowest)[0])
+    over = sweep([*active, -1, extra], overflow_slot=True)
+    with pytest.raises(ConceptGPUError, match='more receivers on active rungs'):
+        mesh.check_errors()
+    assert bool((over[extra] == base[extra]).all())
+    # without the overflow slot nine rows are refused at once
+    with pytest.raises(ConceptGPUError, match='active receivers'):
+        sweep(list(range(9)))
+    assert mesh.error_flags() == 0
+    mesh.close()
+
+
+def test_dense_form_by_default_on_a_clustered_box(monkeypatch):
+    """A box whose corner blob holds thousands of particles per tile, its particles on the
+    upper rungs: with the default threshold (64) and cost model the sub-step's sweep hands the
+    tiles dense with active receivers to the dense tiles' form (the counters show it) — against
+    the oracle, for a plain and an active-first list."""
+    import torch
+    from concept_amd.mesh import PotentialMesh
+    monkeypatch.delenv('CONCEPT_GPU_SR_DENSE_MIN', raising=False)
+    case = get_case(10, 'clustered', 8, 4096, False, n=40000, blob=0.6, sigma=0.45,
+                    blob_rungs=(1, 4))
+    nt, L = case.nt, case.L
+    dev = 'cuda'
+    pos = torch.as_tensor(case.pos, device=dev)
+    rung = torch.as_tensor(case.rung, device=dev)
+    jumped = torch.as_tensor(case.jumped, device=dev)
+    factors = torch.as_tensor(case.factors, device=dev)
+    table = torch.as_tensor(case.table, device=dev)
+    base = torch.as_tensor(np.random.default_rng(8).normal(0, 1e-3*case.s_pair, case.pos.shape),
+                           device=dev)
+    for lowest in (1, 2):
+        for form in ('plain', 'blocks'):
+            outs = []
+            for stats in (False, True):
+                # (a context of its own: no streak of quiet looks before)
+                mesh = PotentialMesh(32, L)
+                cells = (mesh.shortrange_cells(pos, nt, L/nt) if form == 'plain' else
+                         mesh.shortrange_cells(pos, nt, L/nt, (rung, jumped, lowest), True))
+                if stats:
+                    mesh.shortrange_stats(True)
+                got = base.clone()
+                mesh.shortrange_sweep_cells(cells, got, cells, nt, table, case.scaling,
+                                            RANGE**2, 0.0, (factors, rung, jumped, lowest))
+                if stats:
+                    assert mesh.shortrange_stats(False)['dense'][0] > 0, 'dense form not taken'
+                outs.append(got)
+                mesh.close()
+            ref, s = _check(case, lowest, outs[0], base, f'{form}, dense by default')
+            case.check_distinct(lowest, ref, TOL*s)
+
+
+# ----------------------------------------------------------------------------------------------
+# 2. and 3. the dispatch of interactions.gravity() at the population thresholds, and with
+#    populations that disagree with the rung array
+# ----------------------------------------------------------------------------------------------
+N_DISPATCH = 6000
+NT_DISPATCH = 10
+
+
+def _setup_components(names, N_rungs=8, seed=0):
+    import torch
+    from concept_amd import commons
+    from concept_amd.species import Component
+    L = NT_DISPATCH*RANGE*1.03
+    commons.load_params({
+        'boxsize': L, 'N_rungs': N_rungs,
+        'potential_options': {'gridsize': {'gravity': {'p3m': 32}}},
+        'select_forces': {'all': {'gravity': 'p3m'}},
+        'select_softening_length': {'all': '0.03*boxsize/cbrt(N)'},
+        'shortrange_params': {'gravity': {'scale': SCALE, 'range': RANGE, 'tilesize': 1.02,
+                                          'tablesize': 4096}},
+    })
+    rng = np.random.default_rng(100 + seed)
+    comps = []
+    for name in names:
+        c = Component(name, 'matter', N=N_DISPATCH, mass=1.5)
+        assert c.use_rungs
+        c.populate(_positions(rng, N_DISPATCH, L, 'clustered'), 'pos')
+        c.populate(np.zeros((N_DISPATCH, 3)), 'mom')
+        comps.append(c)
+    integrals = rng.uniform(0.5, 2.0, 3*N_rungs - 1)
+    sdt = {('a**(-3*w_eff₀-3*w_eff₁-1)', a.name, b.name): integrals
+           for a in comps for b in comps}
+    return torch, commons.params, comps, integrals, sdt, L
+
+
+def _set_rungs(torch, c, k, lowest, rng):
+    """exactly k particles on rungs >= lowest (some flagged to jump), in the store's row order"""
+    n, nr = c.N, c.N_rungs
+    rung = rng.integers(0, lowest, n).astype(np.int8) if lowest > 0 else np.zeros(n, np.int8)
+    rows = rng.choice(n, k, replace=False)
+    rung[rows] = rng.integers(lowest, nr, k)
+    jumped = rung.copy()
+    for i in rows[::3]:
+        jumped[i] += nr if rung[i] == nr - 1 or i % 2 else 2*nr
+    c.rung_indices.copy_(torch.as_tensor(rung))
+    c.rung_indices_jumped.copy_(torch.as_tensor(jumped))
+    c.lowest_active_rung = lowest
+    c.set_rungs_N()
+    return rung, jumped
+
+
+def _oracle_gravity(comps, rungs, lowest, integrals, p, L):
+    """the oracle's Δmom of every component (equal masses: one union)"""
+    from oracle import oracle
+    from oracle import rungs as orungs
+    factors = p.G_Newton*comps[0].mass**2*integrals
+    table, maxr2 = oracle.shortrange_table(comps[0].softening_length, SCALE, RANGE, 4096)
+    pos = np.concatenate([c.pos.cpu().numpy() for c in comps])
+    out = orungs.shortrange_sweep_rungs(
+        pos, np.concatenate([r for r, _ in rungs]), np.concatenate([j for _, j in rungs]),
+        lowest, factors, boxsize=L, nt=NT_DISPATCH, table=table, maxr2=maxr2, range_=RANGE)
+    return np.split(out, len(comps)), factors.max()/SCALE**2
+
+
+def _spy(monkeypatch):
+    """records the form every sweep took"""
+    from concept_amd.mesh import PotentialMesh
+    taken = []
+    sparse, cells = PotentialMesh.shortrange_sparse, PotentialMesh.shortrange_sweep_cells
+
+    def spy_sparse(self, *a, **kw):
+        taken.append('sparse')
+        return sparse(self, *a, **kw)
+
+    def spy_cells(self, cells_r, *a, **kw):
+        # (dmom_r, cells_s, nt, table, r2_index_scaling, r2_max, factor, rungs, n_active)
+        rungs = kw.get('rungs', a[7] if len(a) > 7 else None)
+        n_active = kw.get('n_active', a[8] if len(a) > 8 else None)
+        if rungs is None or len(cells_r) == 3:
+            taken.append('plain')
+        else:
+            taken.append('blocks' if n_active is None else 'by receiver')
+        return cells(self, cells_r, *a, **kw)
+    monkeypatch.setattr(PotentialMesh, 'shortrange_sparse', spy_sparse)
+    monkeypatch.setattr(PotentialMesh, 'shortrange_sweep_cells', spy_cells)
+    return taken
+
+
+def _run_gravity(torch, comps, sdt, bases):
+    from concept_amd import interactions
+    for c, b in zip(comps, bases):
+        c.Δmom = b.clone()
+    interactions.gravity('p3m', comps, comps, sdt, 'short-range', False)
+    torch.cuda.synchronize()
+    return [c.Δmom.cpu().numpy() for c in comps]
+
+
+_BY_CELL = int(0.16*N_DISPATCH)
+THRESHOLDS = [(0, 2, 'sparse'), (1, 3, 'sparse'), (8, 2, 'sparse'), (9, 2, 'by receiver'),
+              (_BY_CELL, 1, 'by receiver'), (_BY_CELL + 1, 1, 'blocks'),
+              (N_DISPATCH - 1, 1, 'blocks'), (N_DISPATCH, 0, 'plain')]
+
+
+@pytest.mark.parametrize('ncomp', [1, 2])
+@pytest.mark.parametrize('k, lowest, form', THRESHOLDS,
+                         ids=[f'{k}-active-{f}' for k, _, f in THRESHOLDS])
+def test_dispatch_at_the_population_thresholds(k, lowest, form, ncomp, monkeypatch):
+    monkeypatch.delenv('CONCEPT_GPU_SR_DENSE_MIN', raising=False)
+    torch, p, comps, integrals, sdt, L = _setup_components(['a', 'b'][:ncomp], seed=k)
+    rng = np.random.default_rng(k + 10*ncomp)
+    rungs = [_set_rungs(torch, c, k, lowest, rng) for c in comps]
+    for c in comps:
+        assert sum(c.rungs_N[lowest:]) == k
+    bases = [torch.as_tensor(rng.normal(0, 1e-3, (c.N, 3)), device='cuda') for c in comps]
+    taken = _spy(monkeypatch)
+    outs = _run_gravity(torch, comps, sdt, bases)
+    # one sweep per (receiver, supplier) order: 1 for one component, 4 for two
+    assert taken == [form]*ncomp**2, taken
+    refs, s_pair = _oracle_gravity(comps, rungs, lowest, integrals, p, L)
+    for c, out, base, ref, (rung, _) in zip(comps, outs, bases, refs, rungs):
+        base = base.cpu().numpy()
+        active = rung >= lowest
+        assert np.array_equal(out[~active], base[~active])
+        if k:
+            s = max(np.abs(ref).max(), s_pair)
+            assert np.abs(out[active] - (base[active] + ref[active])).max() <= TOL*s
+            assert np.abs(out[active] - base[active]).max() > 0
+
+
+# (true active count, claimed count, what must happen)
+STALE = [
+    (5, 8, 'exact'),            # sparse range, overstated (wrote out of bounds before the fix)
+    (5, 2, 'exact'),            # sparse range, understated
+    (3, 0, 'exact'),            # none claimed, some active
+    (12, 6, 'raise'),           # claimed sparse, more than it takes
+    (6, 12, 'exact'),           # claimed by receiver, few active
+    (100, 150, 'exact'),        # by receiver, overstated
+    (100, 60, 'raise'),         # by receiver, understated
+    (100, 0, 'raise'),          # none claimed, many active
+    (100, 2000, 'exact'),       # claimed many (blocks), fewer active
+]
+
+
+@pytest.mark.parametrize('truth, claimed, outcome', STALE,
+                         ids=[f'{t}-active-{c}-claimed' for t, c, _ in STALE])
+def test_populations_that_disagree_with_the_rungs(truth, claimed, outcome, monkeypatch):
+    """interactions.gravity() with rung populations that over- or understate the receivers on
+    active rungs: the oracle's answer for the rung array as it stands, or ConceptGPUError; the
+    rows outside the active set bit-unchanged either way; a consistent call after an error
+    right."""
+    from concept_amd.lib import ConceptGPUError
+    monkeypatch.delenv('CONCEPT_GPU_SR_DENSE_MIN', raising=False)
+    torch, p, comps, integrals, sdt, L = _setup_components(['a'], seed=truth)
+    c, = comps
+    lowest = 3
+    rng = np.random.default_rng(truth*1000 + claimed)
+    rung, jumped = _set_rungs(torch, c, truth, lowest, rng)
+    consistent = list(c.rungs_N)
+    # (only the sum over the active rungs is asked)
+    stale = consistent[:lowest] + [claimed] + [0]*(c.N_rungs - lowest - 1)
+    c.rungs_N = stale
+    base = torch.as_tensor(rng.normal(0, 1e-3, (c.N, 3)), device='cuda')
+    (ref,), s_pair = _oracle_gravity(comps, [(rung, jumped)], lowest, integrals, p, L)
+    active = rung >= lowest
+    s = max(np.abs(ref).max(), s_pair)
+    base_h = base.cpu().numpy()
+    try:
+        out, = _run_gravity(torch, comps, sdt, [base])
+        raised = False
+    except ConceptGPUError as e:
+        assert 'more receivers on active rungs' in str(e)
+        raised = True
+        torch.cuda.synchronize()
+        out = c.Δmom.cpu().numpy()
+    assert raised == (outcome == 'raise'), f'{truth} active, {claimed} claimed: raised {raised}'
+    assert np.array_equal(out[~active], base_h[~active])
+    if not raised:
+        assert np.abs(out[active] - (base_h[active] + ref[active])).max() <= TOL*s
+    # the populations put right: the same call is right, and nothing is left flagged
+    c.rungs_N = consistent
+    out, = _run_gravity(torch, comps, sdt, [base])
+    assert np.array_equal(out[~active], base_h[~active])
+    assert np.abs(out[active] - (base_h[active] + ref[active])).max() <= TOL*s
+    assert np.abs(out[active] - base_h[active]).max() > 0
+
+
+# ----------------------------------------------------------------------------------------------
+# 4. the dense tiles' decision: the sequence of calls decides, not host timing
+# ----------------------------------------------------------------------------------------------
+def test_dense_decision_does_not_depend_on_host_timing(monkeypatch):
+    """On one context: a streak of quiet sub-steps on a uniform box (more than 2 x 4 looks),
+    then sub-steps on a box with a dense blob of active receivers, the dense threshold at its
+    default.  The whole sequence twice — with the host waiting for the GPU before every sweep,
+    and never — must take the same form in every sweep.  (Which form a sweep took shows in
+    the sweeps' counters: pair tests and hits of the cells sweep, hits of the dense tiles' sweep
+    — all independent of the order of the rows inside a cell.  Δmom itself is compared to the
+    bar, not bit for bit: the cell lists' placing pass orders the rows inside a cell by atomics,
+    so that the order of the additions, not the pairs, varies from run to run.)"""
+    import torch
+    from concept_amd.mesh import PotentialMesh
+    monkeypatch.delenv('CONCEPT_GPU_SR_DENSE_MIN', raising=False)
+    uni = get_case(10, 'uniform', 8, 4096, False, n=36000, seed=1)
+    clu = get_case(10, 'clustered', 8, 4096, False, n=40000, blob=0.6, sigma=0.45,
+                   blob_rungs=(1, 4))
+    assert uni.L == clu.L
+    nt, L = uni.nt, uni.L
+    dev = 'cuda'
+    boxes = []
+    for case, steps in ((uni, 12), (clu, 6)):
+        boxes.append((steps, case, torch.as_tensor(case.pos, device=dev),
+                      torch.as_tensor(case.rung, device=dev),
+                      torch.as_tensor(case.jumped, device=dev),
+                      torch.as_tensor(case.factors, device=dev),
+                      torch.as_tensor(case.table, device=dev),
+                      torch.as_tensor(np.random.default_rng(9).normal(0, 1e-3, case.pos.shape),
+                                      device=dev)))
+    runs, counters = [], []
+    for wait in (True, False):
+        mesh = PotentialMesh(32, L)
+        mesh.shortrange_stats(True)
+        outs = []
+        for steps, case, pos, rung, jumped, factors, table, base in boxes:
+            for step in range(steps):
+                lowest = 1 + step % 2
+                cells = mesh.shortrange_cells(pos, nt, L/nt, (rung, jumped, lowest), True)
+                got = base.clone()
+                if wait:
+                    torch.cuda.synchronize()
+                mesh.shortrange_sweep_cells(cells, got, cells, nt, table, case.scaling,
+                                            RANGE**2, 0.0, (factors, rung, jumped, lowest))
+                outs.append(got)
+        stats = mesh.shortrange_stats(False)
+        counters.append((stats['cells'][:2], stats['dense'][1]))
+        runs.append([o.cpu().numpy() for o in outs])
+        mesh.close()
+    assert counters[0][1] > 0, 'the dense tiles\' form was never taken'
+    assert counters[0] == counters[1], f'the forms taken depend on host timing: {counters}'
+    scales = [max(case.s_pair, 1.0) for steps, case, *_ in boxes for _ in range(steps)]
+    for i, (a, b, s) in enumerate(zip(*runs, scales)):
+        assert np.abs(a - b).max() <= TOL*max(np.abs(a).max(), s), f'sweep {i}'
+    # (and they are right: the last sweep of each box against the oracle)
+    for (steps, case, *_, base), idx in zip(boxes, (11, 17)):
+        lowest = 1 + (steps - 1) % 2
+        ref = case.oracle(lowest)
+        s = max(np.abs(ref).max(), case.s_pair)
+        active = case.rung >= lowest
+        b = base.cpu().numpy()
+        assert np.abs(runs[1][idx][active] - (b[active] + ref[active])).max() <= TOL*s
