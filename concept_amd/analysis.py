@@ -1,0 +1,549 @@
+"""concept_amd.analysis — power spectra of the components (the reference's analysis.py).
+
+  powerspec()                    analysis.py:70-93
+  get_powerspec_declarations()   analysis.py:118-197 with get_output_declarations
+                                 (graphics.py:1080-1143)
+  get_powerspec_bins()           analysis.py:235-438, construct_powerspec_k_bin_centers
+                                 analysis.py:441-496
+  compute_powerspec()            analysis.py:500-579: interpolate_upstream(..., 'ρ', ...,
+                                 output_space='Fourier') (mesh.py:492-635) on mesh contexts of
+                                 their own roles, then the k-shell binning in HIP
+                                 (cg_powerspec_bin, csrc/cg_analysis.hip)
+  compute_powerspec_σ()          analysis.py:856-914
+  save_powerspec()               analysis.py:796-833 with save_polyspec / get_txt_info
+                                 (analysis.py:3283-3484, 3495-3751)
+The linear and corrected spectra need CLASS, and plots need matplotlib: a selection that asks
+for them is warned about once and left out; 'data' is what gets computed."""
+import collections
+import hashlib
+import itertools
+import math
+import os
+import re
+import warnings
+
+import numpy as np
+import torch
+
+from . import commons
+from . import comm as _comm
+from .lib import ConceptGPUError
+from .mesh import get_mesh
+
+π = commons.π
+
+PowerspecDeclaration = collections.namedtuple(
+    'PowerspecDeclaration',
+    ('components', 'do_data', 'do_corrected', 'do_linear', 'do_plot', 'gridsize',
+     'interpolation', 'deconvolve', 'interlace', 'realization_correction', 'k2_max', 'k_max',
+     'bins_per_decade', 'tophat', 'significant_figures', 'k_bin_indices', 'k_bin_centers',
+     'n_modes', 'power', 'power_corrected', 'power_linear'),
+    defaults=[None]*21)
+
+_unsupported_warned = set()
+powerspec_declarations_cache = {}
+powerspec_bins_cache = {}
+_device_tables = {}
+
+
+# -- selections (commons.py:5471-5600 for several components) ----------------------------------
+def is_selected(components, d, default=None):
+    """is_selected for one component (commons.is_selected) or for a combination: then keys are
+    'default', 'all combinations' and collections of representations, species or names."""
+    components = list(components) if isinstance(components, (list, tuple)) else [components]
+    if len(components) == 1:
+        return commons.is_selected(components[0], d, default=default)
+    names = frozenset(c.name.lower() for c in components)
+    representations = frozenset(c.representation.lower() for c in components)
+    single_species = frozenset(s_.lower() for c in components for s_ in c.species.split('+'))
+    species = frozenset(c.species.lower() for c in components)
+    keys = ('default', 'all combinations', representations, single_species, species, names)
+    lowered = {}
+    for key, val in d.items():
+        if isinstance(key, str):
+            key = key.lower()
+        else:
+            key = [k.lower() if isinstance(k, str) else getattr(k, 'name', str(k)).lower()
+                   for k in key]
+            if not key:
+                continue
+            key = key[0] if len(key) == 1 else frozenset(key)
+        lowered[key] = val
+    found = [lowered[k] for k in keys if k in lowered]
+    return found[-1] if found else default
+
+
+def _eval_expr(expr, mapping):
+    """eval_bin_str (analysis.py:470-494) / to_float: a string expression of the names in
+    `mapping` and the units"""
+    if not isinstance(expr, str):
+        return float(expr)
+    p = commons.params
+    ns = {'sqrt': math.sqrt, 'cbrt': np.cbrt, 'log': math.log, 'log10': math.log10, 'exp': math.exp,
+          'π': π, 'pi': π, 'min': min, 'max': max}
+    if p is not None:
+        ns.update(vars(p.units))
+    full = {}
+    for key, val in mapping.items():
+        base = key[2:] if key.startswith('k_') else key
+        for k in (base, base.lower(), base.capitalize()):
+            for k2 in (f'k_{k}', f'k{k}', k, k.replace('_', '')):
+                if k2 not in ('min', 'max'):   # (the functions keep their names)
+                    full[k2] = val
+    ns.update(full)
+    return float(eval(expr, {}, ns))
+
+
+def upstream_gridsize(component):
+    """Component.powerspec_upstream_gridsize (species.py:1371-1394): the selected 'upstream
+    gridsize', else 2*cbrt(Ñ) for particles and the fluid's own grid size for fluids."""
+    p = commons.params
+    g = is_selected(component, p.powerspec_options['upstream gridsize'], default=-1)
+    if g == -1:
+        g = 'gridsize' if component.representation == 'fluid' else '2*cbrt(Ñ)'
+    if isinstance(g, str):
+        N = component.N if component.representation == 'particles' else component.gridsize**3
+        g = _eval_expr(g, {'Ñ': N, 'N': N, 'gridsize': getattr(component, 'gridsize', -1) or -1})
+    g = int(round(float(g)))
+    if component.representation == 'fluid' and g != component.gridsize:
+        raise ConceptGPUError(
+            f'{component.name}: power spectrum upstream grid size {g} differs from the fluid '
+            f'grid size {component.gridsize}')
+    return g
+
+
+# -- declarations ------------------------------------------------------------------------------
+def get_powerspec_declarations(components):
+    """One declaration per component combination that powerspec_select selects (graphics.py:
+    1080-1143), with the bins of get_powerspec_bins.  'linear', 'corrected' (need CLASS) and
+    'plot' are warned about once and switched off; what remains of a selection computes
+    'data'."""
+    p = commons.params
+    cache_key = (id(p),) + tuple(id(c) for c in components)
+    declarations = powerspec_declarations_cache.get(cache_key)
+    if declarations:
+        return declarations
+    selections, options = p.powerspec_select, p.powerspec_options
+    declarations = []
+    combinations = itertools.chain.from_iterable(
+        itertools.combinations(components, i) for i in range(1, len(components) + 1))
+    for combination in map(list, combinations):
+        do = {key: bool(is_selected(combination, {k: v[key] for k, v in selections.items()},
+                                    default=False))
+              for key in ('data', 'corrected', 'linear', 'plot')}
+        if not any(do.values()):
+            continue
+        for key, why in (('linear', 'needs CLASS'), ('corrected', 'needs CLASS'),
+                         ('plot', 'plots are not produced')):
+            if do[key] and key not in _unsupported_warned:
+                _unsupported_warned.add(key)
+                warnings.warn(f"powerspec_select: '{key}' {why}; it is left out")
+        gridsize = is_selected(combination, options['global gridsize'], default=-1)
+        if gridsize == -1:
+            gridsize = max(upstream_gridsize(c) for c in combination)
+        spec = {key.replace(' ', '_'): is_selected(combination, option)
+                for key, option in options.items()
+                if key not in ('upstream gridsize', 'global gridsize')}
+        k2_max, k_bin_indices, k_bin_centers, n_modes = get_powerspec_bins(
+            int(gridsize), spec['k_max'], spec['bins_per_decade'])
+        declarations.append(PowerspecDeclaration(
+            components=combination, do_data=True, do_corrected=False, do_linear=False,
+            do_plot=False, gridsize=int(gridsize), k2_max=k2_max, k_bin_indices=k_bin_indices,
+            k_bin_centers=k_bin_centers, n_modes=n_modes,
+            power=np.empty(len(k_bin_centers)), **spec))
+    powerspec_declarations_cache[cache_key] = declarations
+    return declarations
+
+
+# -- bins --------------------------------------------------------------------------------------
+def _controlpoint_spline(d):
+    """get_controlpoint_spline(d, np.log10) (commons.py:5436-5465): linear in log10 of the
+    keys, clamped at the ends; looked up with log10 k"""
+    x = np.log10(np.fromiter(d.keys(), dtype=np.float64))
+    y = np.fromiter(d.values(), dtype=np.float64)
+    order = np.argsort(x, kind='stable')
+    x, y = x[order], y[order]
+    return lambda logk: float(np.interp(logk, x, y))
+
+
+def construct_powerspec_k_bin_centers(k_min, k_max, bins_per_decade, gridsize, nyquist):
+    """analysis.py:441-496"""
+    k_fundamental = 2*π/commons.params.boxsize
+    binsize_min = (0.5*(1 - 1e-2)*k_fundamental
+                   * (math.sqrt(3*nyquist**2 + 1) - math.sqrt(3*nyquist**2)))
+    mapping = {'nyquist': k_fundamental*nyquist, 'gridsize': gridsize, 'k_min': k_min,
+               'k_max': k_max, 'k_fundamental': k_min, 'k_f': k_min}
+    bpd = {}
+    for k, val in bins_per_decade.items():
+        bpd[_eval_expr(k.strip(), mapping) if isinstance(k, str) else k] = (
+            _eval_expr(val, mapping) if isinstance(val, str) else val)
+    if len(bpd) == 1:
+        bpd.update({k + 1: val for k, val in bpd.items()})
+    logk_min, logk_max = math.log10(k_min), math.log10(k_max)
+    interp = _controlpoint_spline(bpd)
+    centers = []
+    logk_bin_right = logk_min - 0.5/interp(logk_min)
+    while logk_bin_right <= logk_max:
+        logk_bin_left = logk_bin_right
+        logk_bin_right = logk_bin_left + 1/interp(logk_bin_left)
+        logk_bin_right = np.max((logk_bin_right, math.log10(10**logk_bin_left + binsize_min)))
+        centers.append(10**(0.5*(logk_bin_left + logk_bin_right)))
+    if not centers:
+        centers.append(math.sqrt(k_min*k_max))
+    centers = np.asarray(centers, dtype=np.float64)
+    if len(centers) > 1:
+        left = k_min
+        right = 10**(logk_max - 0.5/interp(logk_max))
+        centers = 10**(
+            math.log10(left) + (np.log10(centers) - math.log10(centers[0]))*(
+                (math.log10(right) - math.log10(left))
+                / (math.log10(centers[-1]) - math.log10(centers[0]))))
+    return centers
+
+
+def n_modes_per_k2(gridsize, k2_max):
+    """The multiplicity of every k² in [0, k2_max] over fourier_loop(gridsize, sparse=True,
+    skip_origin=True, k2_max) (mesh.py:2748-2838), in closed form: the (ki, kj) pairs off the
+    Nyquist planes by ki² + kj², shifted by every kk² with 0 < kk < nyquist, plus half of the
+    kk = 0 plane (one of each conjugate pair, the origin left out).  Cached per
+    (gridsize, k2_max)."""
+    key = ('n_modes', int(gridsize), int(k2_max))
+    n = powerspec_bins_cache.get(key)
+    if n is not None:
+        return n
+    N, nyq = int(gridsize), int(gridsize)//2
+    a = np.array([i for i in range(N) if i != nyq], dtype=np.int64)
+    k1 = a - np.where(a >= nyq, N, 0)
+    ki, kj = np.meshgrid(k1, k1, indexing='ij')
+    s = (kj**2 + ki**2).ravel()
+    keep = s <= k2_max
+    c2 = np.bincount(s[keep], minlength=k2_max + 1)[:k2_max + 1]
+    plane0 = ~((ki > 0) | ((ki == 0) & (kj >= 0))).ravel()
+    n = np.bincount(s[keep & plane0], minlength=k2_max + 1)[:k2_max + 1].astype(np.int64)
+    for kk in range(1, nyq):
+        shift = kk*kk
+        if shift > k2_max:
+            break
+        n[shift:] += c2[:k2_max + 1 - shift]
+    powerspec_bins_cache[key] = n
+    return n
+
+
+def get_powerspec_bins(gridsize, k_max, bins_per_decade):
+    """analysis.py:235-438: (k2_max, k_bin_indices, k_bin_centers, n_modes)."""
+    p = commons.params
+    cache_key = (gridsize, p.boxsize, k_max, tuple(bins_per_decade.items()))
+    bins = powerspec_bins_cache.get(cache_key)
+    if bins:
+        return bins
+    k_fundamental = 2*π/p.boxsize
+    k_min = k_fundamental
+    nyquist = gridsize//2
+    if isinstance(k_max, str):
+        k_max = _eval_expr(k_max, {'nyquist': k_fundamental*nyquist, 'gridsize': gridsize,
+                                   'k_min': k_min, 'k_fundamental': k_min, 'k_f': k_min})
+    if k_max < k_min:
+        warnings.warn(f'Power spectrum k_max was set to {k_max} < k_min = 2π/boxsize = '
+                      f'{k_min}. Setting k_max = k_min.')
+        k_max = k_min
+    k2_max = int(round((k_max/k_fundamental)**2))
+    k2_max = min(k2_max, 3*nyquist**2)
+    k_max = k_fundamental*math.sqrt(k2_max)
+    k_bin_centers = construct_powerspec_k_bin_centers(k_min, k_max, bins_per_decade, gridsize,
+                                                      nyquist)
+    logk_bin_centers = np.log(k_bin_centers)
+    k2 = np.arange(1, k2_max + 1)
+    logk = np.log(k_fundamental*np.sqrt(k2.astype(np.float64)))
+    index = np.searchsorted(logk_bin_centers, logk)
+    nb = k_bin_centers.shape[0]
+    last = index == nb
+    mid = (~last) & (index != 0)
+    im = index[mid]
+    dist_left = logk[mid] - logk_bin_centers[im - 1]
+    dist_right = logk_bin_centers[im] - logk[mid]
+    index[mid] = im - (dist_left <= dist_right)
+    index[last] -= 1
+    k_bin_indices = np.empty(k2_max + 1, dtype=np.int64)
+    k_bin_indices[0] = 0
+    k_bin_indices[1:] = index
+    n_modes_fine = n_modes_per_k2(gridsize, k2_max)
+    # centres: the mode-weighted geometric mean of the k that fall into a bin
+    occupied = np.nonzero(n_modes_fine[1:])[0] + 1
+    bins_occ = k_bin_indices[occupied]
+    n_modes = np.bincount(bins_occ, weights=n_modes_fine[occupied], minlength=nb).astype(np.int64)
+    log_sum = np.zeros(nb)
+    for b, w in zip(bins_occ, n_modes_fine[occupied]*np.log(
+            k_fundamental*np.sqrt(occupied.astype(np.float64)))):
+        log_sum[b] += w
+    k_bin_centers = np.zeros(nb)
+    filled = n_modes > 0
+    k_bin_centers[filled] = np.exp(log_sum[filled]/n_modes[filled])
+    # consecutive indices for the non-empty bins (k_bin_indices never decreases along k²)
+    rank = np.cumsum(filled) - 1
+    new = np.where(filled[k_bin_indices], rank[k_bin_indices], -1)
+    new[0] = 0
+    k_bin_indices = np.maximum.accumulate(new)
+    bins = (k2_max, k_bin_indices, k_bin_centers[filled], n_modes[filled])
+    powerspec_bins_cache[cache_key] = bins
+    return bins
+
+
+# -- the spectrum ------------------------------------------------------------------------------
+def _mesh(gridsize, role):
+    p = commons.params
+    return get_mesh(gridsize, p.boxsize, p.nghosts, p.cell_centered, 2, None, role=role)
+
+
+def interpolate_upstream(components, gridsizes_upstream, gridsize_global, order, deconvolve,
+                         interlace, a=1.0):
+    """interpolate_upstream(components, ..., quantity='ρ', output_space='Fourier')
+    (mesh.py:492-635) with add_upstream_to_global_slabs (mesh.py:654-711): the mesh whose
+    Fourier view holds the global slab.  The meshes are of the roles 'powerspec' and
+    'powerspec upstream', apart from those of gravity()."""
+    from .interactions import (_aligned, _check_halo_reach, group_components,
+                               lattice_shifts)
+    p = commons.params
+    boxsize = p.boxsize
+    shifts = lattice_shifts(interlace, p.cell_centered)
+    slab_global = None
+
+    def upstream_mesh(g):
+        if slab_global is None and g == gridsize_global:
+            return _mesh(gridsize_global, 'powerspec')
+        return _mesh(g, 'powerspec upstream')
+
+    def add_to_global(up, deconv_order, nlattice=1, shift=(0, 0, 0)):
+        nonlocal slab_global
+        if slab_global is None and up.gridsize == gridsize_global:
+            slab_global = up.fourier_operate(deconv_order, nlattice, shift)
+        elif slab_global is None:
+            slab_global = _mesh(gridsize_global, 'powerspec')
+            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='=')
+        else:
+            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='+=')
+    for c, g in zip(components, gridsizes_upstream):
+        if c.representation == 'fluid' and c.gridsize != g:
+            raise ConceptGPUError(
+                f'add_fluid_to_grid() got component with global grid size {c.gridsize} and '
+                f'non-matching grid of global grid size {g}')
+    groups = group_components(components, gridsizes_upstream, [gridsize_global, ...])
+    for g, group in groups.items():
+        fft_factor = float(g)**(-3)  # mesh.py:582
+        fluids, particles = group.get('fluid', []), group.get('particles', [])
+        if fluids:
+            up = upstream_mesh(g)
+            for i, fluid in enumerate(fluids):
+                # add_fluid_to_grid, quantity 'ρ' (mesh.py:1713-1718)
+                factor = fft_factor
+                factor *= a**(-3*(1 + fluid.w_eff(a=a)))
+                up.fluid_add(fluid.ϱ, factor, '=' if i == 0 else '+=')
+            up.fft_forward()
+            up.nullify_nyquist()
+            add_to_global(up, 0)
+        for shift in (shifts if particles else ()):
+            up = upstream_mesh(g)
+            cloud = {1: (0, 1), 2: (0, 1), 3: (1, 2), 4: (1, 2)}[order]
+            if shift != (0, 0, 0):
+                cloud = (cloud[0] + 1, cloud[1] + 1)
+            if up.dist and up.nprocs > 1 and max(cloud) > up.ghost_layers:
+                raise ConceptGPUError('interpolation reaches beyond the 3 halo layers')
+            for c in particles:
+                _check_halo_reach(c, up, cloud, 0)
+            up.zero()
+            for c in particles:
+                # interpolate_particles, quantity 'ρ' (mesh.py:1543-1549, 1573)
+                contribution = a**(-3*(1 + c.w_eff(a=a)))
+                contribution *= c.mass
+                contribution *= fft_factor*(g/boxsize)**3
+                if order == 2 and shift == (0, 0, 0):
+                    up.deposit(c.pos, contribution)
+                else:
+                    up.deposit_general(c.pos, contribution, order, shift)
+            up.fold_ghosts(general=not (order == 2 and shift == (0, 0, 0)
+                                        and all(_aligned(c, up) for c in particles)))
+            up.fft_forward()
+            up.nullify_nyquist()
+            add_to_global(up, order*int(bool(deconvolve)), len(shifts), shift)
+    return slab_global
+
+
+def _device_bin_table(declaration, device):
+    key = (id(declaration.k_bin_indices), str(device))
+    t = _device_tables.get(key)
+    if t is None:
+        t = _device_tables[key] = torch.from_numpy(
+            np.ascontiguousarray(declaration.k_bin_indices, dtype=np.int32)).to(device)
+    return t
+
+
+def compute_powerspec(declaration, a=1.0, timings=None):
+    """analysis.py:500-579: the binned power of the declaration's components into
+    declaration.power (on every rank; under comm.init() the ranks' partial bins are summed in
+    rank order).  timings: a dict that receives the seconds of the upstream interpolation
+    (deposits and FFTs) and of the binning."""
+    components = declaration.components
+    gridsizes_upstream = [upstream_gridsize(c) for c in components]
+    if timings is not None:
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+    slab = interpolate_upstream(components, gridsizes_upstream, declaration.gridsize,
+                                declaration.interpolation, declaration.deconvolve,
+                                declaration.interlace, a)
+    if timings is not None:
+        ev[1].record()
+    nbins = len(declaration.k_bin_centers)
+    power = slab.powerspec_bin(_device_bin_table(declaration, slab.device),
+                               declaration.k2_max, nbins)
+    if timings is not None:
+        ev[2].record()
+        ev[2].synchronize()
+        timings['upstream'] = ev[0].elapsed_time(ev[1])*1e-3
+        timings['binning'] = ev[1].elapsed_time(ev[2])*1e-3
+    power = power.cpu().numpy()
+    c = _comm.active()
+    if c is not None and c.world > 1:
+        parts = c.all_gather_floats(power.tolist()).numpy()
+        power = parts[0].copy()
+        for r in range(1, parts.shape[0]):
+            power = power + parts[r]
+    # normalisation (analysis.py:567-577)
+    normalization = 0
+    for component in components:
+        normalization += a**(-3*(1 + component.w_eff(a=a)))*component.ϱ_bar
+    normalization **= -2
+    normalization *= commons.params.boxsize**3
+    power = power*(normalization/declaration.n_modes)
+    declaration.power[:] = power
+    return declaration.power
+
+
+def compute_powerspec_σ(declaration, kind='data'):
+    """analysis.py:856-914: the rms density variation in a sphere of radius tophat"""
+    kind = kind.lower().replace(' ', '').replace('-', '').replace('_', '')
+    if kind != 'data':
+        raise ConceptGPUError(f'compute_powerspec_σ() called with kind = "{kind}": only "data" '
+                              'spectra are computed here (the others need CLASS)')
+    tophat = declaration.tophat
+    k = np.asarray(declaration.k_bin_centers, dtype=np.float64)
+    power = np.asarray(declaration.power, dtype=np.float64)
+    mask = np.isnan(power)
+    if mask.any():
+        power, k = power[~mask], k[~mask]
+    if k.shape[0] < 2:
+        return float('nan')
+    kR = k*tophat
+    with np.errstate(invalid='ignore', divide='ignore'):
+        W = np.where(kR < 1e-3, 1./3. - 1./30.*kR**2, (np.sin(kR) - kR*np.cos(kR))/kR**3)
+    integrand = (k*W)**2*power
+    σ2 = float(np.trapezoid(integrand, k) if hasattr(np, 'trapezoid') else np.trapz(integrand, k))
+    σ2 += 0.5*k[0]*integrand[0]
+    σ2 *= 3**2/(2*π**2)
+    return math.sqrt(σ2)
+
+
+# -- the file ----------------------------------------------------------------------------------
+_subscripts = dict(zip('0123456789-+.e', '₀₁₂₃₄₅₆₇₈₉₋₊.ₑ'))
+
+
+def unicode_subscript(s):
+    return ''.join(_subscripts.get(ch, ch) for ch in s)
+
+
+def _components_str(components):
+    s = ', '.join(c.name for c in components)
+    return f'{{{s}}}' if len(components) > 1 else s
+
+
+def save_powerspec(declarations, filename, a=None, t=None):
+    """save_powerspec (analysis.py:796-833) through save_polyspec (analysis.py:3283-3484):
+    a header (time, components with their upstream grid sizes, per column group the global grid
+    size and every declaration's σ line), then one column group per binning — k, modes and the
+    P of each declaration of that binning — floats as %.{sf-1}e, shorter columns padded with
+    NaN.  Only rank 0 writes."""
+    p = commons.params
+    c = _comm.active()
+    if c is not None and c.rank != 0:
+        return filename
+    declarations = [d for d in declarations if d.do_data]
+    if not declarations:
+        return filename
+    sf = max(int(d.significant_figures) for d in declarations)
+    σ_unit = p.units.Mpc/(p.H0/(100*p.units.km/(p.units.s*p.units.Mpc))) if p.enable_Hubble \
+        else p.units.Mpc
+    groups = collections.OrderedDict()
+    for d in declarations:
+        key = (len(d.k_bin_centers), d.k2_max,
+               hashlib.sha1(np.ascontiguousarray(d.k_bin_centers)).hexdigest())
+        groups.setdefault(key, []).append(d)
+    lines = []
+    tline = f'Power spectra at t = {t:.{sf}g} Gyr' if t is not None else 'Power spectra'
+    if p.enable_Hubble and a is not None:
+        tline += f', a = {a:.{sf}g}'
+    lines.append(tline + ', computed with:')
+    comps = []
+    for d in declarations:
+        for comp in d.components:
+            if comp not in comps:
+                comps.append(comp)
+    width = max(len(comp.name) for comp in comps)
+    lines.append(f'  {"component":<{width}}  upstream gridsize')
+    for comp in comps:
+        lines.append(f'  {comp.name:<{width}}  {upstream_gridsize(comp)}')
+    columns, headings = [], []
+    for gi, ((nbins, k2_max, _), group) in enumerate(groups.items()):
+        d0 = group[0]
+        lines.append(f'Column group {gi + 1}: global gridsize {d0.gridsize}, '
+                     f'k_max = {math.sqrt(k2_max)*2*π/p.boxsize:.{sf}g} Mpc⁻¹')
+        for d in group:
+            σ = compute_powerspec_σ(d)
+            sub = unicode_subscript(f'{d.tophat/σ_unit:.3g}')
+            lines.append(f'  {_components_str(d.components)}: σ{sub} = {σ:.{sf - 1}e}')
+        columns.append(('k', np.asarray(d0.k_bin_centers, dtype=np.float64)))
+        headings.append('k [Mpc⁻¹]')
+        columns.append(('modes', np.asarray(d0.n_modes)))
+        headings.append('modes')
+        for d in group:
+            columns.append(('P', np.asarray(d.power, dtype=np.float64)))
+            headings.append(f'P [Mpc³] {_components_str(d.components)}')
+    nrows = max(len(col) for _, col in columns)
+    fw = sf + 6
+    lines.append('  '.join(f'{h:<{fw}}' for h in headings).rstrip())
+    body = []
+    for r in range(nrows):
+        cells = []
+        for kind, col in columns:
+            if r >= len(col):
+                cells.append(f'{"nan":<{fw}}')
+            elif kind == 'modes':
+                cells.append(f'{int(col[r]):<{fw}d}')
+            else:
+                cells.append(f'{col[r]:<{fw}.{sf - 1}e}')
+        body.append('  '.join(cells).rstrip())
+    d = os.path.dirname(filename)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(filename, 'w', encoding='utf-8') as f:
+        f.write('\n'.join('# ' + line for line in lines) + '\n')
+        f.write('\n'.join(body) + '\n')
+    return filename
+
+
+def powerspec(components, filename, a=1.0, t=None, timings=None):
+    """analysis.py:70-93: compute the power spectra that powerspec_select asks for and write
+    them to `filename`.  a: the current scale factor (universals.a)."""
+    declarations = get_powerspec_declarations(components)
+    for declaration in declarations:
+        compute_powerspec(declaration, a, timings)
+    save_powerspec(declarations, filename, a, t)
+    return declarations
+
+
+def load_powerspec_σ(filename, tophat_Mpc):
+    """The σ of the first declaration from a written file, found the way the reference's
+    test/powerspec/analyze.py does (regex on the header)."""
+    with open(filename, encoding='utf-8') as f:
+        for line in f:
+            m = re.search('σ' + unicode_subscript(f'{tophat_Mpc:.2g}') + r' = ([0-9\.e+-]*)', line)
+            if m:
+                return float(m.group(1))
+    return None

@@ -284,10 +284,13 @@ def load_params(source=None, **overrides):
     p.ewald_gridsize = int(user.get('ewald_gridsize', 64))  # commons.py:3061
     p.N_rungs = int(user.get('N_rungs', 8))
     p.cell_centered = bool(user.get('cell_centered', True))
+    _load_powerspec_params(p, user, units)
     # nghosts (commons.py:4411-4432): default 2 comes from the PCS default of the
     # power-spectrum options; force interpolation and differentiation orders raise it
     # (powerspec_options default: PCS, interlaced -> 4//2 = 2, + 1 with cell-vertex grids)
-    nghosts = 2 + (0 if p.cell_centered else 1)
+    order = max(p.powerspec_options['interpolation'].values())
+    interlaced = any(v != 'sc' for v in p.powerspec_options['interlace'].values())
+    nghosts = order//2 + int(interlaced and (order % 2 != 0 or not p.cell_centered))
     for force, d in p.potential_options['interpolation'].items():
         for m, order in d.items():
             lattices = tuple(p.potential_options['interlace'].get(force, {}).get(m, ('sc', 'sc')))
@@ -347,26 +350,33 @@ def load_params(source=None, **overrides):
         p.output_times[default_param] += _times(rest)
     else:
         p.output_times[default_param] = _times(ot)
-    # which of those dump times are snapshot times, per time parameter (the other output kinds —
-    # power spectra, renders — are dumps of the time loop too, but nothing is written for them)
+    # which of those dump times are snapshot times and which power-spectrum times, per time
+    # parameter (the other output kinds — renders, bispectra — are dumps of the time loop too,
+    # but nothing is written for them)
     def _kind_times(v, kind):
         if isinstance(v, dict):
             return _times(v.get(kind))
         return ()
     p.snapshot_times = {'a': (), 't': ()}
-    if isinstance(ot, dict) and set(ot) & {'a', 't'}:
-        for tp in ('a', 't'):
-            p.snapshot_times[tp] = _kind_times(ot.get(tp), 'snapshot')
-        p.snapshot_times[default_param] += _kind_times(ot, 'snapshot')
-    else:
-        p.snapshot_times[default_param] = _kind_times(ot, 'snapshot')
+    p.powerspec_times = {'a': (), 't': ()}
+    for kind, kind_times in (('snapshot', p.snapshot_times), ('powerspec', p.powerspec_times)):
+        if isinstance(ot, dict) and set(ot) & {'a', 't'}:
+            for tp in ('a', 't'):
+                kind_times[tp] = _kind_times(ot.get(tp), kind)
+            kind_times[default_param] += _kind_times(ot, kind)
+        else:
+            kind_times[default_param] = _kind_times(ot, kind)
     # input / output (commons.py:2547-2572, 2787-2830): where snapshots go, what they are
     # called and which format they have
     od = user.get('output_dirs', {})
+    # the power-spectrum directory (commons.py:2547-2572): a dict entry, or a single string for
+    # every kind, as in the reference — kept apart so that output_dirs stays {'snapshot': ...}
+    p.powerspec_dir = str(od) if isinstance(od, str) and od else (
+        str(od.get('powerspec')) if isinstance(od, dict) and od.get('powerspec') else None)
     if isinstance(od, str):
         od = {'snapshot': od}
     p.output_dirs = {k: str(v) for k, v in dict(od).items() if v}
-    p.output_bases = {'snapshot': 'snapshot'}
+    p.output_bases = {'snapshot': 'snapshot', 'powerspec': 'powerspec'}
     p.output_bases.update({k: str(v) for k, v in dict(user.get('output_bases', {})).items()})
     p.snapshot_type = str(user.get('snapshot_type', 'concept')).lower()
     p.initial_conditions = user.get('initial_conditions', '')
@@ -390,6 +400,103 @@ def load_params(source=None, **overrides):
     p.user = user
     params = p
     return p
+
+
+def _interlace2latticekind(interlace):
+    """commons.py:3150-3157"""
+    if isinstance(interlace, (tuple, list)):
+        return (_interlace2latticekind(interlace[0]), _interlace2latticekind(interlace[1]))
+    if isinstance(interlace, str):
+        return interlace
+    return 'bcc' if interlace else 'sc'
+
+
+def _load_powerspec_params(p, user, units):
+    """powerspec_select (commons.py:2615-2670) and powerspec_options (commons.py:3354-3438,
+    the tophat's h at :5992-5999), with the reference's defaults, key folding and errors."""
+    dos = ('data', 'corrected', 'linear', 'plot')
+    if 'powerspec_select' in user:
+        sel = user['powerspec_select']
+        sel = dict(sel) if isinstance(sel, dict) else {'default': sel}
+        for key, val in list(sel.items()):
+            if isinstance(val, dict):
+                sel[key] = {k.replace(' ', '').replace('-', '').replace('_', ''): v
+                            for k, v in val.items()}
+        sel.setdefault('default', {do: False for do in dos})
+    else:
+        sel = {'default': {'data': True, 'corrected': False, 'linear': True, 'plot': True}}
+    for key, val in list(sel.items()):
+        if isinstance(val, dict):
+            for do in dos:
+                val.setdefault(do, False)
+            unknown = ', '.join(f'"{do}"' for do in sorted(set(val) - set(dos)))
+            if unknown:
+                raise ValueError(f'Unknown selections in powerspec_select["{key}"]: {unknown}')
+        else:
+            sel[key] = {do: bool(val) for do in dos}
+    p.powerspec_select = sel
+    defaults = {
+        'upstream gridsize': {'default': -1},
+        'global gridsize': {'default': -1},
+        'interpolation': {'default': 'PCS'},
+        'deconvolve': {'default': True},
+        'interlace': {'default': True},
+        'realization correction': {'default': True},
+        'k_max': {'default': 'Nyquist'},
+        'bins per decade': {'default': {'  4*k_min': 4, '100*k_min': 40}},
+        'tophat': {'default': '8*Mpc/h'},
+        'significant figures': {'default': 8},
+    }
+    opts = {k: (dict(v) if isinstance(v, dict) else v)
+            for k, v in dict(user.get('powerspec_options') or {}).items()}
+    if 'gridsize' in opts:
+        d = opts.pop('gridsize')
+        if not isinstance(d, dict):
+            d = {'default': d}
+        opts.setdefault('upstream gridsize', dict(d))
+        opts.setdefault('global gridsize', dict(d))
+    for key, d in list(opts.items()):
+        if not isinstance(d, dict):
+            opts[key] = {'default': d}
+    for key in opts:
+        if key not in defaults:
+            raise ValueError(f'powerspec_options["{key}"] not implemented')
+    for key, d_defaults in defaults.items():
+        d = opts.setdefault(key, {})
+        for k, v in d_defaults.items():
+            d.setdefault(k, v)
+    d = opts['global gridsize']
+    for k, v in d.items():
+        d[k] = int(round(v))
+    d = opts['interpolation']
+    for k, v in d.items():
+        d[k] = int(interpolation_orders.get(str(v).upper(), v))
+    d = opts['interlace']
+    for k, v in d.items():
+        d[k] = _interlace2latticekind(v)
+    d = opts['realization correction']
+    for k, v in d.items():
+        if isinstance(v, str):
+            d[k] = bool(v)
+    d = opts['k_max']
+    for k, v in d.items():
+        if isinstance(v, str):
+            d[k] = v.replace('Nyquist', 'nyquist')
+    d = opts['bins per decade']
+    for k, v in d.items():
+        v = dict(v) if isinstance(v, dict) else {1: v}
+        if len(v) == 1:
+            v.update({(f'{k2} + 1' if isinstance(k2, str) else k2 + 1): v2
+                      for k2, v2 in v.items()})
+        d[k] = v
+    enable_Hubble = bool(user.get('enable_Hubble', True))
+    H0 = float(user.get('H0', 67*units['km']/(units['s']*units['Mpc'])))
+    h = H0/(100*units['km']/(units['s']*units['Mpc'])) if enable_Hubble else 1
+    d = opts['tophat']
+    for k, v in d.items():
+        if isinstance(v, str):
+            d[k] = float(eval(v.replace('h', f'({h})'), {}, dict(units)))
+    p.powerspec_options = opts
 
 
 def is_selected(component, d, accumulate=False, default=None):

@@ -141,6 +141,8 @@ SYMBOLS = {
                           _vp, _int]),
     'cg_mesh_copy': (_int, [_vp, _vp]),
     'cg_fluid_kick': (_int, [_vp, _vp, _vp, _vp, _int, _int, _dbl, _dbl]),
+    'cg_powerspec_workspace': (_i64, [_vp, ctypes.c_int32]),
+    'cg_powerspec_bin': (_int, [_vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _i64]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -444,6 +444,30 @@ class PotentialMesh:
                                           int(nlattice), sh, int(operation == '+=')))
         return self
 
+    def powerspec_bin(self, k_bin_indices, k2_max, nbins, out=None):
+        """The binning loop of compute_powerspec (analysis.py:544-560) on this mesh's Fourier
+        view: a float64 tensor of nbins sums of |δ(k)|² over this domain's visited modes
+        (cg_powerspec_bin).  k_bin_indices: int32 tensor of k2_max + 1 entries on the device,
+        every entry in [0, nbins)."""
+        if (k_bin_indices.dtype != torch.int32 or k_bin_indices.device != self.device
+                or not k_bin_indices.is_contiguous() or k_bin_indices.numel() != int(k2_max) + 1):
+            raise lib.ConceptGPUError(
+                f'powerspec_bin(): k_bin_indices must be a contiguous int32 tensor of '
+                f'k2_max + 1 = {int(k2_max) + 1} entries on {self.device}')
+        if out is None:
+            out = torch.empty(int(nbins), dtype=torch.float64, device=self.device)
+        n = int(_L.cg_powerspec_workspace(self._ctx, int(nbins)))
+        if n < 0:
+            raise lib.ConceptGPUError(lib.last_error())
+        key = (self.device, 'powerspec')
+        ws = _stage_buffers.get(key)
+        if ws is None or ws.numel() < n:
+            ws = _stage_buffers[key] = torch.empty(max(n, 1), dtype=torch.float64,
+                                                   device=self.device)
+        check(_L.cg_powerspec_bin(self._ctx, _ptr(k_bin_indices), int(k2_max), int(nbins),
+                                  _ptr(out), _ptr(ws), ws.numel()))
+        return out
+
     def deposit_general(self, pos, contribution, order=2, shift=(0.0, 0.0, 0.0)):
         """interpolate_particles of order 1..4 with a lattice shift (mesh.py:1512-1636)"""
         n = self._check_particles(pos)

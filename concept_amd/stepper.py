@@ -694,6 +694,7 @@ class Timeloop(RungStepper):
         self.streaming = streaming
         self._plan = self._rps = self._spec = self._next_drift = None
         self.stream_passes = self.stream_wrong_guesses = 0
+        dumpers = []
         if on_dump is None and p.output_dirs.get('snapshot') and (
                 p.snapshot_times['a'] or p.snapshot_times['t']):
             # the parameter file asks for snapshots (output_dirs, output_times['snapshot'],
@@ -705,11 +706,24 @@ class Timeloop(RungStepper):
                               'no snapshots will be dumped')
             else:
                 gsp = p.gadget_snapshot_params
-                self.on_dump = self.snapshot_dumper(
+                dumpers.append(self.snapshot_dumper(
                     p.output_dirs['snapshot'], p.output_bases.get('snapshot', 'snapshot'),
                     only_snapshot_times=True, snapformat=gsp['snapformat'],
                     dataformat=gsp['dataformat'], header=gsp['header'],
-                    particles_per_file=gsp['particles per file'], units=gsp['units'])
+                    particles_per_file=gsp['particles per file'], units=gsp['units']))
+        if on_dump is None and getattr(p, 'powerspec_dir', None) and (
+                p.powerspec_times['a'] or p.powerspec_times['t']):
+            # power spectra at the times output_times lists for 'powerspec' (main.dump,
+            # main.py:1676-1700)
+            dumpers.append(self.powerspec_dumper(p.powerspec_dir,
+                                                 p.output_bases.get('powerspec', 'powerspec')))
+        if len(dumpers) == 1:
+            self.on_dump = dumpers[0]
+        elif dumpers:
+            def on_dump_all(loop, dump_time):
+                for dumper in dumpers:
+                    dumper(loop, dump_time)
+            self.on_dump = on_dump_all
 
     # universals.t / universals.a live in the Cosmology object
     t = property(lambda self: self.cosmo.t, lambda self, v: setattr(self.cosmo, 't', float(v)))
@@ -1002,20 +1016,7 @@ class Timeloop(RungStepper):
         other output kinds' times are dumps of the loop too)."""
         from . import snapshot
         p = self.params
-        fmts = {}
-        for kind, begin in (('a', self.cosmo.a), ('t', self.cosmo.t)):
-            times = sorted(set((begin,) + tuple(p.output_times[kind])))
-            if len(times) < 2 and not p.output_times[kind]:
-                continue
-            ndigits = 0
-            while True:
-                fmt = f'{{:.{ndigits}f}}'
-                if (len(set(fmt.format(ot) for ot in times)) == len(times)
-                        and (fmt.format(times[0]) != fmt.format(0) or not times[0])):
-                    break
-                ndigits += 1
-            fmts[kind] = ndigits
-        ndigits = max(fmts.values()) if fmts else 2
+        ndigits = self._dump_ndigits()
         sep = '_' if output_base else ''
         self.snapshots_written = []
 
@@ -1041,6 +1042,46 @@ class Timeloop(RungStepper):
             fn = snapshot.save(particles, name, a=loop.cosmo.a,
                                **{'output_base': output_base or 'snapshot', **save_options})
             loop.snapshots_written.append(fn)
+        return on_dump
+
+    def _dump_ndigits(self):
+        """just enough digits that neighbouring dumps and the initial time differ in the
+        names of the dumped files (prepare_for_output, main.py:2242-2278)"""
+        p = self.params
+        fmts = {}
+        for kind, begin in (('a', self.cosmo.a), ('t', self.cosmo.t)):
+            times = sorted(set((begin,) + tuple(p.output_times[kind])))
+            if len(times) < 2 and not p.output_times[kind]:
+                continue
+            ndigits = 0
+            while True:
+                fmt = f'{{:.{ndigits}f}}'
+                if (len(set(fmt.format(ot) for ot in times)) == len(times)
+                        and (fmt.format(times[0]) != fmt.format(0) or not times[0])):
+                    break
+                ndigits += 1
+            fmts[kind] = ndigits
+        return max(fmts.values()) if fmts else 2
+
+    def powerspec_dumper(self, output_dir, output_base='powerspec'):
+        """An on_dump callback that writes the power spectra powerspec_select asks for
+        (analysis.powerspec) at the times output_times lists for 'powerspec', named
+        <output_dir>/<output_base>_<a|t>=<value> with the digits of snapshot_dumper (main.dump,
+        main.py:1676-1700)."""
+        from . import analysis
+        p = self.params
+        ndigits = self._dump_ndigits()
+        sep = '_' if output_base else ''
+        self.powerspecs_written = []
+
+        def on_dump(loop, dump_time):
+            value = dump_time.a if dump_time.time_param == 'a' else dump_time.t
+            if not any(abs(value - v) <= 1e-12*max(abs(v), 1e-300)
+                       for v in p.powerspec_times[dump_time.time_param]):
+                return
+            name = f'{output_dir}/{output_base}{sep}{dump_time.time_param}={value:.{ndigits}f}'
+            analysis.powerspec(loop.components, name, a=loop.cosmo.a, t=loop.cosmo.t)
+            loop.powerspecs_written.append(name)
         return on_dump
 
     # -- main.timeloop (main.py:102-471) ---------------------------------------------------

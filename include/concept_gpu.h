@@ -681,6 +681,21 @@ int cg_pp_kick(cg_ctx *ctx, const double *pos_r /*DEV 3 n_r*/, int64_t n_r,
                const signed char *rung /*DEV or NULL*/, const signed char *rung_jumped,
                int lowest_active);
 
+/* --- power spectrum (analysis.py:70-93, 500-579) ---------------------------------
+ * cg_powerspec_bin: the binning loop of compute_powerspec (analysis.py:544-560) over
+ *   fourier_loop(gridsize, sparse=True, skip_origin=True, k2_max=k2_max) (mesh.py:2748-2838)
+ *   on the context's current Fourier view (the in-place slab of one domain, or the buffer
+ *   bound by cg_dist_bind_fourier): power_out[k_bin_indices[k2]] = sum of re^2 + im^2 over
+ *   the visited modes of this domain, k2 = ki^2 + kj^2 + kk^2.  k_bin_indices holds k2_max + 1
+ *   entries; an entry outside [0, nbins) drops its modes.  Deterministic: the same slab and
+ *   the same context give bit-identical bins (no floating-point atomics; fixed summation
+ *   order).  The mode counts per k^2 depend on the geometry only and are not produced here.
+ *   workspace: cg_powerspec_workspace(ctx, nbins) doubles (DEV), any content. */
+int64_t cg_powerspec_workspace(cg_ctx *ctx, int32_t nbins);
+int cg_powerspec_bin(cg_ctx *ctx, const int32_t *k_bin_indices /*DEV k2_max+1*/, int64_t k2_max,
+                     int32_t nbins, double *power_out /*DEV nbins*/, double *workspace /*DEV*/,
+                     int64_t workspace_doubles);
+
 /* --- debug fetch (parity tests) -------------------------------------------- */
 int cg_fetch(cg_ctx *ctx, int which, double *out /*HOST*/, int64_t n_doubles);
 /* CIC cell indices exactly as set_weights_CIC returns them for the deposit
