@@ -94,11 +94,13 @@ def _eval_expr(expr, mapping):
     return float(eval(expr, {}, ns))
 
 
-def upstream_gridsize(component):
-    """Component.powerspec_upstream_gridsize (species.py:1371-1394): the selected 'upstream
-    gridsize', else 2*cbrt(Ñ) for particles and the fluid's own grid size for fluids."""
+def upstream_gridsize(component, output_type='powerspec'):
+    """Component.<output_type>_upstream_gridsize (species.py:1371-1394) for the output types
+    'powerspec' and 'render2D': the selected 'upstream gridsize', else 2*cbrt(Ñ) for particles
+    and the fluid's own grid size for fluids."""
     p = commons.params
-    g = is_selected(component, p.powerspec_options['upstream gridsize'], default=-1)
+    options = getattr(p, f'{output_type}_options')
+    g = is_selected(component, options['upstream gridsize'], default=-1)
     if g == -1:
         g = 'gridsize' if component.representation == 'fluid' else '2*cbrt(Ñ)'
     if isinstance(g, str):
@@ -107,12 +109,39 @@ def upstream_gridsize(component):
     g = int(round(float(g)))
     if component.representation == 'fluid' and g != component.gridsize:
         raise ConceptGPUError(
-            f'{component.name}: power spectrum upstream grid size {g} differs from the fluid '
+            f'{component.name}: '
+            f'{"power spectrum" if output_type == "powerspec" else output_type} '
+            f'upstream grid size {g} differs from the fluid '
             f'grid size {component.gridsize}')
     return g
 
 
 # -- declarations ------------------------------------------------------------------------------
+def get_output_declarations(output_type, components, selections, options):
+    """The generic part of the output declarations (graphics.py:1080-1143), for the output types
+    'powerspec' and 'render2D': for every combination of components for which `selections`
+    selects at least one output, (combination, {output: bool}, specifications).  The
+    specifications are the options looked up for the combination under their names with '_'
+    for ' ', and 'gridsize': the 'global gridsize', or the largest upstream grid size of the
+    combination where that is -1."""
+    combinations = itertools.chain.from_iterable(
+        itertools.combinations(components, i) for i in range(1, len(components) + 1))
+    for combination in map(list, combinations):
+        do = {key: bool(is_selected(combination, {k: v[key] for k, v in selections.items()},
+                                    default=False))
+              for key in selections['default']}
+        if not any(do.values()):
+            continue
+        gridsize = is_selected(combination, options['global gridsize'], default=-1)
+        if gridsize == -1:
+            gridsize = max(upstream_gridsize(c, output_type) for c in combination)
+        specifications = {'gridsize': int(gridsize)}
+        specifications.update({key.replace(' ', '_'): is_selected(combination, option)
+                               for key, option in options.items()
+                               if key not in ('upstream gridsize', 'global gridsize')})
+        yield combination, do, specifications
+
+
 def get_powerspec_declarations(components):
     """One declaration per component combination that powerspec_select selects (graphics.py:
     1080-1143), with the bins of get_powerspec_bins.  'linear', 'corrected' (need CLASS) and
@@ -123,27 +152,15 @@ def get_powerspec_declarations(components):
     declarations = powerspec_declarations_cache.get(cache_key)
     if declarations:
         return declarations
-    selections, options = p.powerspec_select, p.powerspec_options
     declarations = []
-    combinations = itertools.chain.from_iterable(
-        itertools.combinations(components, i) for i in range(1, len(components) + 1))
-    for combination in map(list, combinations):
-        do = {key: bool(is_selected(combination, {k: v[key] for k, v in selections.items()},
-                                    default=False))
-              for key in ('data', 'corrected', 'linear', 'plot')}
-        if not any(do.values()):
-            continue
+    for combination, do, spec in get_output_declarations(
+            'powerspec', components, p.powerspec_select, p.powerspec_options):
+        gridsize = spec.pop('gridsize')
         for key, why in (('linear', 'needs CLASS'), ('corrected', 'needs CLASS'),
                          ('plot', 'plots are not produced')):
             if do[key] and key not in _unsupported_warned:
                 _unsupported_warned.add(key)
                 warnings.warn(f"powerspec_select: '{key}' {why}; it is left out")
-        gridsize = is_selected(combination, options['global gridsize'], default=-1)
-        if gridsize == -1:
-            gridsize = max(upstream_gridsize(c) for c in combination)
-        spec = {key.replace(' ', '_'): is_selected(combination, option)
-                for key, option in options.items()
-                if key not in ('upstream gridsize', 'global gridsize')}
         k2_max, k_bin_indices, k_bin_centers, n_modes = get_powerspec_bins(
             int(gridsize), spec['k_max'], spec['bins_per_decade'])
         declarations.append(PowerspecDeclaration(
@@ -295,11 +312,11 @@ def _mesh(gridsize, role):
 
 
 def interpolate_upstream(components, gridsizes_upstream, gridsize_global, order, deconvolve,
-                         interlace, a=1.0):
+                         interlace, a=1.0, role='powerspec'):
     """interpolate_upstream(components, ..., quantity='ρ', output_space='Fourier')
     (mesh.py:492-635) with add_upstream_to_global_slabs (mesh.py:654-711): the mesh whose
-    Fourier view holds the global slab.  The meshes are of the roles 'powerspec' and
-    'powerspec upstream', apart from those of gravity()."""
+    Fourier view holds the global slab.  The meshes are of the roles `role` and
+    `role` + ' upstream' ('powerspec' by default), apart from those of gravity()."""
     from .interactions import (_aligned, _check_halo_reach, group_components,
                                lattice_shifts)
     p = commons.params
@@ -309,15 +326,15 @@ def interpolate_upstream(components, gridsizes_upstream, gridsize_global, order,
 
     def upstream_mesh(g):
         if slab_global is None and g == gridsize_global:
-            return _mesh(gridsize_global, 'powerspec')
-        return _mesh(g, 'powerspec upstream')
+            return _mesh(gridsize_global, role)
+        return _mesh(g, role + ' upstream')
 
     def add_to_global(up, deconv_order, nlattice=1, shift=(0, 0, 0)):
         nonlocal slab_global
         if slab_global is None and up.gridsize == gridsize_global:
             slab_global = up.fourier_operate(deconv_order, nlattice, shift)
         elif slab_global is None:
-            slab_global = _mesh(gridsize_global, 'powerspec')
+            slab_global = _mesh(gridsize_global, role)
             slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='=')
         else:
             slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='+=')

@@ -13,6 +13,8 @@ Mirrors (does not import) the relevant slice of the reference's commons.py:
   N_rungs                commons.py:3891
   cell_centered          commons.py:3926
   nghosts                commons.py:4411-4432
+  render2D_select        commons.py:2718-2760, render2D_options :4080-4154 (checks :6021-6040)
+  terminal_width         commons.py:4044
 A parameter file is Python source executed in a namespace that holds the
 units (commons.py:2001-2140); `load_params` does the same for the names above
 and ignores everything else (I/O, cosmology tables, ... are out of scope).
@@ -96,7 +98,8 @@ _PATH_PARAMETERS = ('G_Newton', 'N_rungs', 'boxsize', 'cell_centered', 'ewald_gr
                     'enable_Hubble', 'Δt_base_background_factor', 'Δt_base_nonlinear_factor',
                     'Δt_increase_max_factor', 'Δt_rung_factor', 'Δa_max_early', 'Δa_max_late',
                     'static_timestepping', 'output_times', 't_begin', 'output_dirs', 'output_bases',
-                    'snapshot_type', 'gadget_snapshot_params', 'initial_conditions')
+                    'snapshot_type', 'gadget_snapshot_params', 'initial_conditions',
+                    'render2D_select', 'render2D_options', 'terminal_width')
 
 
 def load_params(source=None, **overrides):
@@ -285,12 +288,17 @@ def load_params(source=None, **overrides):
     p.N_rungs = int(user.get('N_rungs', 8))
     p.cell_centered = bool(user.get('cell_centered', True))
     _load_powerspec_params(p, user, units)
+    _load_render2D_params(p, user)
     # nghosts (commons.py:4411-4432): default 2 comes from the PCS default of the
-    # power-spectrum options; force interpolation and differentiation orders raise it
-    # (powerspec_options default: PCS, interlaced -> 4//2 = 2, + 1 with cell-vertex grids)
-    order = max(p.powerspec_options['interpolation'].values())
-    interlaced = any(v != 'sc' for v in p.powerspec_options['interlace'].values())
-    nghosts = order//2 + int(interlaced and (order % 2 != 0 or not p.cell_centered))
+    # power-spectrum and 2D render options; force interpolation and differentiation orders
+    # raise it (powerspec_options default: PCS, interlaced -> 4//2 = 2, + 1 with cell-vertex
+    # grids)
+    nghosts = 0
+    for options in (p.powerspec_options, p.render2D_options):
+        order = max(options['interpolation'].values())
+        interlaced = any(v != 'sc' for v in options['interlace'].values())
+        nghosts = max(nghosts,
+                      order//2 + int(interlaced and (order % 2 != 0 or not p.cell_centered)))
     for force, d in p.potential_options['interpolation'].items():
         for m, order in d.items():
             lattices = tuple(p.potential_options['interlace'].get(force, {}).get(m, ('sc', 'sc')))
@@ -350,16 +358,18 @@ def load_params(source=None, **overrides):
         p.output_times[default_param] += _times(rest)
     else:
         p.output_times[default_param] = _times(ot)
-    # which of those dump times are snapshot times and which power-spectrum times, per time
-    # parameter (the other output kinds — renders, bispectra — are dumps of the time loop too,
-    # but nothing is written for them)
+    # which of those dump times are snapshot times, which power-spectrum times and which 2D
+    # render times, per time parameter (the other output kinds — 3D renders, bispectra — are
+    # dumps of the time loop too, but nothing is written for them)
     def _kind_times(v, kind):
         if isinstance(v, dict):
             return _times(v.get(kind))
         return ()
     p.snapshot_times = {'a': (), 't': ()}
     p.powerspec_times = {'a': (), 't': ()}
-    for kind, kind_times in (('snapshot', p.snapshot_times), ('powerspec', p.powerspec_times)):
+    p.render2D_times = {'a': (), 't': ()}
+    for kind, kind_times in (('snapshot', p.snapshot_times), ('powerspec', p.powerspec_times),
+                             ('render2D', p.render2D_times)):
         if isinstance(ot, dict) and set(ot) & {'a', 't'}:
             for tp in ('a', 't'):
                 kind_times[tp] = _kind_times(ot.get(tp), kind)
@@ -373,10 +383,13 @@ def load_params(source=None, **overrides):
     # every kind, as in the reference — kept apart so that output_dirs stays {'snapshot': ...}
     p.powerspec_dir = str(od) if isinstance(od, str) and od else (
         str(od.get('powerspec')) if isinstance(od, dict) and od.get('powerspec') else None)
+    # the 2D render directory, likewise
+    p.render2D_dir = str(od) if isinstance(od, str) and od else (
+        str(od.get('render2D')) if isinstance(od, dict) and od.get('render2D') else None)
     if isinstance(od, str):
         od = {'snapshot': od}
     p.output_dirs = {k: str(v) for k, v in dict(od).items() if v}
-    p.output_bases = {'snapshot': 'snapshot', 'powerspec': 'powerspec'}
+    p.output_bases = {'snapshot': 'snapshot', 'powerspec': 'powerspec', 'render2D': 'render2D'}
     p.output_bases.update({k: str(v) for k, v in dict(user.get('output_bases', {})).items()})
     p.snapshot_type = str(user.get('snapshot_type', 'concept')).lower()
     p.initial_conditions = user.get('initial_conditions', '')
@@ -497,6 +510,93 @@ def _load_powerspec_params(p, user, units):
         if isinstance(v, str):
             d[k] = float(eval(v.replace('h', f'({h})'), {}, dict(units)))
     p.powerspec_options = opts
+
+
+def _load_render2D_params(p, user):
+    """render2D_select (commons.py:2718-2760), render2D_options (commons.py:4080-4154) with the
+    checks on axis and extent (commons.py:6021-6040), and terminal_width (commons.py:4044), with
+    the reference's defaults, key folding and errors."""
+    dos = ('data', 'image', 'terminalimage')
+    if 'render2D_select' in user:
+        sel = user['render2D_select']
+        sel = dict(sel) if isinstance(sel, dict) else {'default': sel}
+        for key, val in list(sel.items()):
+            if isinstance(val, dict):
+                sel[key] = {k.replace(' ', '').replace('-', '').replace('_', ''): v
+                            for k, v in val.items()}
+        sel.setdefault('default', {do: False for do in dos})
+    else:
+        sel = {'default': {do: True for do in dos}}
+    for key, val in list(sel.items()):
+        if isinstance(val, dict):
+            for do in dos:
+                val.setdefault(do, False)
+            unknown = ', '.join(f'"{do}"' for do in sorted(set(val) - set(dos)))
+            if unknown:
+                raise ValueError(f'Unknown selections in render2D_select["{key}"]: {unknown}')
+        else:
+            sel[key] = {do: bool(val) for do in dos}
+    p.render2D_select = sel
+    defaults = {
+        'upstream gridsize': {'default': -1},
+        'global gridsize': {'default': -1},
+        'terminal resolution': {'default': -1},
+        'interpolation': {'default': 'PCS'},
+        'deconvolve': {'default': False},
+        'interlace': {'default': False},
+        'axis': {'default': 'z'},
+        'extent': {'default': (0, 0.1*p.boxsize)},
+        'colormap': {'default': 'inferno'},
+        'enhance': {'default': True},
+    }
+    opts = {k: (dict(v) if isinstance(v, dict) else v)
+            for k, v in dict(user.get('render2D_options') or {}).items()}
+    if 'gridsize' in opts:
+        d = opts.pop('gridsize')
+        if not isinstance(d, dict):
+            d = {'default': d}
+        opts.setdefault('upstream gridsize', dict(d))
+        opts.setdefault('global gridsize', dict(d))
+    for key, d in list(opts.items()):
+        if not isinstance(d, dict):
+            opts[key] = {'default': d}
+    for key in opts:
+        if key not in defaults:
+            raise ValueError(f'render2D_options["{key}"] not implemented')
+    for key, d_defaults in defaults.items():
+        d = opts.setdefault(key, {})
+        for k, v in d_defaults.items():
+            d.setdefault(k, v)
+    for name in ('global gridsize', 'terminal resolution'):
+        d = opts[name]
+        for k, v in d.items():
+            d[k] = int(round(v))
+    d = opts['interpolation']
+    for k, v in d.items():
+        d[k] = int(interpolation_orders.get(str(v).upper(), v))
+    d = opts['interlace']
+    for k, v in d.items():
+        d[k] = _interlace2latticekind(v)
+    d = opts['axis']
+    for k, v in d.items():
+        d[k] = str(v).lower()
+        if d[k] not in ('x', 'y', 'z'):
+            raise ValueError(f'render2D_options["axis"]["{k}"] = "{d[k]}" ∉ {{"x", "y", "z"}}')
+    d = opts['extent']
+    for k, v in d.items():
+        v = tuple(float(x) for x in (v if isinstance(v, (tuple, list, np.ndarray)) else (v,)))
+        if len(v) == 1:
+            v = (0.0, v[0])
+        v = (min(v), max(v))
+        if v[0] < 0 or v[1] > p.boxsize:
+            raise ValueError(f'render2D_options["extent"]["{k}"] = ({v[0]}*Mpc, {v[1]}*Mpc) '
+                             'is out-of-bounds')
+        if v[0] == v[1]:
+            raise ValueError(f'Equal limits on render2D_options["extent"]["{k}"] '
+                             f'= ({v[0]}*Mpc, {v[1]}*Mpc)')
+        d[k] = v
+    p.render2D_options = opts
+    p.terminal_width = int(user.get('terminal_width', 80))
 
 
 def is_selected(component, d, accumulate=False, default=None):

@@ -5,6 +5,7 @@ FFTW slabs (mesh.py:492-710 interpolate_upstream, :3769-3866 get_fftw_slab,
 communication.py:1666 get_buffer): one persistent mesh per (grid size,
 device), living in HBM, reused across calls."""
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -467,6 +468,62 @@ class PotentialMesh:
         check(_L.cg_powerspec_bin(self._ctx, _ptr(k_bin_indices), int(k2_max), int(nbins),
                                   _ptr(out), _ptr(ws), ws.numel()))
         return out
+
+    # -- 2D render (graphics.py:1374-1755; csrc/cg_render.hip) -------------------------
+    def render2D_project(self, axis, plane_bgn, plane_end, frac_bgn, frac_end, factor, out=None):
+        """project_render2D (graphics.py:1374-1532) of this mesh's real-space values: the N x N
+        image, in its final orientation, of this domain's part of the planes
+        [plane_bgn, plane_end) along axis 'x' | 'y' | 'z' (cg_render2d_project)."""
+        N = self.gridsize
+        if out is None:
+            out = torch.empty((N, N), dtype=torch.float64, device=self.device)
+        elif (out.dtype != torch.float64 or out.device != self.device or not out.is_contiguous()
+                or out.numel() != N*N):
+            raise lib.ConceptGPUError(f'render2D_project(): the image must be a contiguous '
+                                      f'float64 tensor of {N} x {N} pixels on {self.device}')
+        check(_L.cg_render2d_project(self._ctx, 'xyz'.index(axis), int(plane_bgn), int(plane_end),
+                                     float(frac_bgn), float(frac_end), float(factor), _ptr(out)))
+        return out
+
+    def _check_image(self, image):
+        if (image.dtype != torch.float64 or image.device != self.device
+                or not image.is_contiguous() or image.numel() < 1):
+            raise lib.ConceptGPUError(
+                f'a render image must be a contiguous, non-empty float64 tensor on {self.device}')
+
+    def render2D_minmax(self, image, exponent=1.0):
+        """Device tensor (min, max) of image**exponent (cg_render2d_minmax)."""
+        self._check_image(image)
+        key = (self.device, 'render2D')
+        ws = _stage_buffers.get(key)
+        if ws is None:
+            ws = _stage_buffers[key] = torch.empty(int(_L.cg_render2d_workspace()),
+                                                   dtype=torch.float64, device=self.device)
+        out = torch.empty(2, dtype=torch.float64, device=self.device)
+        check(_L.cg_render2d_minmax(self._ctx, _ptr(image), image.numel(), float(exponent),
+                                    _ptr(out), _ptr(ws)))
+        return out
+
+    def render2D_histogram(self, image, exponent, bin_edges):
+        """np.histogram(image**exponent, n_bins)[0] as an int64 device tensor, for the n_bins + 1
+        uniform edges `bin_edges` (float64 device tensor) (cg_render2d_histogram)."""
+        self._check_image(image)
+        self._check_image(bin_edges)
+        n_bins = bin_edges.numel() - 1
+        counts = torch.empty(n_bins, dtype=torch.int64, device=self.device)
+        check(_L.cg_render2d_histogram(self._ctx, _ptr(image), image.numel(), float(exponent),
+                                       _ptr(bin_edges), n_bins, _ptr(counts)))
+        return counts
+
+    def render2D_apply(self, image, exponent=1.0, vmin=-math.inf, vmax=math.inf, shift=0.0,
+                       scale=1.0, fill=-1.0):
+        """In place: image = (clamp(image**exponent, vmin, vmax) - shift)*scale, or `fill`
+        everywhere when fill >= 0 (cg_render2d_apply)."""
+        self._check_image(image)
+        check(_L.cg_render2d_apply(self._ctx, _ptr(image), image.numel(), float(exponent),
+                                   float(vmin), float(vmax), float(shift), float(scale),
+                                   float(fill)))
+        return image
 
     def deposit_general(self, pos, contribution, order=2, shift=(0.0, 0.0, 0.0)):
         """interpolate_particles of order 1..4 with a lattice shift (mesh.py:1512-1636)"""

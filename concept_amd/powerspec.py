@@ -10,15 +10,17 @@ import os
 import sys
 
 
-def main(argv=None):
-    parser = argparse.ArgumentParser(prog='python -m concept_amd.powerspec',
-                                     description=__doc__.split('\n\n')[1])
+def snapshot_utility(argv, prog, description, kind):
+    """The part the snapshot utilities share (utilities.py:465-497): parse the command line,
+    load the parameters with the snapshot's box size and the snapshot itself; returns
+    (components, a, t, <output dir>/<output_bases[kind]>_<snapshot basename>)."""
+    parser = argparse.ArgumentParser(prog=prog, description=description)
     parser.add_argument('snapshot')
     parser.add_argument('--params', default=None, help='parameter file')
     parser.add_argument('--output-dir', default=None)
     args = parser.parse_args(argv)
     import torch  # noqa: F401  (before the library, see concept_amd.lib)
-    from . import analysis, commons, snapshot
+    from . import commons, snapshot
     from .integration import Cosmology
     p = commons.load_params(args.params)
     head = snapshot.load(args.snapshot, only_params=True, params=p,
@@ -33,12 +35,19 @@ def main(argv=None):
         cosmo.init_time()
         t = cosmo.cosmic_time(a)
     output_dir = args.output_dir or os.path.dirname(os.path.abspath(args.snapshot))
-    base = p.output_bases.get('powerspec', 'powerspec')
+    base = p.output_bases.get(kind, kind)
     # the snapshot's basename without its extension (utilities.py:465-497); the digits after
     # the point of a dump name such as snapshot_a=0.12 are no extension
     root, ext = os.path.splitext(os.path.basename(args.snapshot.rstrip('/')))
     name = root if ext and not ext[1:].isdigit() else root + ext
     filename = os.path.join(output_dir, f'{base}_{name}' if base else name)
+    return components, a, t, filename
+
+
+def main(argv=None):
+    components, a, t, filename = snapshot_utility(
+        argv, 'python -m concept_amd.powerspec', __doc__.split('\n\n')[1], 'powerspec')
+    from . import analysis
     analysis.powerspec(components, filename, a=a, t=t)
     print(f'power spectrum written to "{filename}"')
     return filename

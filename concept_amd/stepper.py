@@ -717,6 +717,12 @@ class Timeloop(RungStepper):
             # main.py:1676-1700)
             dumpers.append(self.powerspec_dumper(p.powerspec_dir,
                                                  p.output_bases.get('powerspec', 'powerspec')))
+        if on_dump is None and getattr(p, 'render2D_dir', None) and (
+                p.render2D_times['a'] or p.render2D_times['t']):
+            # 2D renders at the times output_times lists for 'render2D' (main.dump,
+            # main.py:1676-1700)
+            dumpers.append(self.render2D_dumper(p.render2D_dir,
+                                                p.output_bases.get('render2D', 'render2D')))
         if len(dumpers) == 1:
             self.on_dump = dumpers[0]
         elif dumpers:
@@ -1082,6 +1088,28 @@ class Timeloop(RungStepper):
             name = f'{output_dir}/{output_base}{sep}{dump_time.time_param}={value:.{ndigits}f}'
             analysis.powerspec(loop.components, name, a=loop.cosmo.a, t=loop.cosmo.t)
             loop.powerspecs_written.append(name)
+        return on_dump
+
+    def render2D_dumper(self, output_dir, output_base='render2D', stream=None):
+        """An on_dump callback that writes the 2D renders render2D_select asks for
+        (render.render2D: data file, PNG, terminal image on `stream`) at the times output_times
+        lists for 'render2D', named <output_dir>/<output_base>_<a|t>=<value> plus the extension,
+        with the digits of snapshot_dumper (main.dump, main.py:1676-1700)."""
+        from . import render
+        p = self.params
+        ndigits = self._dump_ndigits()
+        sep = '_' if output_base else ''
+        self.renders2D_written = []
+
+        def on_dump(loop, dump_time):
+            value = dump_time.a if dump_time.time_param == 'a' else dump_time.t
+            if not any(abs(value - v) <= 1e-12*max(abs(v), 1e-300)
+                       for v in p.render2D_times[dump_time.time_param]):
+                return
+            name = f'{output_dir}/{output_base}{sep}{dump_time.time_param}={value:.{ndigits}f}'
+            _, files = render.render2D(loop.components, name, a=loop.cosmo.a, t=loop.cosmo.t,
+                                       stream=stream)
+            loop.renders2D_written.extend(files)
         return on_dump
 
     # -- main.timeloop (main.py:102-471) ---------------------------------------------------

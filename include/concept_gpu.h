@@ -696,6 +696,37 @@ int cg_powerspec_bin(cg_ctx *ctx, const int32_t *k_bin_indices /*DEV k2_max+1*/,
                      int32_t nbins, double *power_out /*DEV nbins*/, double *workspace /*DEV*/,
                      int64_t workspace_doubles);
 
+/* --- 2D render (graphics.py:1027-1955) --------------------------------------------
+ * cg_render2d_project: project_render2D (graphics.py:1374-1532) of the context's real-space
+ *   mesh (after the inverse transform) along axis (0 x, 1 y, 2 z): the planes
+ *   [plane_bgn, plane_end) of the axis are summed, the first one weighted by frac_bgn and the
+ *   last one by frac_end (graphics.py:1387-1400, 1482-1504; one plane alone takes frac_bgn),
+ *   times factor (the (a*cellsize)^3 of graphics.py:1516).  image: N x N doubles in the final
+ *   orientation (the transpose and the vertical flip of graphics.py:1524-1531 are part of the
+ *   store).  An x-slab domain projects its own layers: its columns of the image for the axes y
+ *   and z, a partial image for axis x, zero elsewhere; the caller sums the domains' images.
+ *   Planes outside the range are not read.  Deterministic (fixed summation order).
+ * cg_render2d_minmax: minmax_out[0, 1] = min and max of image[i]^exponent (graphics.py:
+ *   1619-1620, 1745-1746); workspace: cg_render2d_workspace() doubles (DEV), any content.
+ * cg_render2d_histogram: np.histogram(image^exponent, n_bins)[0] (graphics.py:1634, 1686) by
+ *   numpy's rule for uniform bins over the edges bin_edges = linspace(min, max, n_bins + 1);
+ *   counts_out is overwritten.  Integer counts: the same image gives the same counts.
+ * cg_render2d_apply: in place, image[i] = (min(max(image[i]^exponent, vmin), vmax) - shift)
+ *   * scale (graphics.py:1683-1685, 1713-1717, 1755), or fill for every pixel when fill >= 0
+ *   (the homogeneous image of graphics.py:1747-1751).  An exponent of 1 leaves the values
+ *   as they are. */
+int cg_render2d_project(cg_ctx *ctx, int axis, int64_t plane_bgn, int64_t plane_end,
+                        double frac_bgn, double frac_end, double factor,
+                        double *image /*DEV N*N*/);
+int64_t cg_render2d_workspace(void);
+int cg_render2d_minmax(cg_ctx *ctx, const double *image /*DEV n*/, int64_t n, double exponent,
+                       double *minmax_out /*DEV 2*/, double *workspace /*DEV*/);
+int cg_render2d_histogram(cg_ctx *ctx, const double *image /*DEV n*/, int64_t n, double exponent,
+                          const double *bin_edges /*DEV n_bins+1*/, int32_t n_bins,
+                          int64_t *counts_out /*DEV n_bins*/);
+int cg_render2d_apply(cg_ctx *ctx, double *image /*DEV n*/, int64_t n, double exponent,
+                      double vmin, double vmax, double shift, double scale, double fill);
+
 /* --- debug fetch (parity tests) -------------------------------------------- */
 int cg_fetch(cg_ctx *ctx, int which, double *out /*HOST*/, int64_t n_doubles);
 /* CIC cell indices exactly as set_weights_CIC returns them for the deposit
