@@ -95,6 +95,11 @@ def main():
         if 'traj_pm' in arg:
             for streaming in (True, False):
                 tt.test_stepper_timeloop_replays_reference_integrals(golden, arg, streaming)
+    elif case == 'blobs':
+        import test_gpu_general_interp
+        interp, lattice, diff = arg.split(',')
+        test_gpu_general_interp.test_gravity_pm_on_tile_sorted_blobs_vs_oracle(interp, lattice,
+                                                                              int(diff))
     elif case == 'config4':
         import test_gpu_fluid
         n_side, gs = (int(v) for v in arg.split(','))

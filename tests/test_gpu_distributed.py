@@ -253,6 +253,9 @@ COMPONENT_CASES = [
     ('traj', 'traj_pm_n8_g16'), ('traj', 'traj_p3m_n8_g32'),
     # the clustered box with five rungs populated: a slab holds most of a clump
     ('traj', 'traj_p3m_n16_g32_clustered'),
+    # tile-sorted blobs through interlaced TSC: the LDS boxes of the general deposit and gather
+    # on slabs (layers mapped through the halo)
+    ('blobs', 'TSC,bcc,2'),
 ]
 
 
