@@ -21,16 +21,6 @@
 // Compiled with -ffp-contract=off; FP64 throughout, k² as an integer.
 #include "cg_internal.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 namespace {
 
 constexpr int kWaves = 4;                 // waves per workgroup of k_powerspec_bin

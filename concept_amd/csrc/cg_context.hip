@@ -20,6 +20,20 @@ void cg_set_error(const char *fmt, ...) {
 }
 
 extern "C" const char *cg_last_error(void) { return g_err.c_str(); }
+
+void cg_devmem::release() {
+    (void)hipFree(ptr);
+    ptr = nullptr;
+    bytes = 0;
+}
+int cg_devmem::reserve(cg_ctx *c, size_t need) {
+    if (need <= bytes) return 0;
+    if (ptr) CG_HIP(hipStreamSynchronize(c->stream));  // (an empty buffer is in nobody's use)
+    release();
+    CG_HIP(hipMalloc(&ptr, need));
+    bytes = need;
+    return 0;
+}
 extern "C" int cg_abi_version(void) { return CG_ABI_VERSION; }
 
 static const double kMachineEps = 2.220446049250313e-16;  // np.finfo(float64).eps, commons.py:1814
@@ -80,16 +94,16 @@ static int make_plans(cg_ctx *c) {
     size_t wf = 0, wb = 0;
     CG_FFT(rocfft_plan_get_work_buffer_size(c->plan_fwd, &wf));
     CG_FFT(rocfft_plan_get_work_buffer_size(c->plan_bwd, &wb));
-    c->fft_work_bytes = wf > wb ? wf : wb;
-    if (c->fft_work_bytes) {
-        CG_HIP(hipMalloc(&c->fft_work, c->fft_work_bytes));
-        c->device_bytes += (i64)c->fft_work_bytes;
+    const size_t work = wf > wb ? wf : wb;
+    if (work) {
+        if (c->fft_work.reserve(c, work)) return 1;
+        c->device_bytes += (i64)work;
     }
     CG_FFT(rocfft_execution_info_create(&c->info_fwd));
     CG_FFT(rocfft_execution_info_create(&c->info_bwd));
-    if (c->fft_work_bytes) {
-        CG_FFT(rocfft_execution_info_set_work_buffer(c->info_fwd, c->fft_work, c->fft_work_bytes));
-        CG_FFT(rocfft_execution_info_set_work_buffer(c->info_bwd, c->fft_work, c->fft_work_bytes));
+    if (work) {
+        CG_FFT(rocfft_execution_info_set_work_buffer(c->info_fwd, c->fft_work, work));
+        CG_FFT(rocfft_execution_info_set_work_buffer(c->info_bwd, c->fft_work, work));
     }
     return 0;
 }
@@ -109,24 +123,17 @@ struct DistPlans {
     std::map<i64, std::pair<rocfft_plan, rocfft_plan>> layers2d;  // by number of layers
     rocfft_plan x_fwd = nullptr, x_bwd = nullptr;
     rocfft_execution_info info = nullptr;
-    void *work = nullptr;
-    size_t work_bytes = 0;
+    cg_buf<void> work;  // (freed after the plans are destroyed: dist_plans_destroy)
 };
 
 static int dist_work(cg_ctx *c, rocfft_plan plan) {
     DistPlans *d = c->dist_plans;
     size_t w = 0;
     CG_FFT(rocfft_plan_get_work_buffer_size(plan, &w));
-    if (w > d->work_bytes) {
-        CG_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(d->work);
-        d->work = nullptr;
-        CG_HIP(hipMalloc(&d->work, w));
-        d->work_bytes = w;
-    }
+    if (d->work.reserve(c, w)) return 1;
     if (!d->info) CG_FFT(rocfft_execution_info_create(&d->info));
-    if (d->work_bytes)
-        CG_FFT(rocfft_execution_info_set_work_buffer(d->info, d->work, d->work_bytes));
+    if (d->work.bytes)
+        CG_FFT(rocfft_execution_info_set_work_buffer(d->info, d->work, d->work.bytes));
     CG_FFT(rocfft_execution_info_set_stream(d->info, c->stream));
     return 0;
 }
@@ -266,12 +273,20 @@ static void dist_plans_destroy(cg_ctx *c) {
     if (d->x_fwd) rocfft_plan_destroy(d->x_fwd);
     if (d->x_bwd) rocfft_plan_destroy(d->x_bwd);
     if (d->info) rocfft_execution_info_destroy(d->info);
-    (void)hipFree(d->work);
     delete d;
     c->dist_plans = nullptr;
 }
 
+// a table of the host in a device buffer of its size
+static bool upload(cg_ctx *c, cg_devmem &buf, const std::vector<double> &host) {
+    const size_t bytes = sizeof(double) * host.size();
+    return !buf.reserve(c, bytes) &&
+           hipMemcpy(buf.ptr, host.data(), bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
 static bool g_rocfft_ready = false;
+
+static int ctx_init(cg_ctx *c);
 
 extern "C" int cg_create(const cg_params *p, cg_ctx **out) {
     CG_CHECK(p && out, "cg_create: null argument");
@@ -308,21 +323,26 @@ extern "C" int cg_create(const cg_params *p, cg_ctx **out) {
     cg_ctx *c = new cg_ctx();
     c->sub_begin = new SubstepBegin();
     c->p = *p;
+    if (ctx_init(c)) {  // (every failure of the set-up leaves here)
+        cg_destroy(c);
+        return 1;
+    }
+    *out = c;
+    return 0;
+}
+
+// geometry, mesh, tables and FFT of a new context
+static int ctx_init(cg_ctx *c) {
+    const cg_params *p = &c->p;
     c->N = p->gridsize;
     c->pad = (c->N % 16 == 0) ? c->N + 16 : c->N + 2;
     if (p->nprocs == 1) c->xmap = XMap{0, c->N, 0, 1};
     else c->xmap = XMap{(c->N / p->nprocs) * p->rank, c->N / p->nprocs, 3, 0};
     c->ny = (c->N % 16 == 0) ? c->N + 1 : c->N;
     c->mesh_doubles = (c->xmap.nxl + 2 * c->xmap.G) * c->ny * c->pad;
-    auto fail = [&]() {
-        cg_destroy(c);
-        return 1;
-    };
-    if (hipMalloc(&c->mesh, sizeof(double) * c->mesh_doubles) != hipSuccess) {
-        cg_set_error("cg_create: hipMalloc of the %lld^3 mesh (%.2f GB) failed", (long long)c->N,
-                     c->mesh_doubles * 8e-9);
-        return fail();
-    }
+    CG_CHECK(!c->mesh.reserve(c, sizeof(double) * c->mesh_doubles),
+             "cg_create: hipMalloc of the %lld^3 mesh (%.2f GB) failed", (long long)c->N,
+             c->mesh_doubles * 8e-9);
     c->device_bytes += 8 * c->mesh_doubles;
     c->mesh0 = c->mesh + (i64)c->xmap.G * c->ny * c->pad;
     if (p->nprocs == 1) {  // Fourier space shares the mesh in place, all rows
@@ -350,41 +370,27 @@ extern "C" int cg_create(const cg_params *p, cg_ctx **out) {
             ts[i] = sin(tn[i]);
             tq[i] = tn[i] / ts[i];
         }
-        if (hipMalloc(&c->ktab_n, 8 * c->N) != hipSuccess ||
-            hipMalloc(&c->ktab_s, 8 * c->N) != hipSuccess ||
-            hipMalloc(&c->ktab_q, 8 * c->N) != hipSuccess ||
-            hipMemcpy(c->ktab_n, tn.data(), 8 * c->N, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->ktab_q, tq.data(), 8 * c->N, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(c->ktab_s, ts.data(), 8 * c->N, hipMemcpyHostToDevice) != hipSuccess) {
-            cg_set_error("cg_create: k-space table upload failed");
-            return fail();
-        }
+        CG_CHECK(upload(c, c->ktab_n, tn) && upload(c, c->ktab_s, ts) && upload(c, c->ktab_q, tq),
+                 "cg_create: k-space table upload failed");
     }
     // tiles: cubic, 16 cells when the grid allows (at least 2 tiles per dimension),
     // for the particle memory order and the LDS-tiled deposit / gather kernels
     {
         int t = 16;
         while (t > 2 && (c->N % t || c->N / t < 2 || c->xmap.nxl % t)) t /= 2;
-        if (c->N % t || c->xmap.nxl % t) {
-            cg_set_error("cg_create: gridsize %lld / %d domains is not divisible by 2",
-                         (long long)c->N, p->nprocs);
-            return fail();
-        }
+        CG_CHECK(c->N % t == 0 && c->xmap.nxl % t == 0,
+                 "cg_create: gridsize %lld / %d domains is not divisible by 2", (long long)c->N,
+                 p->nprocs);
         c->tiles = {t, t, t, (int)(c->xmap.nxl / t), (int)(c->N / t), (int)(c->N / t)};
         c->ntiles = (i64)c->tiles.ntx * c->tiles.nty * c->tiles.ntz;
         // 8 buckets per tile (which of the +x/+y/+z neighbour tiles a particle's CIC
         // cloud reaches), see cg_particles.hip
-        if (hipMalloc(&c->tile_count, 4 * (8 * c->ntiles + 1)) != hipSuccess ||
-            hipMalloc(&c->tile_cursor, 4 * (8 * c->ntiles + 1)) != hipSuccess) {
-            cg_set_error("cg_create: tile table allocation failed");
-            return fail();
-        }
+        CG_CHECK(!c->tile_count.reserve(c, 4 * (8 * c->ntiles + 1)) &&
+                     !c->tile_cursor.reserve(c, 4 * (8 * c->ntiles + 1)),
+                 "cg_create: tile table allocation failed");
         c->device_bytes += 8 * (8 * c->ntiles + 1);
-        if (hipMalloc(&c->err_flags, 4) != hipSuccess ||
-            hipMemset(c->err_flags, 0, 4) != hipSuccess) {
-            cg_set_error("cg_create: error word allocation failed");
-            return fail();
-        }
+        CG_CHECK(!c->err_flags.reserve(c, 4) && hipMemset(c->err_flags, 0, 4) == hipSuccess,
+                 "cg_create: error word allocation failed");
     }
     // FFT backend: the hand-written passes for power-of-two grids, rocFFT otherwise
     // (CONCEPT_GPU_FFT=rocfft forces the library, for A/B measurements)
@@ -401,18 +407,14 @@ extern "C" int cg_create(const cg_params *p, cg_ctx **out) {
             tw[2 * k] = (double)cosl(a);
             tw[2 * k + 1] = (double)sinl(a);
         }
-        if (hipMalloc(&c->fft_tw, 16 * c->N) != hipSuccess ||
-            hipMemcpy(c->fft_tw, tw.data(), 16 * c->N, hipMemcpyHostToDevice) != hipSuccess) {
-            cg_set_error("cg_create: FFT twiddle upload failed");
-            return fail();
-        }
+        CG_CHECK(upload(c, c->fft_tw, tw), "cg_create: FFT twiddle upload failed");
     } else if (p->nprocs == 1 && make_plans(c)) {  // (x-slab domains: plans made on first use)
-        return fail();
+        return 1;
     }
-    *out = c;
     return 0;
 }
 
+// (the buffers go with the context, after the plans that use them)
 extern "C" int cg_destroy(cg_ctx *c) {
     if (!c) return 0;
     dist_plans_destroy(c);
@@ -420,28 +422,7 @@ extern "C" int cg_destroy(cg_ctx *c) {
     if (c->plan_bwd) rocfft_plan_destroy(c->plan_bwd);
     if (c->info_fwd) rocfft_execution_info_destroy(c->info_fwd);
     if (c->info_bwd) rocfft_execution_info_destroy(c->info_bwd);
-    (void)hipFree(c->fft_work);
-    (void)hipFree(c->fft_tw);
-    (void)hipFree(c->mesh);
-    (void)hipFree(c->fetch_tmp);
-    (void)hipFree(c->ktab_n);
-    (void)hipFree(c->ktab_s);
-    (void)hipFree(c->ktab_q);
-    (void)hipFree(c->tile_count);
-    (void)hipFree(c->tile_cursor);
-    (void)hipFree(c->err_flags);
-    (void)hipFree(c->sr_tile_active);
-    (void)hipFree(c->mom2_partial);
-    (void)hipFree(c->sr_stats);
-    (void)hipFree(c->sr_sparse_partial);
-    (void)hipFree(c->scan_tmp);
-    (void)hipFree(c->tile_order_buf);
     if (c->tile_order_seen) (void)hipHostFree(c->tile_order_seen);
-    (void)hipFree(c->sr_tmp);
-    (void)hipFree(c->sr_sub_tmp);
-    (void)hipFree(c->srd_small);
-    (void)hipFree(c->srd_buf);
-    (void)hipFree(c->srd_rung);
     for (auto &look : c->srd_look)
         if (look.ev) (void)hipEventDestroy(look.ev);
     if (c->srd_host) (void)hipHostFree(c->srd_host);
@@ -455,9 +436,7 @@ extern "C" int cg_destroy(cg_ctx *c) {
         if (c->sr_join[i]) (void)hipEventDestroy(c->sr_join[i]);
     }
     if (c->sr_fork) (void)hipEventDestroy(c->sr_fork);
-    (void)hipFree(c->sr_active);
     delete c->sub_begin;
-    (void)hipFree(c->sub_partial);
     delete c;
     return 0;
 }
@@ -1118,7 +1097,7 @@ extern "C" int cg_shortrange_sweep_cells_active(
 extern "C" int cg_shortrange_stats(cg_ctx *c, int enable, uint64_t *out) {
     CG_CHECK(c, "cg_shortrange_stats: null context");
     if (enable) {
-        if (!c->sr_stats) CG_HIP(hipMalloc((void **)&c->sr_stats, 8 * sizeof(uint64_t)));
+        if (c->sr_stats.reserve(c, 8 * sizeof(uint64_t))) return 1;
         CG_HIP(hipMemsetAsync(c->sr_stats, 0, 8 * sizeof(uint64_t), c->stream));
         return 0;
     }
@@ -1128,8 +1107,7 @@ extern "C" int cg_shortrange_stats(cg_ctx *c, int enable, uint64_t *out) {
     }
     CG_HIP(hipStreamSynchronize(c->stream));
     if (out) CG_HIP(hipMemcpy(out, c->sr_stats, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    (void)hipFree(c->sr_stats);
-    c->sr_stats = nullptr;
+    c->sr_stats.release();
     return 0;
 }
 
@@ -1408,7 +1386,7 @@ extern "C" int cg_fetch(cg_ctx *c, int which, double *out, int64_t n_doubles) {
     }
     if (which == CG_FETCH_MESH_FOURIER) {
         CG_CHECK(c->p.nprocs == 1, "cg_fetch: the Fourier slab fetch is single-domain only");
-        if (!c->fetch_tmp) CG_HIP(hipMalloc(&c->fetch_tmp, 8 * ref_doubles));
+        if (c->fetch_tmp.reserve(c, 8 * ref_doubles)) return 1;
         if (cgk_transpose_fourier(c, c->mesh, c->fetch_tmp)) return 1;
         CG_HIP(hipStreamSynchronize(c->stream));
         CG_HIP(hipMemcpy(out, c->fetch_tmp, 8 * ref_doubles, hipMemcpyDeviceToHost));

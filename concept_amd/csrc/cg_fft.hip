@@ -25,16 +25,6 @@
 #include "cg_internal.h"
 #include "cg_kspace.h"  // its factor function pins fp-contract off itself
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 __device__ __forceinline__ double2 cmul(double2 a, double2 b) {
     return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }

@@ -14,16 +14,6 @@
 // Compiled with -ffp-contract=off; every expression keeps the reference's order.
 #include "cg_internal.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 // Fluid grids of an x-slab domain are its own layers double[nxl][N][N]; `mesh` is then the
 // first OWNED layer of the local buffer.
 __global__ __launch_bounds__(256) void k_fluid_add(double *__restrict__ mesh,

@@ -25,6 +25,17 @@ void cg_set_error(const char *fmt, ...);
         }                                                                                     \
     } while (0)
 
+// after a kernel launch
+#define CG_LAUNCH_CHECK()                                                                     \
+    do {                                                                                      \
+        hipError_t e_ = hipGetLastError();                                                    \
+        if (e_ != hipSuccess) {                                                               \
+            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
+                         __LINE__);                                                           \
+            return 1;                                                                         \
+        }                                                                                     \
+    } while (0)
+
 #define CG_FFT(call)                                                                          \
     do {                                                                                      \
         rocfft_status s_ = (call);                                                            \
@@ -84,20 +95,46 @@ struct TileGeom {
     int ntx, nty, ntz;  // tiles per dimension
 };
 
+// A device allocation that belongs to its holder (the context, DistPlans) and is freed with it.
+// reserve() returns at once when the buffer is large enough; otherwise it drains c->stream (the
+// old buffer may be in use), frees it and allocates the new size: the contents are not kept.
+// On failure the buffer is left empty, the error is set and 1 is returned.
+struct cg_ctx;
+struct cg_devmem {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    cg_devmem() = default;
+    cg_devmem(const cg_devmem &) = delete;
+    cg_devmem &operator=(const cg_devmem &) = delete;
+    ~cg_devmem() { release(); }
+    int reserve(cg_ctx *c, size_t need);
+    void release();
+};
+// ... seen as an array of T
+template <typename T>
+struct cg_buf : cg_devmem {
+    operator T *() const { return (T *)ptr; }
+};
+
 struct cg_ctx {
+    // ---- parameters and geometry ----
     cg_params p;
     hipStream_t stream = nullptr;
-    i64 N = 0, pad = 0;          // grid size and padded innermost length N+2
+    i64 N = 0, pad = 0;          // grid size and row pitch: N+16 when N is a multiple of 16, else N+2
     XMap xmap{};                 // local layers of the mesh buffer
-    double *mesh = nullptr;      // double[layers][N][pad], layers = nxl + 2G
-    double *mesh0 = nullptr;     // first OWNED layer (= mesh + G*N*pad)
-    i64 mesh_doubles = 0;
     // rows per x layer.  N rows are used; with N a power of two the layer stride N*pad*8 B
     // is 2^17 x odd at 1024^3 and the 1024 row segments an x-pass tile touches alias onto
     // few memory channels (measured with tools/stride_probe.cpp: 3.99 ms per in-place
     // sweep at stride 8,519,680 B, 3.52 ms at 8,528,000 B): one unused row per layer
     // breaks the pattern.
     i64 ny = 0;
+    CicGeom geom_deposit{}, geom_gather{};
+    i64 device_bytes = 0;        // cg_device_bytes: the mesh, the tile tables, rocFFT's work buffer
+
+    // ---- mesh and Fourier view ----
+    cg_buf<double> mesh;         // double[layers][ny][pad], layers = nxl + 2G
+    double *mesh0 = nullptr;     // first OWNED layer (= mesh + G*ny*pad)
+    i64 mesh_doubles = 0;
     // Fourier view: where the modes of this context live and which of them.  Mode (ki, kj, kk)
     // with array indices (a, b, kk), b in [f_j0, f_j0 + f_nj), sits at
     // four[a*f_si + (b - f_j0)*cp + kk], cp = pad/2.  Single domain: the mesh itself, in place
@@ -108,54 +145,71 @@ struct cg_ctx {
     double2 *four = nullptr;
     i64 f_si = 0;
     int f_j0 = 0, f_nj = 0;
-    double *fetch_tmp = nullptr; // lazily allocated, for CG_FETCH_MESH_FOURIER
-    // k-space tables: numerator n(k) and denominator sin(n(k)) by array index
-    double *ktab_n = nullptr, *ktab_s = nullptr, *ktab_q = nullptr;
-    // rocFFT
+    cg_buf<double> fetch_tmp;    // lazily allocated, for CG_FETCH_MESH_FOURIER
+    // k-space tables: numerator n(k), denominator sin(n(k)) and their quotient by array index
+    cg_buf<double> ktab_n, ktab_s, ktab_q;
+
+    // ---- FFT ----
+    // rocFFT (single domain; the plans are destroyed before fft_work is freed)
     rocfft_plan plan_fwd = nullptr, plan_bwd = nullptr;
-    struct DistPlans *dist_plans = nullptr;  // x-slab domains on the rocFFT backend (cg_context.hip)
     rocfft_execution_info info_fwd = nullptr, info_bwd = nullptr;
-    void *fft_work = nullptr;
-    size_t fft_work_bytes = 0;
+    cg_buf<void> fft_work;
+    struct DistPlans *dist_plans = nullptr;  // x-slab domains on the rocFFT backend (cg_context.hip)
     // hand-written FFT (cg_fft.hip): twiddles exp(-2 pi i k/N) as double2[N]
     bool custom_fft = false;
-    double *fft_tw = nullptr;
-    // side streams of the short-range sweep (its interior and face launches are independent and
-    // run side by side: a clustered box otherwise waits for the few dense tiles of each launch
-    // in turn), created at the first sweep
-    // a sub-step's first pass, deferred to the cell list that follows it (cg_substep.h)
-    struct SubstepBegin *sub_begin = nullptr;
-    bool sub_pending = false;
-    long long *sub_counts = nullptr;     // where the pending pass leaves the populations (DEV)
-    unsigned *sub_partial = nullptr;     // ... per workgroup first
-    size_t sub_partial_bytes = 0;
-    unsigned *sr_active = nullptr;   // [0] count, [64..] the cells that hold an active receiver
-    size_t sr_active_bytes = 0;
-    hipStream_t sr_streams[3] = {nullptr, nullptr, nullptr};
-    hipEvent_t sr_fork = nullptr, sr_join[3] = {nullptr, nullptr, nullptr};
-    unsigned long long *sr_stats = nullptr;   // cg_shortrange_stats: device counters while on
-    unsigned char *sr_tile_active = nullptr;  // cells sweep with rungs: one byte per tile
-    double *sr_sparse_partial = nullptr;      // cg_shortrange_sparse: per-workgroup partial sums
-    size_t sr_tile_active_cap = 0;
-    hipEvent_t *pass_events = nullptr;  // when set: 6 events recorded around the 5 passes
-    // particle sort scratch (owned, grown on demand)
+    cg_buf<double2> fft_tw;
+
+    // ---- tiles, sort and regions ----
     TileGeom tiles{};
-    unsigned int *tile_count = nullptr;   // [ntiles + 1]
-    unsigned int *tile_cursor = nullptr;  // [ntiles]
-    void *scan_tmp = nullptr;
+    i64 ntiles = 0;
+    cg_buf<unsigned> tile_count;   // [8 ntiles + 1]: 8 buckets per tile (cg_particles.hip)
+    cg_buf<unsigned> tile_cursor;  // [8 ntiles + 1]
+    cg_buf<void> scan_tmp;         // cg_exclusive_sum's temporary storage
     // tile kernels: heavy tiles first when the tiles' populations are far from equal
     // (cgk_tile_order; off = the plain walk)
-    unsigned int *tile_order = nullptr;  // the list [tile_order_cap], counters and bytes behind
-    unsigned int *tile_order_buf = nullptr;
+    cg_buf<unsigned> tile_order_buf;     // populations, the list, counters and ranks
+    unsigned int *tile_order = nullptr;  // the list [tile_order_cap] inside tile_order_buf
     unsigned tile_order_cap = 0;
     unsigned *tile_order_seen = nullptr;  // pinned: length of the list of the last build done
     bool tile_order_on = false;          // list and bytes of one build are there
     int tile_order_mode = -1;            // from CONCEPT_GPU_TILE_ORDER_MIN: 0 off, 1 on, 2 also on small boxes
     unsigned tile_order_floor = 1536;    // |CONCEPT_GPU_TILE_ORDER_MIN|
     const void *tile_order_src[2] = {nullptr, nullptr};  // (start, count) it was made from
-    size_t scan_tmp_bytes = 0;
-    void *sr_tmp = nullptr;  // short-range cell-list counters
-    size_t sr_tmp_bytes = 0;
+
+    // ---- fused pass and emigrants ----
+    // tile histogram of the NEXT drift prepared by cg_gather_kick_tiled_prepare
+    bool prep_valid = false;
+    const double *prep_pos = nullptr, *prep_mom = nullptr;
+    i64 prep_n = 0;
+    double prep_dtm = 0;
+    hipEvent_t *pass_events = nullptr;  // when set: 6 events recorded around the 5 passes
+    // caller-owned list of the particles leaving the slab with the prepared drift
+    i64 *emig_idx = nullptr;
+    unsigned *emig_count = nullptr;
+    i64 emig_cap = 0;
+    // fused kick + drift + scatter on x-slab domains: the particles the drift takes out of the
+    // slab are appended here as rows of 8 doubles (pos 3, mom 3, id bits, unused) — caller-owned
+    double *emig_rows = nullptr;
+    unsigned *emig_rows_count = nullptr;
+    i64 emig_rows_cap = 0;
+    // cg_set_momentum_sum: where the fused pass leaves the sum of |mom|^2 (null: not summed;
+    // caller-owned), and its per-workgroup partial sums
+    double *mom2_sum_out = nullptr;
+    cg_buf<double> mom2_partial;
+
+    // ---- short-range list and sweeps ----
+    cg_buf<unsigned> sr_tmp;  // cell-list and tile-list counters
+    // side streams of the short-range sweep (its interior and face launches are independent and
+    // run side by side: a clustered box otherwise waits for the few dense tiles of each launch
+    // in turn), created at the first sweep
+    hipStream_t sr_streams[3] = {nullptr, nullptr, nullptr};
+    hipEvent_t sr_fork = nullptr, sr_join[3] = {nullptr, nullptr, nullptr};
+    cg_buf<unsigned long long> sr_stats;   // cg_shortrange_stats: device counters while on
+    cg_buf<unsigned char> sr_tile_active;  // cells sweep with rungs: one byte per tile
+    cg_buf<unsigned> sr_active;   // [0] count, [64..] the cells that hold an active receiver
+    cg_buf<double> sr_sparse_partial;      // cg_shortrange_sparse: per-workgroup partial sums
+
+    // ---- dense tiles ----
     // the dense tiles' sweep (cg_shortrange_dense.hip): counters, pinned read-back, lists, stream;
     // srd_look: what is known about the cell lists built last (keyed by their offsets' address)
     struct SrdLook {
@@ -172,52 +226,112 @@ struct cg_ctx {
     int srd_quiet = 0;   // counted looks in a row that found no dense tile
     bool srd_hilbert_done = false;
     unsigned *srd_host = nullptr;
-    void *srd_small = nullptr, *srd_buf = nullptr, *srd_rung = nullptr;
-    size_t srd_small_bytes = 0, srd_buf_bytes = 0, srd_rung_bytes = 0;
+    cg_buf<unsigned> srd_small;
+    cg_buf<void> srd_buf;
+    cg_buf<signed char> srd_rung;
     hipStream_t srd_stream = nullptr;
     hipEvent_t srd_fork = nullptr, srd_join = nullptr;
-    void *sr_sub_tmp = nullptr;  // rows of the dense tiles while they are re-ordered by sub-cell
-    size_t sr_sub_bytes = 0;
-    i64 ntiles = 0;
-    CicGeom geom_deposit{}, geom_gather{};
-    // tile histogram of the NEXT drift prepared by cg_gather_kick_tiled_prepare
-    bool prep_valid = false;
-    const double *prep_pos = nullptr, *prep_mom = nullptr;
-    i64 prep_n = 0;
-    double prep_dtm = 0;
-    // caller-owned list of the particles leaving the slab with the prepared drift
-    i64 *emig_idx = nullptr;
-    unsigned *emig_count = nullptr;
-    i64 emig_cap = 0;
-    // fused kick + drift + scatter on x-slab domains: the particles the drift takes out of the
-    // slab are appended here as rows of 8 doubles (pos 3, mom 3, id bits, unused) — caller-owned
-    // cg_set_momentum_sum: where the fused pass leaves the sum of |mom|^2 (null: not summed)
-    double *mom2_sum_out = nullptr, *mom2_partial = nullptr;
-    size_t mom2_partial_bytes = 0;
-    double *emig_rows = nullptr;
-    unsigned *emig_rows_count = nullptr;
-    i64 emig_rows_cap = 0;
+    cg_buf<void> sr_sub_tmp;  // rows of the dense tiles while they are re-ordered by sub-cell
+
+    // ---- sub-step ----
+    // a sub-step's first pass, deferred to the cell list that follows it (cg_substep.h)
+    struct SubstepBegin *sub_begin = nullptr;
+    bool sub_pending = false;
+    long long *sub_counts = nullptr;     // where the pending pass leaves the populations (DEV)
+    cg_buf<unsigned> sub_partial;        // ... per workgroup first
+
+    // ---- errors ----
     // device word of sticky error bits set by kernels (CG_ERR_*), read by cg_error_flags
-    unsigned *err_flags = nullptr;
-    i64 device_bytes = 0;
+    cg_buf<unsigned> err_flags;
 };
 
-// kernels (cg_mesh_kernels.hip, cg_particles.hip)
+// ---- cg_mesh_kernels.hip: CIC deposit and gather, k-space kernel, slab helpers ----
 int cgk_deposit_cic(cg_ctx *c, const double *pos, i64 n, double contribution);
 int cgk_kspace(cg_ctx *c, int deconv_order, double C, int long_range, double E);
 int cgk_gather_kick(cg_ctx *c, const double *pos, double *mom, i64 n, int diff_order,
                     double factor);
+int cgk_cic_indices(cg_ctx *c, const double *pos, i64 n, int for_gather, i64 *idx);
+int cgk_transpose_fourier(cg_ctx *c, const double *src, double *dst);
+int cgk_emigrant_dest(cg_ctx *c, const double *pos, const double *mom, const i64 *idx,
+                      const unsigned *count, i64 cap, double dtm, int *dest, int *send_counts);
+int cgk_layers_write(cg_ctx *c, i64 layer0, i64 nlayers, const double *src, int add);
+int cgk_owner_rank(cg_ctx *c, const double *pos, i64 n, int *owner);
+
+// ---- cg_general.hip: the general particle_mesh() pieces ----
+int cgk_copy_modes_pack(cg_ctx *from, i64 n_small, const int *rows_local, i64 n_rows, double *out);
+int cgk_copy_modes_unpack(cg_ctx *onto, cg_ctx *from, i64 n_small, const int *rows_local,
+                          i64 n_rows, const double *in, int deconv_order, int nlattice,
+                          const double *shift, int op_add);
+int cgk_fluid_add(cg_ctx *c, const double *fluid, double factor, int op_add);
+int cgk_nullify_nyquist(cg_ctx *c);
+int cgk_fourier_operate(cg_ctx *onto, cg_ctx *from, int deconv_order, int nlattice,
+                        const double *shift, int diff_dim, int op_add);
+int cgk_copy_modes(cg_ctx *onto, cg_ctx *from, int deconv_order, int nlattice,
+                   const double *shift, int op_add);
+int cgk_deposit_general(cg_ctx *c, const double *pos, i64 n, double contribution, int order,
+                        const CicGeom &geo);
+int cgk_gather_scalar(cg_ctx *c, const double *pos, double *mom, i64 n, int dim, int order,
+                      const CicGeom &geo, double factor);
+int cgk_mesh_diff(cg_ctx *dst, cg_ctx *src, int dim, int diff_order);
+int cgk_fluid_kick(cg_ctx *c, double *J, const double *rho, const double *P, int dim,
+                   int diff_order, double minus_dt, double inv_c2);
+
+// ---- cg_fft.hip: the hand-written FFT ----
+bool cgk_fft_supported(i64 N);
+int cgk_fft_dist_forward(cg_ctx *c, double *send_buf, i64 layer0, i64 nlayers);
+int cgk_fft_dist_xsolve(cg_ctx *c, double *buf, int deconv_order, double C, int long_range,
+                        double E);
+int cgk_fft_dist_backward(cg_ctx *c, const double *recv_buf, i64 layer0, i64 nlayers);
+int cgk_fft_dist_x(cg_ctx *c, double *buf, int inverse);
+// what: 0 forward, 1 backward, 2 forward + Poisson kernel + backward (fused)
+int cgk_fft(cg_ctx *c, int what, int deconv_order, double C, int long_range, double E);
+
+// ---- cg_particles.hip: drift, tile sort, regions ----
+// out[i] = in[0] + ... + in[i-1] for i < n, on c->stream (temporary storage: c->scan_tmp)
+int cg_exclusive_sum(cg_ctx *c, const unsigned *in, unsigned *out, i64 n);
 int cgk_drift(cg_ctx *c, double *pos, const double *mom, i64 n, double dt_over_mass);
 int cgk_measure_mom(cg_ctx *c, const double *mom, i64 n, double *out, double *scratch);
 int cgk_measure_mom_regions(cg_ctx *c, const double *mom, const unsigned *start,
                             const unsigned *count, double *out, double *scratch);
-int cgk_cic_indices(cg_ctx *c, const double *pos, i64 n, int for_gather, i64 *idx);
-int cgk_transpose_fourier(cg_ctx *c, const double *src, double *dst);
 int cgk_sort(cg_ctx *c, const double *pos_in, const double *mom_in, const i64 *ids_in,
              double *pos_out, double *mom_out, i64 *ids_out, i64 n, unsigned *tile_offset_out,
              int drift, double dt_over_mass, int use_prepared);
 int cgk_permute_rows(cg_ctx *c, const i64 *perm, i64 n, int ncols, const void *const *src,
                      void *const *dst, const int *row_bytes);
+int cgk_owner_rank_drifted(cg_ctx *c, const double *pos, const double *mom, i64 n, double dtm,
+                           int *owner);
+int cgk_prepare_rebind(cg_ctx *c, const double *pos, const double *mom, i64 n_total,
+                       const double *add_pos, const double *add_mom, i64 n_add);
+int cgk_predict_regions(cg_ctx *c, const unsigned *start_in, const unsigned *count_in,
+                        unsigned *start_out);
+int cgk_emigrant_rows_dest(cg_ctx *c, const double *rows, const unsigned *count, i64 cap,
+                           int *dest, int *send_counts);
+int cgk_region_insert(cg_ctx *c, const double *rows, i64 m, const unsigned *start,
+                      unsigned *count, double *pos_out, double *mom_out, i64 *ids_out,
+                      i64 *aux_out, i64 capacity);
+
+// ---- cg_tiled_kernels.hip: the LDS-tiled deposit and the fused particle pass ----
+int cgk_deposit_cic_tiled(cg_ctx *c, const double *pos, i64 n, const unsigned *tile_offset,
+                          const unsigned *count, double contribution, int accumulate);
+// output side of the fused kick + drift + scatter (cg_gather_kick_drift_scatter)
+struct FusedScatter {
+    const unsigned *count_in;  // populations of the input regions (null: dense tile order)
+    const unsigned *start_out;
+    unsigned *count_out;
+    double *pos_out, *mom_out;
+    const i64 *ids_in;
+    i64 *ids_out;
+    const i64 *aux_in;
+    i64 *aux_out;
+    i64 out_capacity;
+};
+int cgk_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i64 n,
+                          const unsigned *tile_offset, int diff_order, double factor,
+                          int prepare, double next_dtm, const FusedScatter *fs = nullptr);
+// workgroup -> tile for the kernels that give a tile to a workgroup
+int cgk_tile_order(cg_ctx *c, const unsigned *start, const unsigned *count);
+
+// ---- cg_shortrange.hip: cell list and the cells sweep ----
 int cgk_shortrange_cells(cg_ctx *c, const double *pos, i64 n, i64 nt, double tile_extent,
                          unsigned *order, unsigned *offset, double *pos_sorted,
                          const signed char *rung, const signed char *rung_jumped,
@@ -234,6 +348,8 @@ int cgk_shortrange_sweep_cells(cg_ctx *c, const double *pos_r_sorted, const unsi
                                const signed char *rung_jumped, int lowest_active,
                                const unsigned *nact_r, const signed char *rj_sorted_r,
                                i64 n_active_max);
+
+// ---- cg_shortrange_dense.hip: tile lists and the dense tiles' sweep ----
 int cgk_shortrange_dense(cg_ctx *c, const double *pos_r_sorted, const unsigned *order_r,
                          const unsigned *off_r, double *dmom_r, const double *pos_s_sorted,
                          const unsigned *off_s, i64 nt, const double *table,
@@ -250,6 +366,8 @@ int cgk_shortrange_dense_look(cg_ctx *c, const unsigned *off_cells, i64 nt);
 int cgk_shortrange_tiles(cg_ctx *c, const double *pos, i64 n, i64 nt, double tile_extent,
                          const signed char *rung, int lowest_active, unsigned *order,
                          unsigned *offset, double *pos_sorted);
+
+// ---- cg_rungs.hip: rungs and the sub-step passes ----
 int cgk_dmom_active(cg_ctx *c, double *mom, double *dmom, const signed char *rung, i64 n,
                     int lowest_active, int op);
 int cgk_dmom_to_acc(cg_ctx *c, double *dmom, const signed char *rung,
@@ -277,67 +395,10 @@ int cgk_substep_end(cg_ctx *c, double *mom, double *dmom, signed char *rung,
                     signed char *rung_jumped, i64 n, int do_apply, int lowest_active,
                     const double *conversion_factors, int N_rungs, long long *counts);
 int cgk_rung_populations(cg_ctx *c, const signed char *rung, i64 n, int N_rungs, long long *counts);
-bool cgk_fft_supported(i64 N);
-int cgk_fft_dist_forward(cg_ctx *c, double *send_buf, i64 layer0, i64 nlayers);
-int cgk_fft_dist_xsolve(cg_ctx *c, double *buf, int deconv_order, double C, int long_range,
-                        double E);
-int cgk_fft_dist_backward(cg_ctx *c, const double *recv_buf, i64 layer0, i64 nlayers);
-int cgk_fft_dist_x(cg_ctx *c, double *buf, int inverse);
-int cgk_copy_modes_pack(cg_ctx *from, i64 n_small, const int *rows_local, i64 n_rows, double *out);
-int cgk_copy_modes_unpack(cg_ctx *onto, cg_ctx *from, i64 n_small, const int *rows_local,
-                          i64 n_rows, const double *in, int deconv_order, int nlattice,
-                          const double *shift, int op_add);
-int cgk_emigrant_dest(cg_ctx *c, const double *pos, const double *mom, const i64 *idx,
-                      const unsigned *count, i64 cap, double dtm, int *dest, int *send_counts);
-int cgk_layers_write(cg_ctx *c, i64 layer0, i64 nlayers, const double *src, int add);
-int cgk_owner_rank(cg_ctx *c, const double *pos, i64 n, int *owner);
-// what: 0 forward, 1 backward, 2 forward + Poisson kernel + backward (fused)
-int cgk_fluid_add(cg_ctx *c, const double *fluid, double factor, int op_add);
-int cgk_nullify_nyquist(cg_ctx *c);
-int cgk_fourier_operate(cg_ctx *onto, cg_ctx *from, int deconv_order, int nlattice,
-                        const double *shift, int diff_dim, int op_add);
-int cgk_copy_modes(cg_ctx *onto, cg_ctx *from, int deconv_order, int nlattice,
-                   const double *shift, int op_add);
-int cgk_deposit_general(cg_ctx *c, const double *pos, i64 n, double contribution, int order,
-                        const CicGeom &geo);
-int cgk_gather_scalar(cg_ctx *c, const double *pos, double *mom, i64 n, int dim, int order,
-                      const CicGeom &geo, double factor);
-int cgk_mesh_diff(cg_ctx *dst, cg_ctx *src, int dim, int diff_order);
+
+// ---- cg_pp.hip: direct summation ----
 int cgk_ewald_tabulate(cg_ctx *c, int gridsize, double *grid);
 int cgk_pp_kick(cg_ctx *c, const double *pos_r, i64 n_r, double *dmom_r, const double *pos_s,
                 i64 n_s, int same, const double *ewald_grid, int ewald_gridsize,
                 double softening, int kernel, double factor, const double *factors,
                 const signed char *rung, const signed char *rung_jumped, int lowest_active);
-int cgk_owner_rank_drifted(cg_ctx *c, const double *pos, const double *mom, i64 n, double dtm,
-                           int *owner);
-int cgk_prepare_rebind(cg_ctx *c, const double *pos, const double *mom, i64 n_total,
-                       const double *add_pos, const double *add_mom, i64 n_add);
-int cgk_fluid_kick(cg_ctx *c, double *J, const double *rho, const double *P, int dim,
-                   int diff_order, double minus_dt, double inv_c2);
-int cgk_fft(cg_ctx *c, int what, int deconv_order, double C, int long_range, double E);
-int cgk_deposit_cic_tiled(cg_ctx *c, const double *pos, i64 n, const unsigned *tile_offset,
-                          const unsigned *count, double contribution, int accumulate);
-// output side of the fused kick + drift + scatter (cg_gather_kick_drift_scatter)
-struct FusedScatter {
-    const unsigned *count_in;  // populations of the input regions (null: dense tile order)
-    const unsigned *start_out;
-    unsigned *count_out;
-    double *pos_out, *mom_out;
-    const i64 *ids_in;
-    i64 *ids_out;
-    const i64 *aux_in;
-    i64 *aux_out;
-    i64 out_capacity;
-};
-int cgk_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i64 n,
-                          const unsigned *tile_offset, int diff_order, double factor,
-                          int prepare, double next_dtm, const FusedScatter *fs = nullptr);
-// workgroup -> tile for the kernels that give a tile to a workgroup (cg_tiled_kernels.hip)
-int cgk_tile_order(cg_ctx *c, const unsigned *start, const unsigned *count);
-int cgk_predict_regions(cg_ctx *c, const unsigned *start_in, const unsigned *count_in,
-                        unsigned *start_out);
-int cgk_emigrant_rows_dest(cg_ctx *c, const double *rows, const unsigned *count, i64 cap,
-                           int *dest, int *send_counts);
-int cgk_region_insert(cg_ctx *c, const double *rows, i64 m, const unsigned *start,
-                      unsigned *count, double *pos_out, double *mom_out, i64 *ids_out,
-                      i64 *aux_out, i64 capacity);

@@ -6,16 +6,6 @@
 #include "cg_internal.h"
 #include "cg_kspace.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 // ---------------------------------------------------------------------------
 // CIC index + weights, set_weights_CIC (mesh.py:5319-5324) under the
 // coordinate map of mesh.py:1604-1606 / :430-432.

@@ -5,16 +5,6 @@
 #include "cg_internal.h"
 #include "cg_tiles.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 // ---------------------------------------------------------------------------
 // A11 drift: pos[r] = mod(pos[r] + mom[r]*dt_over_mass, boxsize) for all 3N
 // reals (species.py:2194-2196).  mod is the reference's pure-Python one
@@ -324,6 +314,15 @@ int cgk_prepare_rebind(cg_ctx *c, const double *pos, const double *mom, i64 n_to
     return 0;
 }
 
+// hipcub's two calls: the size of the temporary storage, then the scan
+int cg_exclusive_sum(cg_ctx *c, const unsigned *in, unsigned *out, i64 n) {
+    size_t need = 0;
+    CG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, (int)n, c->stream));
+    if (c->scan_tmp.reserve(c, need)) return 1;
+    CG_HIP(hipcub::DeviceScan::ExclusiveSum(c->scan_tmp, need, in, out, (int)n, c->stream));
+    return 0;
+}
+
 int cgk_sort(cg_ctx *c, const double *pos_in, const double *mom_in, const i64 *ids_in,
              double *pos_out, double *mom_out, i64 *ids_out, i64 n, unsigned *tile_offset_out,
              int drift, double dt_over_mass, int use_prepared) {
@@ -335,42 +334,21 @@ int cgk_sort(cg_ctx *c, const double *pos_in, const double *mom_in, const i64 *i
     // 4096 workgroups the scatter took 5.9 ms at 2^28 particles, uncapped 5.1 ms (the same
     // holds for a plain copy kernel, tools/copy_probe.cpp: 4.9 vs 5.6 TB/s).
     const i64 blocks = (n + 255) / 256;
+    const double dtm = drift ? dt_over_mass : 0.0;
     if (n > 0 && !use_prepared) {
-        if (drift)
-            hipLaunchKernelGGL(k_tile_histogram<true>, dim3((unsigned)blocks), dim3(256), 0,
-                               c->stream, pos_in, mom_in, n, dt_over_mass, c->p.boxsize,
-                               c->geom_deposit, c->p.nghosts, c->N, c->tiles, c->xmap.x0,
-                               c->tile_count);
-        else
-            hipLaunchKernelGGL(k_tile_histogram<false>, dim3((unsigned)blocks), dim3(256), 0,
-                               c->stream, pos_in, mom_in, n, 0.0, c->p.boxsize, c->geom_deposit,
-                               c->p.nghosts, c->N, c->tiles, c->xmap.x0, c->tile_count);
+        hipLaunchKernelGGL(drift ? k_tile_histogram<true> : k_tile_histogram<false>,
+                           dim3((unsigned)blocks), dim3(256), 0, c->stream, pos_in, mom_in, n, dtm,
+                           c->p.boxsize, c->geom_deposit, c->p.nghosts, c->N, c->tiles, c->xmap.x0,
+                           c->tile_count);
         CG_LAUNCH_CHECK();
     }
-    size_t need = 0;
-    CG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, c->tile_count, tile_offset_out,
-                                            (int)(nt + 1), c->stream));
-    if (need > c->scan_tmp_bytes) {
-        CG_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->scan_tmp);
-        c->scan_tmp = nullptr;
-        CG_HIP(hipMalloc(&c->scan_tmp, need));
-        c->scan_tmp_bytes = need;
-    }
-    CG_HIP(hipcub::DeviceScan::ExclusiveSum(c->scan_tmp, need, c->tile_count, tile_offset_out,
-                                            (int)(nt + 1), c->stream));
+    if (cg_exclusive_sum(c, c->tile_count, tile_offset_out, nt + 1)) return 1;
     if (n > 0) {
-        if (drift)
-            hipLaunchKernelGGL(k_tile_scatter<true>, dim3((unsigned)blocks), dim3(256), 0,
-                               c->stream, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n,
-                               dt_over_mass, c->p.boxsize, c->geom_deposit, c->p.nghosts, c->N,
-                               c->tiles, c->xmap.x0, tile_offset_out, c->tile_cursor,
-                               c->err_flags);
-        else
-            hipLaunchKernelGGL(k_tile_scatter<false>, dim3((unsigned)blocks), dim3(256), 0,
-                               c->stream, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n,
-                               0.0, c->p.boxsize, c->geom_deposit, c->p.nghosts, c->N, c->tiles,
-                               c->xmap.x0, tile_offset_out, c->tile_cursor, c->err_flags);
+        hipLaunchKernelGGL(drift ? k_tile_scatter<true> : k_tile_scatter<false>,
+                           dim3((unsigned)blocks), dim3(256), 0, c->stream, pos_in, mom_in, ids_in,
+                           pos_out, mom_out, ids_out, n, dtm, c->p.boxsize, c->geom_deposit,
+                           c->p.nghosts, c->N, c->tiles, c->xmap.x0, tile_offset_out,
+                           c->tile_cursor, c->err_flags);
         CG_LAUNCH_CHECK();
     }
     return 0;
@@ -396,19 +374,7 @@ int cgk_predict_regions(cg_ctx *c, const unsigned *start_in, const unsigned *cou
     hipLaunchKernelGGL(k_region_caps, dim3((unsigned)((nb + 256) / 256)), dim3(256), 0, c->stream,
                        start_in, count_in, nb, c->tile_cursor);
     CG_LAUNCH_CHECK();
-    size_t need = 0;
-    CG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, c->tile_cursor, start_out,
-                                            (int)(nb + 1), c->stream));
-    if (need > c->scan_tmp_bytes) {
-        CG_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->scan_tmp);
-        c->scan_tmp = nullptr;
-        CG_HIP(hipMalloc(&c->scan_tmp, need));
-        c->scan_tmp_bytes = need;
-    }
-    CG_HIP(hipcub::DeviceScan::ExclusiveSum(c->scan_tmp, need, c->tile_cursor, start_out,
-                                            (int)(nb + 1), c->stream));
-    return 0;
+    return cg_exclusive_sum(c, c->tile_cursor, start_out, nb + 1);
 }
 
 // ---------------------------------------------------------------------------

@@ -9,16 +9,6 @@
 // method of small particle numbers; suppliers are staged through LDS in chunks.
 #include "cg_internal.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 __global__ __launch_bounds__(64) void k_ewald_tabulate(double *__restrict__ grid, int gs) {
 #pragma clang fp contract(off)
     // ewald.py:245-271

@@ -20,16 +20,6 @@
 // (LDS and global integer atomics).  Compiled with -ffp-contract=off; FP64 throughout.
 #include "cg_internal.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 namespace {
 
 constexpr int kThreads = 256;

@@ -9,16 +9,6 @@
 #include "cg_internal.h"
 #include "cg_substep.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 typedef signed char i8;
 
 static inline unsigned nblocks(i64 n) { return (unsigned)((n + 255) / 256); }
@@ -232,14 +222,7 @@ int cgk_substep_populations(cg_ctx *c, i64 nwg, int N_rungs, long long *counts) 
 int cgk_substep_partial(cg_ctx *c, i64 n, i64 per, int N_rungs, i64 *nwg_out) {
     const i64 nwg = (n + per - 1) / per;
     const size_t need = sizeof(unsigned) * (size_t)N_rungs * (size_t)(nwg + 1);
-    if (need > c->sub_partial_bytes) {
-        CG_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->sub_partial);
-        c->sub_partial = nullptr;
-        c->sub_partial_bytes = 0;
-        CG_HIP(hipMalloc((void **)&c->sub_partial, need));
-        c->sub_partial_bytes = need;
-    }
+    if (c->sub_partial.reserve(c, need)) return 1;
     *nwg_out = nwg;
     return 0;
 }

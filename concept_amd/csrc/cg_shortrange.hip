@@ -18,23 +18,11 @@
 // (The tiles of 64 particles and more go to cg_shortrange_dense.hip; earlier forms of the
 // sweep — one wavefront per tile, a single-precision pre-test, a matrix-core range filter —
 // were measured slower and are gone: profiles/README.md keeps their numbers.)
-#include <hipcub/hipcub.hpp>
-
 #include <cstdlib>
 #include <type_traits>
 
 #include "cg_internal.h"
 #include "cg_substep.h"
-
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
 
 struct SrParams {
     double boxsize, r2_index_scaling, r2_max, factor;
@@ -303,15 +291,8 @@ int cgk_shortrange_cells(cg_ctx *c, const double *pos, i64 n, i64 nt, double til
     const bool begin = c->sub_pending && c->sub_begin->pos == pos && c->sub_begin->n == n && n > 0;
     if (!begin && cgk_substep_flush(c)) return 1;
     const size_t words = (size_t)(ncells + 4) + 2 * (size_t)(n + 1);  // counts | (cell, place)
-    if (4 * words > c->sr_tmp_bytes) {
-        CG_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->sr_tmp);
-        c->sr_tmp = nullptr;
-        c->sr_tmp_bytes = 0;
-        CG_HIP(hipMalloc(&c->sr_tmp, 4 * words));
-        c->sr_tmp_bytes = 4 * words;
-    }
-    unsigned *count = (unsigned *)c->sr_tmp;
+    if (c->sr_tmp.reserve(c, 4 * words)) return 1;
+    unsigned *count = c->sr_tmp;
     uint2 *cellrel = (uint2 *)(count + ((ncells + 2) & ~(i64)1));
     CG_HIP(hipMemsetAsync(count, 0, 4 * (size_t)(ncells + 1), c->stream));
     if (act) CG_HIP(hipMemsetAsync(nact, 0, 4 * (size_t)ncells, c->stream));
@@ -339,18 +320,7 @@ int cgk_shortrange_cells(cg_ctx *c, const double *pos, i64 n, i64 nt, double til
             CG_LAUNCH_CHECK();
         }
     }
-    size_t need = 0;
-    CG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, count, offset, (int)(ncells + 1),
-                                            c->stream));
-    if (need > c->scan_tmp_bytes) {
-        CG_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->scan_tmp);
-        c->scan_tmp = nullptr;
-        CG_HIP(hipMalloc(&c->scan_tmp, need));
-        c->scan_tmp_bytes = need;
-    }
-    CG_HIP(hipcub::DeviceScan::ExclusiveSum(c->scan_tmp, need, count, offset, (int)(ncells + 1),
-                                            c->stream));
+    if (cg_exclusive_sum(c, count, offset, ncells + 1)) return 1;
     if (n > 0) {
         hipLaunchKernelGGL(act ? k_sr_cell_place<true> : k_sr_cell_place<false>,
                            dim3((unsigned)((blocks + 7) / 8 * 8)), dim3(256), 0, c->stream, pos, n,
@@ -1197,9 +1167,8 @@ int cgk_shortrange_sparse(cg_ctx *c, const double *pos_r, const i64 *active, int
                factors,      rung_jumped /* non-null = rungs in use */, rung_jumped, 0, nullptr,
                nullptr,      0};
     if (!factors) P.rung = nullptr;
-    if (!c->sr_sparse_partial)
-        CG_HIP(hipMalloc((void **)&c->sr_sparse_partial,
-                         sizeof(double) * 3 * kSrSparseMax * kSrSparseBlocks));
+    if (c->sr_sparse_partial.reserve(c, sizeof(double) * 3 * kSrSparseMax * kSrSparseBlocks))
+        return 1;
     // (no suppliers: the final kernel alone, which adds nothing and still checks the slots)
     i64 nbl = (n_s + 255) / 256;
     const int nb = (int)(nbl < kSrSparseBlocks ? nbl : kSrSparseBlocks);
@@ -1506,13 +1475,7 @@ int cgk_shortrange_sweep_cells(cg_ctx *c, const double *pos_r_sorted, const unsi
     if (partial && !act) {
         // which tiles have a receiver on an active rung (the others leave at once)
         const size_t ntl = (size_t)nt * nt * nt;
-        if (c->sr_tile_active_cap < ntl) {
-            (void)hipFree(c->sr_tile_active);
-            c->sr_tile_active = nullptr;
-            c->sr_tile_active_cap = 0;
-            CG_HIP(hipMalloc((void **)&c->sr_tile_active, ntl));
-            c->sr_tile_active_cap = ntl;
-        }
+        if (c->sr_tile_active.reserve(c, ntl)) return 1;
         hipLaunchKernelGGL(k_sr_tile_activity, dim3((unsigned)((ntl + 255) / 256)), dim3(256), 0,
                            c->stream, order_r, off_r, rung, lowest_active, (int)nt,
                            c->sr_tile_active);
@@ -1544,14 +1507,7 @@ int cgk_shortrange_sweep_cells(cg_ctx *c, const double *pos_r_sorted, const unsi
         // few active receivers: one wavefront per cell that holds one
         const i64 ncells = 8 * nt * nt * nt;
         const size_t need = 4 * (2 * (size_t)n_active_max + 64);
-        if (need > c->sr_active_bytes) {
-            CG_HIP(hipStreamSynchronize(c->stream));
-            (void)hipFree(c->sr_active);
-            c->sr_active = nullptr;
-            c->sr_active_bytes = 0;
-            CG_HIP(hipMalloc((void **)&c->sr_active, need));
-            c->sr_active_bytes = need;
-        }
+        if (c->sr_active.reserve(c, need)) return 1;
         unsigned *count = c->sr_active, *list = c->sr_active + 64, *rows = list + n_active_max;
         CG_HIP(hipMemsetAsync(count, 0, 4, c->stream));
         // (a bound of 0 lists nobody, but an active receiver still raises the flag)

@@ -28,23 +28,11 @@
 // tests per pair in range in tiles of 256 particles and more, 3.2 at 128-256, 4.1 at 64-128
 // (the cells sweep: 4.1-4.7), worse below — so cg_shortrange_sweep_cells hands the tiles above a
 // population threshold to this kernel and keeps the others.
-#include <hipcub/hipcub.hpp>
-
 #include <cstdlib>
 #include <cstring>
 
 #include "cg_internal.h"
 #include "cg_tiles.h"
-
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
 
 namespace {
 
@@ -669,18 +657,6 @@ __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sr_sweep_dense(
     }
 }
 
-// grows a device buffer of the context (the stream is drained first: the old one may be in use)
-int srd_reserve(cg_ctx *c, void **buf, size_t *have, size_t need) {
-    if (need <= *have) return 0;
-    CG_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    CG_HIP(hipMalloc(buf, need));
-    *have = need;
-    return 0;
-}
-
 }  // namespace
 
 // CONCEPT_GPU_SR_DENSE_MIN: the population from which a tile is "dense" (64; 0 switches the
@@ -704,23 +680,18 @@ int cgk_shortrange_tiles_phase(cg_ctx *c, int phase, const double *pos, i64 n, i
     const i64 ntiles = nt * nt * nt;
     const i64 blocks = (n + 255) / 256;
     if (phase != 2) {
-        if (srd_reserve(c, &c->sr_tmp, &c->sr_tmp_bytes, (size_t)(8 * (ntiles + 1)))) return 1;
-        unsigned *count = (unsigned *)c->sr_tmp;
-        CG_HIP(hipMemsetAsync(c->sr_tmp, 0, 8 * (ntiles + 1), c->stream));
+        if (c->sr_tmp.reserve(c, (size_t)(8 * (ntiles + 1)))) return 1;
+        unsigned *count = c->sr_tmp;
+        CG_HIP(hipMemsetAsync(count, 0, 8 * (ntiles + 1), c->stream));
         if (n > 0) {
             hipLaunchKernelGGL(k_srd_histogram, dim3((unsigned)blocks), dim3(256), 0, c->stream,
                                pos, n, inv, (unsigned)nt, rung, lowest_active, count);
             CG_LAUNCH_CHECK();
         }
-        size_t need = 0;
-        CG_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, count, offset, (int)(ntiles + 1),
-                                                c->stream));
-        if (srd_reserve(c, &c->scan_tmp, &c->scan_tmp_bytes, need)) return 1;
-        CG_HIP(hipcub::DeviceScan::ExclusiveSum(c->scan_tmp, need, count, offset,
-                                                (int)(ntiles + 1), c->stream));
+        if (cg_exclusive_sum(c, count, offset, ntiles + 1)) return 1;
     }
     if (phase != 1 && n > 0) {
-        unsigned *cursor = (unsigned *)c->sr_tmp + (ntiles + 1);
+        unsigned *cursor = c->sr_tmp + (ntiles + 1);
         hipLaunchKernelGGL(k_srd_scatter, dim3((unsigned)blocks), dim3(256), 0, c->stream, pos, n,
                            inv, (unsigned)nt, rung, lowest_active, offset, cursor, order,
                            pos_sorted);
@@ -734,12 +705,10 @@ int cgk_shortrange_tiles_phase(cg_ctx *c, int phase, const double *pos, i64 n, i
             }
             const i64 cap_tiles = sub_rows / sub_min + 1;
             const size_t head = (size_t)((8 * (cap_tiles + 2) + 255) / 256 * 256);
-            if (srd_reserve(c, &c->sr_sub_tmp, &c->sr_sub_bytes,
-                            head + sizeof(SrdRow) * (size_t)sub_rows))
-                return 1;
-            unsigned *counters = (unsigned *)c->sr_sub_tmp, *tiles = counters + 2,
+            if (c->sr_sub_tmp.reserve(c, head + sizeof(SrdRow) * (size_t)sub_rows)) return 1;
+            unsigned *counters = (unsigned *)c->sr_sub_tmp.ptr, *tiles = counters + 2,
                      *seg = tiles + cap_tiles;
-            SrdRow *scratch = (SrdRow *)((char *)c->sr_sub_tmp + head);
+            SrdRow *scratch = (SrdRow *)((char *)c->sr_sub_tmp.ptr + head);
             CG_HIP(hipMemsetAsync(counters, 0, 8, c->stream));
             hipLaunchKernelGGL(k_srd_sub_tiles, dim3((unsigned)((ntiles + 255) / 256)), dim3(256),
                                0, c->stream, offset, (unsigned)ntiles, (unsigned)sub_min,
@@ -799,7 +768,7 @@ int cgk_shortrange_dense_look(cg_ctx *c, const unsigned *off_cells, i64 nt) {
     if (min_pop < 0 || nt < 4) return 0;
     const i64 ntiles = nt * nt * nt, ncells = 8 * ntiles;
     if (!c->srd_host) CG_HIP(hipHostMalloc((void **)&c->srd_host, 256));
-    if (srd_reserve(c, (void **)&c->srd_small, &c->srd_small_bytes, 256)) return 1;
+    if (c->srd_small.reserve(c, 256)) return 1;
     // (the slot's look, taken kdLooks looks ago, is counted before it is replaced)
     if (c->srd_looks >= kdLooks && srd_count_looks(c, c->srd_looks - kdLooks + 1)) return 1;
     const int slot = (int)(c->srd_looks % kdLooks);
@@ -807,7 +776,7 @@ int cgk_shortrange_dense_look(cg_ctx *c, const unsigned *off_cells, i64 nt) {
     cg_ctx::SrdLook &L = c->srd_look[slot];
     if (!L.ev) CG_HIP(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
     // device words 16 + 8 slot: [0] particles in dense tiles, [1] dense tiles, [4..5] sum pop^2
-    unsigned *dev = (unsigned *)c->srd_small + 16 + 8 * slot, *host = c->srd_host + 16 + 8 * slot;
+    unsigned *dev = c->srd_small + 16 + 8 * slot, *host = c->srd_host + 16 + 8 * slot;
     CG_HIP(hipMemsetAsync(dev, 0, 32, c->stream));
     hipLaunchKernelGGL(k_srd_precheck, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0,
                        c->stream, off_cells, (unsigned)nt, (unsigned)min_pop, dev);
@@ -871,13 +840,11 @@ int cgk_shortrange_dense(cg_ctx *c, const double *pos_r_sorted, const unsigned *
     memcpy(&sq, hr + 4, 8);
     // buffers nobody has used for a while go back (a run whose clumps dissolve, a test)
     if (ndense == 0) {
-        if (++c->srd_idle >= 16 && c->srd_buf_bytes + c->sr_sub_bytes > ((size_t)256 << 20)) {
+        if (++c->srd_idle >= 16 && c->srd_buf.bytes + c->sr_sub_tmp.bytes > ((size_t)256 << 20)) {
             CG_HIP(hipStreamSynchronize(c->stream));
             if (c->srd_stream) CG_HIP(hipStreamSynchronize(c->srd_stream));
-            (void)hipFree(c->srd_buf);
-            (void)hipFree(c->sr_sub_tmp);
-            c->srd_buf = c->sr_sub_tmp = nullptr;
-            c->srd_buf_bytes = c->sr_sub_bytes = 0;
+            c->srd_buf.release();
+            c->sr_sub_tmp.release();
         }
         return 0;
     }
@@ -905,7 +872,7 @@ int cgk_shortrange_dense(cg_ctx *c, const double *pos_r_sorted, const unsigned *
     c->srd_idle = 0;
     // [2] items, [6] active receivers in tiles dense with them, [7] such tiles, [8..9] sum of
     // active x pop
-    unsigned *dev = (unsigned *)c->srd_small;
+    unsigned *dev = c->srd_small;
     CG_HIP(hipMemsetAsync(dev, 0, 40, c->stream));
     // buffers: take | items | offsets r, s | order r, s | positions r, s
     const size_t a_take = 0, a_items = (size_t)((ntiles + 255) / 256 * 256),
@@ -916,8 +883,8 @@ int cgk_shortrange_dense(cg_ctx *c, const double *pos_r_sorted, const unsigned *
                  a_posr = a_ords + (same ? 0 : (size_t)((4 * n_s + 255) / 256 * 256)),
                  a_poss = a_posr + 24 * (size_t)n_r,
                  a_end = a_poss + (same ? 0 : 24 * (size_t)n_s);
-    if (srd_reserve(c, &c->srd_buf, &c->srd_buf_bytes, a_end)) return 1;
-    char *B = (char *)c->srd_buf;
+    if (c->srd_buf.reserve(c, a_end)) return 1;
+    char *B = (char *)c->srd_buf.ptr;
     unsigned char *take = (unsigned char *)(B + a_take);
     unsigned long long *items = (unsigned long long *)(B + a_items);
     unsigned *offr = (unsigned *)(B + a_offr), *offs = same ? offr : (unsigned *)(B + a_offs);
@@ -927,8 +894,8 @@ int cgk_shortrange_dense(cg_ctx *c, const double *pos_r_sorted, const unsigned *
     if (partial) {
         // the active receivers' offsets first (a histogram: 0.07 ms at 256^3): do the tiles that
         // are dense WITH THEM hold enough of this sub-step's pair work?
-        if (srd_reserve(c, &c->srd_rung, &c->srd_rung_bytes, (size_t)n_r)) return 1;
-        signed char *rung_sorted = (signed char *)c->srd_rung;
+        if (c->srd_rung.reserve(c, (size_t)n_r)) return 1;
+        signed char *rung_sorted = c->srd_rung;
         hipLaunchKernelGGL(k_srd_gather_rung, dim3((unsigned)((n_r + 255) / 256)), dim3(256), 0,
                            c->stream, order_r, rung, (unsigned)n_r, rung_sorted);
         CG_LAUNCH_CHECK();

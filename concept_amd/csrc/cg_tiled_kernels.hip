@@ -15,16 +15,6 @@
 #include "cg_internal.h"
 #include "cg_tiles.h"
 
-#define CG_LAUNCH_CHECK()                                                                     \
-    do {                                                                                      \
-        hipError_t e_ = hipGetLastError();                                                    \
-        if (e_ != hipSuccess) {                                                               \
-            cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
 // 32-bit cell arithmetic: x is positive and < gridsize + 2*nghosts + 1 (positions are in
 // [0, boxsize)), so the reference's truncation to Py_ssize_t equals truncation to int —
 // one v_cvt_i32_f64 instead of the ~15-instruction double -> int64 sequence, and every
@@ -239,8 +229,8 @@ int cgk_tile_order(cg_ctx *c, const unsigned *start, const unsigned *count) {
     // blocks on the XCDs it had)
     const unsigned cap = ((ntiles / 8u) + 7u) & ~7u;
     if (!c->tile_order_buf) {
-        CG_HIP(hipMalloc(&c->tile_order_buf,
-                         sizeof(unsigned) * (2 * (size_t)ntiles + cap + ncounters)));
+        if (c->tile_order_buf.reserve(c, sizeof(unsigned) * (2 * (size_t)ntiles + cap + ncounters)))
+            return 1;
         c->tile_order = c->tile_order_buf + ntiles;
         c->tile_order_cap = cap;
         // (pinned memory is a convenience: without it every launch takes the full number of
@@ -1020,14 +1010,7 @@ int cgk_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i64 n,
         if (c->emig_rows) CG_HIP(hipMemsetAsync(c->emig_rows_count, 0, 4, c->stream));
         if (c->mom2_sum_out) {
             const size_t need = sizeof(double) * (8 * ((size_t)c->ntiles + (c->ntiles / 8 + 8)) + 256);
-            if (need > c->mom2_partial_bytes) {
-                CG_HIP(hipStreamSynchronize(c->stream));
-                (void)hipFree(c->mom2_partial);
-                c->mom2_partial = nullptr;
-                c->mom2_partial_bytes = 0;
-                CG_HIP(hipMalloc((void **)&c->mom2_partial, need));
-                c->mom2_partial_bytes = need;
-            }
+            if (c->mom2_partial.reserve(c, need)) return 1;
             CG_HIP(hipMemsetAsync(c->mom2_partial, 0, need, c->stream));
             prep_args.mom2_out = c->mom2_partial;
         }
