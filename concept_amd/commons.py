@@ -289,6 +289,7 @@ def load_params(source=None, **overrides):
     p.cell_centered = bool(user.get('cell_centered', True))
     _load_powerspec_params(p, user, units)
     _load_render2D_params(p, user)
+    _load_fluid_params(p, user)
     # nghosts (commons.py:4411-4432): default 2 comes from the PCS default of the
     # power-spectrum and 2D render options; force interpolation and differentiation orders
     # raise it (powerspec_options default: PCS, interlaced -> 4//2 = 2, + 1 with cell-vertex
@@ -597,6 +598,63 @@ def _load_render2D_params(p, user):
         d[k] = v
     p.render2D_options = opts
     p.terminal_width = int(user.get('terminal_width', 80))
+
+
+ρ_vacuum = float(1e+2*machine_ϵ)  # commons.py:1818
+
+
+def _load_fluid_params(p, user):
+    """fluid_scheme_select and fluid_options (commons.py:3940-4030) with the reference's
+    defaults and key folding.  The Kurganov-Tadmor options are loaded as the reference loads
+    them; concept_amd.fluid refuses the scheme itself."""
+    fold = lambda s: str(s).lower().replace(' ', '').replace('-', '')
+    sel = {'all': 'MacCormack'}
+    if user.get('fluid_scheme_select'):
+        given = user['fluid_scheme_select']
+        sel = dict(given) if isinstance(given, dict) else {'all': given}
+    sel['default'] = 'MacCormack'
+    p.fluid_scheme_select = {key: fold(val) for key, val in sel.items()}
+    matter = ('baryon', 'cold dark matter', 'decaying cold dark matter', 'matter')
+    defaults = {
+        'maccormack': {
+            'vacuum_corrections_select': True,
+            'max_vacuum_corrections_select': (1, 'gridsize'),
+            'foresight_select': 25,
+            # matter fluids require a lot of smoothing
+            'smoothing_select': {'default': 1.0, **{s: 2.0 for s in matter}},
+        },
+        'kurganovtadmor': {
+            'rungekuttaorder': 2,
+            'flux_limiter_select': {'default': 'mc', **{s: 'minmod' for s in matter}},
+        },
+    }
+    opts = {fold(scheme): {fold(key): val for key, val in dict(d).items()}
+            for scheme, d in dict(user.get('fluid_options') or {}).items()}
+    for scheme, d in defaults.items():
+        opts.setdefault(scheme, {})
+        for key, val in d.items():
+            opts[scheme].setdefault(key, val)
+    for scheme, d in opts.items():
+        for key, val in list(d.items()):
+            d[key] = dict(val) if isinstance(val, dict) else {'all': val}
+    for scheme, d in defaults.items():
+        for key, val in d.items():
+            if not isinstance(val, dict):
+                opts[scheme][key]['default'] = val
+    opts['kurganovtadmor']['flux_limiter_select'] = {
+        key: fold(val) for key, val in opts['kurganovtadmor']['flux_limiter_select'].items()}
+    mc = opts['maccormack']
+    mc['vacuum_corrections_select'] = {
+        key: bool(val) for key, val in mc['vacuum_corrections_select'].items()}
+    for key, val in list(mc['max_vacuum_corrections_select'].items()):
+        val = list(val) if isinstance(val, (tuple, list, np.ndarray)) else [val]
+        val = [el.lower() if isinstance(el, str) else int(np.round(el)) for el in val]
+        if len(val) == 1:
+            val *= 2
+        mc['max_vacuum_corrections_select'][key] = val
+    mc['foresight_select'] = {key: int(np.round(val)) for key, val in mc['foresight_select'].items()}
+    mc['smoothing_select'] = {key: float(val) for key, val in mc['smoothing_select'].items()}
+    p.fluid_options = opts
 
 
 def is_selected(component, d, accumulate=False, default=None):

@@ -1,0 +1,398 @@
+// cg_fluid.hip — the flux terms of the MacCormack scheme for a fluid with non-linear ϱ and J
+// (boltzmann_order = 1, closure 'truncate'), its vacuum sweep and its v_max.
+//   k_mc_step         maccormack_step, all four variables in one pass     fluid.py:841-946
+//   k_mc_halve        scale_nonlinear_fluid_grids(0.5)                    fluid.py:788
+//   k_vacuum_detect   the detection compare and fac_time of correct_vacuum, and the compare of
+//                     check_vacuum                                        fluid.py:1241-1286, 1094-1097
+//   k_vacuum_gather   the pair terms of the 3x3x3 blocks, as a gather     fluid.py:1289-1319
+//   k_vacuum_apply    variable += Δ                                       fluid.py:1333-1340
+//   k_vmax            max (Jx² + Jy² + Jz²)/(ϱ + c⁻²𝒫)²                   analysis.py:3940-3955
+//
+// A fluid grid is this domain's layers of the global grid, double[nxl][g][g] without ghosts
+// (species.Component).  y and z are periodic by index wrap.  In x a kernel reads up to H layers
+// beyond the own ones: with lo = hi = NULL they are the own layers on the other side of the box
+// (one domain, nxl = g); else lo holds the H layers below the first own one and hi the H layers
+// above the last, each double[H][g][g] in ascending x (the caller exchanged them).
+//
+// FP64, compiled with -ffp-contract=off: every sum, product and quotient is evaluated as the
+// reference writes it.  No floating-point atomics: the results do not depend on the launch.
+#include "cg_internal.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kTY = 8, kTZ = 32;   // cells of a step tile along y and z (kTY*kTZ = kThreads)
+constexpr int kXC = 8;             // layers a workgroup of the step walks along x
+constexpr int kPartials = 1024;    // partial maxima of k_vmax
+
+// the layers of one grid as a kernel sees them
+struct Layers {
+    const double *own, *lo, *hi;
+};
+template <int n>
+struct LayersN {
+    Layers v[n];
+};
+struct Out4 {
+    double *p[4];
+};
+struct In4 {
+    const double *p[4];
+};
+
+// layer l in [-H, nxl + H) of a grid; g2 = g*g
+template <int H>
+__device__ inline const double *layer_of(const Layers &a, int l, int nxl, i64 g2) {
+    if (a.lo == nullptr) {
+        l = l < 0 ? l + nxl : (l >= nxl ? l - nxl : l);
+        return a.own + (i64)l * g2;
+    }
+    if (l < 0) return a.lo + (i64)(l + H) * g2;
+    if (l >= nxl) return a.hi + (i64)(l - nxl) * g2;
+    return a.own + (i64)l * g2;
+}
+
+__device__ inline int wrap(int a, int g) { return a < 0 ? a + g : (a >= g ? a - g : a); }
+
+// One MacCormack step.  src: ϱ, Jx, Jy, Jz as the stencil reads them (the unstarred grids in
+// step 0, the starred in step 1) and 𝒫 (always the unstarred grid); dst: the four grids the step
+// writes (the starred in step 0, the unstarred in step 1).  The prologue of fluid.py:862-870
+// touches only dst — dst = src in step 0, dst += src in step 1 — so it is the first term of the
+// cell's own sum.  A workgroup owns a tile of kTY x kTZ cells and walks kXC layers in the direction
+// of the x step: the layer it reads as the +s_x neighbour is the layer it updates next, kept in
+// the other half of the LDS buffer, and the +s_y and +s_z neighbours are the tile's own cells and
+// one halo row and column.  Every cell is loaded once per walk (plus the halo).
+__global__ __launch_bounds__(kThreads) void k_mc_step(LayersN<5> src, Out4 dst, int g, int nxl,
+                                                      int sx, int sy, int sz, double c,
+                                                      double inv_c2, int mc_step, int halve) {
+#pragma clang fp contract(off)
+    __shared__ double tile[2][5][kTY + 1][kTZ + 1];
+    const int tz = threadIdx.x % kTZ, ty = threadIdx.x / kTZ;
+    const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
+    const int xa = blockIdx.z * kXC, xb = xa + kXC < nxl ? xa + kXC : nxl;
+    const i64 g2 = (i64)g * g;
+    // the halo row sits on the side the step points to: local (ly, lz) is cell
+    // (y0 - oy + ly, z0 - oz + lz) of the layer, wrapped
+    const int oy = sy < 0, oz = sz < 0;
+    auto load = [&](int buf, int l) {
+        for (int e = threadIdx.x; e < (kTY + 1) * (kTZ + 1); e += kThreads) {
+            const int ly = e / (kTZ + 1), lz = e - ly * (kTZ + 1);
+            // (a partial tile's rows beyond the grid wrap as well: loaded, never used)
+            const int y = (y0 - oy + ly + g) % g, z = (z0 - oz + lz + g) % g;
+            const i64 at = (i64)y * g + z;
+#pragma unroll
+            for (int v = 0; v < 5; v++) tile[buf][v][ly][lz] = layer_of<1>(src.v[v], l, nxl, g2)[at];
+        }
+    };
+    const int count = xb - xa, first = sx > 0 ? xa : xb - 1;
+    const bool mine = y0 + ty < g && z0 + tz < g;
+    const int cy = ty + oy, cz = tz + oz;
+    load(0, first);
+    for (int n = 0; n < count; n++) {
+        const int l = first + n * sx, b = n & 1;
+        load(b ^ 1, l + sx);
+        __syncthreads();
+        if (mine) {
+            const i64 at = ((i64)l * g + (y0 + ty)) * g + (z0 + tz);
+            // the cell itself and its +s_x, +s_y, +s_z neighbours: J and ϱ + c⁻²𝒫
+            double J0[3], JN[3][3], den0, denN[3];
+#pragma unroll
+            for (int el = 0; el < 3; el++) {
+                J0[el] = tile[b][1 + el][cy][cz];
+                JN[0][el] = tile[b ^ 1][1 + el][cy][cz];
+                JN[1][el] = tile[b][1 + el][cy + sy][cz];
+                JN[2][el] = tile[b][1 + el][cy][cz + sz];
+            }
+            const double rho0 = tile[b][0][cy][cz];
+            den0 = rho0 + inv_c2 * tile[b][4][cy][cz];
+            denN[0] = tile[b ^ 1][0][cy][cz] + inv_c2 * tile[b ^ 1][4][cy][cz];
+            denN[1] = tile[b][0][cy + sy][cz] + inv_c2 * tile[b][4][cy + sy][cz];
+            denN[2] = tile[b][0][cy][cz + sz] + inv_c2 * tile[b][4][cy][cz + sz];
+            const double s[3] = {(double)sx, (double)sy, (double)sz};
+            // the continuity equation, fluid.py:883-894
+            double out = mc_step == 0 ? rho0 : dst.p[0][at] + rho0;
+#pragma unroll
+            for (int d = 0; d < 3; d++) out = out + (s[d] * (JN[d][d] - J0[d])) * c;
+            dst.p[0][at] = halve ? 0.5 * out : out;
+            // the Euler equation, fluid.py:915-939
+#pragma unroll
+            for (int el = 0; el < 3; el++) {
+                out = mc_step == 0 ? J0[el] : dst.p[1 + el][at] + J0[el];
+#pragma unroll
+                for (int d = 0; d < 3; d++)
+                    out = out + (s[d] * (JN[d][el] * JN[d][d] / denN[d] - J0[el] * J0[d] / den0)) * c;
+                dst.p[1 + el][at] = halve ? 0.5 * out : out;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_mc_halve(Out4 grids, i64 n) {
+    for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads) {
+#pragma unroll
+        for (int v = 0; v < 4; v++) grids.p[v][i] = grids.p[v][i] * 0.5;
+    }
+}
+
+// mode 0: a*k1 + b < threshold, fac_time = 0.5 (a - b)/(a - ρ_vacuum)   (first step: a = ϱ, b = ϱˣ)
+// mode 1: b < threshold, fac_time = 1                                   (second step: b = ϱ)
+// mode 2: a < threshold, nothing written but the flag                   (check_vacuum)
+__global__ __launch_bounds__(kThreads) void k_vacuum_detect(const double *__restrict__ a,
+                                                           const double *__restrict__ b, i64 n,
+                                                           int mode, double k1, double threshold,
+                                                           double rho_vacuum,
+                                                           double *__restrict__ fac_time,
+                                                           int *__restrict__ flag) {
+#pragma clang fp contract(off)
+    int any = 0;
+    for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads) {
+        double ft = 0;
+        bool imminent;
+        if (mode == 0) {
+            const double r = a[i], rs = b[i];
+            imminent = r * k1 + rs < threshold;
+            if (imminent) ft = 0.5 * (r - rs) / (r - rho_vacuum);
+        } else if (mode == 1) {
+            imminent = b[i] < threshold;
+            if (imminent) ft = 1;
+        } else {
+            imminent = a[i] < threshold;
+        }
+        any |= imminent;
+        if (mode != 2) fac_time[i] = ft;
+    }
+    if (__syncthreads_or(any) && threadIdx.x == 0) atomicOr(flag, 1);
+}
+
+// The sweep of fluid.py:1289-1319 seen from the cell p that receives: every vacuum centre c whose
+// 3x3x3 block holds p pairs p with the 26 other cells q of that block, and each pair moves
+// (v[q] - v[p]) fac_smoothing fac_time(c) / |q - p|² to p.  Centres and, within a centre, the
+// cells q are walked in ascending (x, y, z) offset, the order in which the reference's loops reach
+// the pairs of an interior cell.  var: the four variables with two layers beyond the own ones,
+// fac_time with one.
+__global__ __launch_bounds__(kThreads) void k_vacuum_gather(LayersN<4> var, Layers fac_time,
+                                                           Out4 delta, int g, int nxl,
+                                                           double fac_smoothing) {
+#pragma clang fp contract(off)
+    const i64 g2 = (i64)g * g, n = (i64)nxl * g2;
+    const i64 idx = (i64)blockIdx.x * kThreads + threadIdx.x;
+    if (idx >= n) return;
+    const int i = (int)(idx / g2), j = (int)((idx - (i64)i * g2) / g), k = (int)(idx % g);
+    double vp[4], sum[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int v = 0; v < 4; v++) vp[v] = var.v[v].own[idx];
+    for (int di = -1; di <= 1; di++)
+        for (int dj = -1; dj <= 1; dj++)
+            for (int dk = -1; dk <= 1; dk++) {
+                const double ft =
+                    layer_of<1>(fac_time, i + di, nxl, g2)[(i64)wrap(j + dj, g) * g + wrap(k + dk, g)];
+                if (ft == 0) continue;
+                const double f = fac_smoothing * ft;
+                for (int ei = di - 1; ei <= di + 1; ei++)
+                    for (int ej = dj - 1; ej <= dj + 1; ej++)
+                        for (int ek = dk - 1; ek <= dk + 1; ek++) {
+                            const int dist2 = ei * ei + ej * ej + ek * ek;
+                            if (dist2 == 0) continue;
+                            const double w = 1.0 / (double)dist2;
+                            const i64 at = (i64)wrap(j + ej, g) * g + wrap(k + ek, g);
+#pragma unroll
+                            for (int v = 0; v < 4; v++) {
+                                const double vq = layer_of<2>(var.v[v], i + ei, nxl, g2)[at];
+                                sum[v] = sum[v] + (vq - vp[v]) * f * w;
+                            }
+                        }
+            }
+#pragma unroll
+    for (int v = 0; v < 4; v++) delta.p[v][idx] = sum[v];
+}
+
+__global__ __launch_bounds__(kThreads) void k_vacuum_apply(Out4 var, In4 delta, i64 n) {
+    for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads) {
+#pragma unroll
+        for (int v = 0; v < 4; v++) var.p[v][i] = var.p[v][i] + delta.p[v][i];
+    }
+}
+
+// partial maxima per workgroup (final = 0), then one workgroup over the partials (final = 1);
+// the reference's compare (value > maximum, from 0) lets no NaN in
+__global__ __launch_bounds__(kThreads) void k_vmax(const double *__restrict__ rho,
+                                                  const double *__restrict__ P, In4 J, i64 n,
+                                                  double inv_c2, int final,
+                                                  double *__restrict__ out) {
+#pragma clang fp contract(off)
+    __shared__ double red[kThreads];
+    double best = 0;
+    if (!final) {
+        for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads) {
+            const double jx = J.p[0][i], jy = J.p[1][i], jz = J.p[2][i];
+            const double den = rho[i] + inv_c2 * P[i];
+            const double v = (jx * jx + jy * jy + jz * jz) / (den * den);
+            if (v > best) best = v;
+        }
+    } else {
+        for (i64 i = threadIdx.x; i < n; i += kThreads)
+            if (rho[i] > best) best = rho[i];
+    }
+    red[threadIdx.x] = best;
+    __syncthreads();
+    for (int m = kThreads / 2; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m && red[threadIdx.x + m] > red[threadIdx.x])
+            red[threadIdx.x] = red[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+}
+
+unsigned grid_for(i64 n, i64 cap) {
+    i64 blocks = (n + kThreads - 1) / kThreads;
+    if (blocks > cap) blocks = cap;
+    return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+// nvar grids with their layers beyond the own ones (both lists or neither)
+int take_layers(const char *who, Layers *out, int nvar, const void *const *own,
+                const void *const *lo, const void *const *hi) {
+    CG_CHECK(own, "%s: null argument", who);
+    CG_CHECK((lo == nullptr) == (hi == nullptr), "%s: give both lo and hi or neither", who);
+    for (int v = 0; v < nvar; v++) {
+        CG_CHECK(own[v] && (!lo || (lo[v] && hi[v])), "%s: null grid %d", who, v);
+        out[v] = Layers{(const double *)own[v], lo ? (const double *)lo[v] : nullptr,
+                        hi ? (const double *)hi[v] : nullptr};
+    }
+    return 0;
+}
+
+int check_shape(const char *who, int64_t gridsize, int64_t nxl, bool periodic, int H) {
+    CG_CHECK(gridsize >= 3 && gridsize <= 32768, "%s: grid size %lld", who, (long long)gridsize);
+    CG_CHECK(nxl >= H && nxl <= gridsize, "%s: %lld layers of a grid of size %lld (at least %d)",
+             who, (long long)nxl, (long long)gridsize, H);
+    CG_CHECK(!periodic || nxl == gridsize,
+             "%s: %lld of %lld layers and no layers of the neighbouring domains", who,
+             (long long)nxl, (long long)gridsize);
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cg_fluid_mc_step(cg_ctx *c, const void *const *src, const void *const *src_lo,
+                                const void *const *src_hi, void *const *dst, int64_t gridsize,
+                                int64_t nxl, const int *steps, double factor, double inv_c2,
+                                int mc_step, int halve) {
+    CG_CHECK(c && dst && steps, "cg_fluid_mc_step: null argument");
+    LayersN<5> s;
+    if (take_layers("cg_fluid_mc_step", s.v, 5, src, src_lo, src_hi)) return 1;
+    if (check_shape("cg_fluid_mc_step", gridsize, nxl, src_lo == nullptr, 1)) return 1;
+    CG_CHECK(mc_step == 0 || mc_step == 1, "cg_fluid_mc_step: mc_step %d", mc_step);
+    Out4 d;
+    for (int v = 0; v < 4; v++) {
+        CG_CHECK(dst[v], "cg_fluid_mc_step: null grid %d", v);
+        CG_CHECK(steps[v % 3] == 1 || steps[v % 3] == -1, "cg_fluid_mc_step: step %d", steps[v % 3]);
+        d.p[v] = (double *)dst[v];
+        // the stencil must not read what the pass writes
+        for (int u = 0; u < 5; u++)
+            CG_CHECK(dst[v] != src[u], "cg_fluid_mc_step: grid %d is read and written", v);
+    }
+    const dim3 grid((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
+                    (unsigned)((nxl + kXC - 1) / kXC));
+    hipLaunchKernelGGL(k_mc_step, grid, dim3(kThreads), 0, c->stream, s, d, (int)gridsize, (int)nxl,
+                       steps[0], steps[1], steps[2], factor, inv_c2, mc_step, halve);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_mc_finish(cg_ctx *c, void *const *grids, void *const *starred,
+                                  void *const *delta, int64_t n, int halve) {
+    CG_CHECK(c && grids && starred && n >= 1, "cg_fluid_mc_finish: null argument");
+    if (halve) {
+        Out4 gr;
+        for (int v = 0; v < 4; v++) {
+            CG_CHECK(grids[v], "cg_fluid_mc_finish: null grid %d", v);
+            gr.p[v] = (double *)grids[v];
+        }
+        hipLaunchKernelGGL(k_mc_halve, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, gr,
+                           (i64)n);
+        CG_LAUNCH_CHECK();
+    }
+    for (int v = 0; v < 4; v++) {
+        CG_CHECK(starred[v], "cg_fluid_mc_finish: null starred grid %d", v);
+        CG_HIP(hipMemsetAsync(starred[v], 0, sizeof(double) * n, c->stream));
+        if (delta && delta[v]) CG_HIP(hipMemsetAsync(delta[v], 0, sizeof(double) * n, c->stream));
+    }
+    return 0;
+}
+
+extern "C" int cg_fluid_vacuum_detect(cg_ctx *c, const double *a, const double *b, int64_t n,
+                                      int mode, double k1, double threshold, double rho_vacuum,
+                                      double *fac_time, int *flag) {
+    CG_CHECK(c && flag && n >= 1, "cg_fluid_vacuum_detect: null argument");
+    CG_CHECK(mode >= 0 && mode <= 2, "cg_fluid_vacuum_detect: mode %d", mode);
+    CG_CHECK((mode == 1 || a) && (mode == 2 || (b && fac_time)),
+             "cg_fluid_vacuum_detect: null grid for mode %d", mode);
+    CG_HIP(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
+    hipLaunchKernelGGL(k_vacuum_detect, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, a, b,
+                       (i64)n, mode, k1, threshold, rho_vacuum, fac_time, flag);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_vacuum_gather(cg_ctx *c, const void *const *var, const void *const *var_lo,
+                                      const void *const *var_hi, const double *fac_time,
+                                      const double *fac_time_lo, const double *fac_time_hi,
+                                      void *const *delta, int64_t gridsize, int64_t nxl,
+                                      double fac_smoothing) {
+    CG_CHECK(c && delta && fac_time, "cg_fluid_vacuum_gather: null argument");
+    LayersN<4> s;
+    if (take_layers("cg_fluid_vacuum_gather", s.v, 4, var, var_lo, var_hi)) return 1;
+    if (check_shape("cg_fluid_vacuum_gather", gridsize, nxl, var_lo == nullptr, 2)) return 1;
+    CG_CHECK((fac_time_lo == nullptr) == (var_lo == nullptr) &&
+                 (fac_time_hi == nullptr) == (var_lo == nullptr),
+             "cg_fluid_vacuum_gather: fac_time and the variables need the same neighbours");
+    Out4 d;
+    for (int v = 0; v < 4; v++) {
+        CG_CHECK(delta[v] && delta[v] != var[v], "cg_fluid_vacuum_gather: Δ buffer %d", v);
+        d.p[v] = (double *)delta[v];
+    }
+    const i64 n = nxl * gridsize * gridsize;
+    hipLaunchKernelGGL(k_vacuum_gather, dim3((unsigned)((n + kThreads - 1) / kThreads)),
+                       dim3(kThreads), 0, c->stream, s, Layers{fac_time, fac_time_lo, fac_time_hi},
+                       d, (int)gridsize, (int)nxl, fac_smoothing);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_vacuum_apply(cg_ctx *c, void *const *var, const void *const *delta,
+                                     int64_t n) {
+    CG_CHECK(c && var && delta && n >= 1, "cg_fluid_vacuum_apply: null argument");
+    Out4 o;
+    In4 d;
+    for (int v = 0; v < 4; v++) {
+        CG_CHECK(var[v] && delta[v], "cg_fluid_vacuum_apply: null grid %d", v);
+        o.p[v] = (double *)var[v];
+        d.p[v] = (const double *)delta[v];
+    }
+    hipLaunchKernelGGL(k_vacuum_apply, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, o, d,
+                       (i64)n);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_vmax(cg_ctx *c, const double *rho, const double *P, const void *const *J,
+                             int64_t n, double inv_c2, double *out) {
+    CG_CHECK(c && rho && P && J && out && n >= 1, "cg_fluid_vmax: null argument");
+    In4 j{};
+    for (int v = 0; v < 3; v++) {
+        CG_CHECK(J[v], "cg_fluid_vmax: null grid %d", v);
+        j.p[v] = (const double *)J[v];
+    }
+    if (c->fluid_partial.reserve(c, sizeof(double) * kPartials)) return 1;
+    const unsigned blocks = grid_for(n, kPartials);
+    hipLaunchKernelGGL(k_vmax, dim3(blocks), dim3(kThreads), 0, c->stream, rho, P, j, (i64)n, inv_c2,
+                       0, (double *)c->fluid_partial);
+    CG_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_vmax, dim3(1), dim3(kThreads), 0, c->stream,
+                       (const double *)c->fluid_partial, (const double *)nullptr, In4{},
+                       (i64)blocks, 0.0, 1, out);
+    CG_LAUNCH_CHECK();
+    return 0;
+}

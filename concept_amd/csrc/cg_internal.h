@@ -240,6 +240,9 @@ struct cg_ctx {
     long long *sub_counts = nullptr;     // where the pending pass leaves the populations (DEV)
     cg_buf<unsigned> sub_partial;        // ... per workgroup first
 
+    // ---- fluid solver ----
+    cg_buf<double> fluid_partial;        // cg_fluid_vmax: per-workgroup partial maxima
+
     // ---- errors ----
     // device word of sticky error bits set by kernels (CG_ERR_*), read by cg_error_flags
     cg_buf<unsigned> err_flags;

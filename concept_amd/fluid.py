@@ -1,0 +1,267 @@
+"""concept_amd.fluid — the flux terms of the MacCormack scheme for fluid components
+(fluid.py:724-961, 1079-1363 of the reference) on the GPU (csrc/cg_fluid.hip).
+
+In scope: a fluid with non-linear ϱ and J (boltzmann_order = 1, closure 'truncate') and
+w_eff = 0: the two MacCormack steps with their vacuum check and correction, the eight-fold cycle
+of step directions, v_max and the Courant limit.  Out of scope (drift() raises): the internal
+sources (pressure gradient, Hubble term, ς: maccormack_internal_sources), Kurganov-Tadmor, and
+linear variables realised by CLASS.
+
+Use is explicit — nothing calls this module on its own:
+
+    stepper.Timeloop(comps, fluid_drift=fluid.drift, fluid_limiter=fluid.courant_limit)
+
+The starred grids of a component, its fac_time grid and the device flag are allocated on its
+first maccormack(), the Δ buffers on its first vacuum sweep.  On several x-slab domains
+(comm.init) the step exchanges one neighbour layer of the five grids it reads, the sweep two
+layers of the variables and one of fac_time (Comm.sendrecv), and the flag is reduced with
+Comm.any; the kernels read those layers where one domain wraps around, so the result does not
+depend on the number of domains, bit for bit.
+"""
+import ctypes
+import itertools
+import math
+import types
+import warnings
+
+import torch
+
+from .commons import is_selected, machine_ϵ, ρ_vacuum
+from .lib import ConceptGPUError, check, raw
+
+_L = raw()
+
+# The 8 triples of step/flux directions of the first MacCormack step (fluid.py:796-804): module
+# state shared by all components, advanced once per maccormack() call.
+STEP_TRIPLES = tuple(tuple(sign*s for s in triple) for sign in (+1, -1)
+                     for triple in ((+1, +1, +1), (-1, +1, -1), (-1, -1, +1), (+1, -1, -1)))
+_steps = itertools.cycle(STEP_TRIPLES)
+
+
+def reset_steps():
+    """Rewind the cycle of step triples to its first entry (tests)."""
+    global _steps
+    _steps = itertools.cycle(STEP_TRIPLES)
+
+
+def _ptrs(tensors):
+    return (ctypes.c_void_p*len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _state(component):
+    """the solver's buffers of a component, made at its first maccormack()"""
+    st = component.__dict__.get('_maccormack_state')
+    if st is None:
+        z = lambda: torch.zeros_like(component.ϱ)
+        st = types.SimpleNamespace(starred=[z(), z(), z(), z()], Δ=None, fac_time=z(),
+                                   flag=torch.zeros(1, dtype=torch.int32, device=component.device))
+        component._maccormack_state = st
+    return st
+
+
+def _ctx(component):
+    # (the kernels use a context for its stream, launch checks and scratch memory only)
+    return component._mesh()._ctx
+
+
+def _grids(component):
+    return [component.ϱ] + list(component.J)
+
+
+def _neighbour_layers(component, tensors, H):
+    """(lo, hi): the H layers below and above this domain's own of every tensor, stacked, from
+    the neighbouring domains; (None, None) on one domain, where the kernels wrap around"""
+    if component.nprocs == 1:
+        return None, None
+    if component.nxl < H:
+        raise ConceptGPUError(f'{component.name}: {component.nxl} layers per domain, the fluid '
+                              f'solver needs at least {H}')
+    comm = component.comm
+    up = torch.stack([t[-H:] for t in tensors]).contiguous()   # -> lo of the next domain
+    down = torch.stack([t[:H] for t in tensors]).contiguous()  # -> hi of the previous domain
+    lo, hi = torch.empty_like(up), torch.empty_like(down)
+    comm.sendrecv(up, comm.next, lo, comm.prev)
+    comm.sendrecv(down, comm.prev, hi, comm.next)
+    return lo, hi
+
+
+def _check_scope(component, a):
+    if component.representation != 'fluid':
+        raise ConceptGPUError(f'{component.name}: the fluid solver was given a particle component')
+    if component.boltzmann_order > 1:
+        raise ConceptGPUError(
+            f'{component.name}: boltzmann_order = {component.boltzmann_order}: the non-linear '
+            'evolution of ς and 𝒫 (maccormack_internal_sources) is not implemented')
+    w_eff = component.w_eff(a=a)
+    if w_eff != 0:
+        raise ConceptGPUError(
+            f'{component.name}: w_eff = {w_eff}: the internal sources of a fluid with pressure '
+            '(pressure gradient, Hubble term: maccormack_internal_sources) are not implemented')
+
+
+def maccormack_step(component, ᔑdt, steps, mc_step, halve=False):
+    """maccormack_step (fluid.py:841-946) and its ghost exchange (:951-960): the starred grids
+    from the unstarred ones (mc_step 0) or the unstarred ones from the starred (mc_step 1)."""
+    st = _state(component)
+    p = component.params
+    src, dst = (_grids(component), st.starred) if mc_step == 0 else (st.starred, _grids(component))
+    src = src + [component.𝒫]
+    Δx = p.boxsize/component.gridsize
+    factor = -ᔑdt['a**(3*w_eff-2)', component.name]/Δx
+    lo, hi = _neighbour_layers(component, src, 1)
+    check(_L.cg_fluid_mc_step(
+        _ctx(component), _ptrs(src), _ptrs(list(lo)) if lo is not None else None,
+        _ptrs(list(hi)) if hi is not None else None, _ptrs(dst), component.gridsize,
+        component.nxl, (ctypes.c_int*3)(*[int(s) for s in steps]), float(factor),
+        float(p.light_speed**(-2)), int(mc_step), int(bool(halve))))
+
+
+def _any(component, st):
+    flag = bool(st.flag.item())
+    if component.nprocs > 1:
+        flag = component.comm.any(flag)
+    return flag
+
+
+def correct_vacuum(component, mc_step, record=None):
+    """correct_vacuum (fluid.py:1157-1343): True if vacuum was imminent anywhere and one sweep of
+    corrections was applied.  record: a list that receives (mc_step, fac_time of this domain's
+    cells as a host array) for every sweep."""
+    st = _state(component)
+    mc = component.params.fluid_options['maccormack']
+    foresight = is_selected(component, mc['foresight_select'])
+    fac_smoothing = 1./(6 + 12./2. + 8./3.)*is_selected(component, mc['smoothing_select'])
+    ctx = _ctx(component)
+    n = component.ϱ.numel()
+    # in the second step the starred and the unstarred variables swap roles (fluid.py:1229-1237)
+    if mc_step == 0:
+        a, b, var = component.ϱ, st.starred[0], _grids(component)
+        k1, threshold = 2/foresight - 1, 2/foresight*ρ_vacuum
+    else:
+        a, b, var = st.starred[0], component.ϱ, st.starred
+        k1, threshold = 0.0, 2*ρ_vacuum
+    check(_L.cg_fluid_vacuum_detect(ctx, _ptr(a), _ptr(b), n, int(mc_step), float(k1),
+                                    float(threshold), float(ρ_vacuum), _ptr(st.fac_time),
+                                    _ptr(st.flag)))
+    if not _any(component, st):
+        return False
+    if record is not None:
+        record.append((mc_step, st.fac_time.cpu().numpy().copy()))
+    if st.Δ is None:
+        st.Δ = [torch.zeros_like(component.ϱ) for _ in range(4)]
+    lo, hi = _neighbour_layers(component, var, 2)
+    ft_lo, ft_hi = _neighbour_layers(component, [st.fac_time], 1)
+    check(_L.cg_fluid_vacuum_gather(
+        ctx, _ptrs(var), _ptrs(list(lo)) if lo is not None else None,
+        _ptrs(list(hi)) if hi is not None else None, _ptr(st.fac_time),
+        _ptr(ft_lo[0]) if ft_lo is not None else None,
+        _ptr(ft_hi[0]) if ft_hi is not None else None, _ptrs(st.Δ), component.gridsize,
+        component.nxl, float(fac_smoothing)))
+    check(_L.cg_fluid_vacuum_apply(ctx, _ptrs(var), _ptrs(st.Δ), n))
+    return True
+
+
+def check_vacuum(component, mc_step):
+    """check_vacuum (fluid.py:1079-1101): warn about densities below ρ_vacuum, correct nothing"""
+    st = _state(component)
+    ϱ = component.ϱ if mc_step == 0 else st.starred[0]
+    check(_L.cg_fluid_vacuum_detect(_ctx(component), _ptr(ϱ), None, ϱ.numel(), 2, 0.0,
+                                    float(ρ_vacuum), float(ρ_vacuum), None, _ptr(st.flag)))
+    if _any(component, st):
+        warnings.warn(f'Vacuum detected in {component.name}')
+
+
+def finish(component, halve=True):
+    """the epilogue of maccormack (fluid.py:784-792): both steps together leave double the
+    values of all variables, and the starred and Δ buffers are left with no junk"""
+    st = _state(component)
+    check(_L.cg_fluid_mc_finish(_ctx(component), _ptrs(_grids(component)), _ptrs(st.starred),
+                                _ptrs(st.Δ) if st.Δ is not None else None,
+                                component.ϱ.numel(), int(bool(halve))))
+
+
+def maccormack(component, ᔑdt, a_next=-1, record=None):
+    """maccormack (fluid.py:724-792).  component.maccormack_attempts holds the number of
+    attempts of the two steps of the last call, component.maccormack_sweeps the vacuum sweeps."""
+    if component.boltzmann_order == 0:
+        return   # no J variable: nothing to do (fluid.py:727-730)
+    _check_scope(component, a_next if a_next != -1 else 1.0)
+    mc = component.params.fluid_options['maccormack']
+    max_vacuum_corrections = [component.gridsize if v == 'gridsize' else v for v in
+                              is_selected(component, mc['max_vacuum_corrections_select'])]
+    correct = is_selected(component, mc['vacuum_corrections_select'])
+    steps = list(next(_steps))
+    attempts, sweeps = [0, 0], [0, 0]
+    halved = False
+    for mc_step in range(2):
+        for attempt in range(max_vacuum_corrections[mc_step]):
+            attempts[mc_step] += 1
+            # the first step is re-evolved at each attempt, the second evolved once and then
+            # corrected repeatedly
+            if attempt == 0 or mc_step == 0:
+                # a second step that no sweep can follow leaves the halved values at once
+                halved = mc_step == 1 and not correct
+                maccormack_step(component, ᔑdt, steps, mc_step, halve=halved)
+            if correct:
+                if not correct_vacuum(component, mc_step, record):
+                    break
+                sweeps[mc_step] += 1
+            else:
+                check_vacuum(component, mc_step)
+                break
+        else:
+            if mc_step == 1:
+                component.maccormack_attempts, component.maccormack_sweeps = attempts, sweeps
+                raise ConceptGPUError(
+                    f'Giving up after {max_vacuum_corrections[mc_step]} failed attempts '
+                    f'to remove negative densities in {component.name}')
+        steps = [-s for s in steps]
+    component.maccormack_attempts, component.maccormack_sweeps = attempts, sweeps
+    finish(component, halve=not halved)
+
+
+def drift(component, ᔑdt, a_end=-1):
+    """Component.drift for fluids (species.py:2200-2216); the `fluid_drift` hook of
+    stepper.Timeloop."""
+    if component.representation != 'fluid':
+        raise ConceptGPUError(f'{component.name}: fluid.drift() is for fluid components')
+    scheme = is_selected(component, component.params.fluid_scheme_select)
+    if scheme != 'maccormack':
+        raise ConceptGPUError(
+            f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
+            'Kurganov-Tadmor is outside this path)')
+    maccormack(component, ᔑdt, a_end)
+
+
+def v_max(component, a):
+    """measure(component, 'v_max') for a fluid with non-linear J (analysis.py:3940-3963; the
+    sound speed light_speed*sqrt(w)/a is 0 for the w = 0 this module accepts)."""
+    _check_scope(component, a)
+    if component.boltzmann_order == 0:
+        return 0.0
+    p = component.params
+    out = torch.zeros(1, dtype=torch.float64, device=component.device)
+    check(_L.cg_fluid_vmax(_ctx(component), _ptr(component.ϱ), _ptr(component.𝒫),
+                           _ptrs(list(component.J)), component.ϱ.numel(),
+                           float(p.light_speed**(-2)), _ptr(out)))
+    J_over_ϱ_plus_𝒫_2_max = float(out.item())
+    if component.nprocs > 1:
+        J_over_ϱ_plus_𝒫_2_max = float(
+            component.comm.all_gather_floats([J_over_ϱ_plus_𝒫_2_max]).max())
+    w_eff = component.w_eff(a=a)
+    return a**(3*w_eff - 2)*math.sqrt(J_over_ϱ_plus_𝒫_2_max)
+
+
+def courant_limit(component, a):
+    """The Courant condition on the base step (main.py:803-823, fac_courant of main.py:2413);
+    the `fluid_limiter` hook of stepper.Timeloop."""
+    p = component.params
+    fac_courant = 0.21*p.Δt_base_nonlinear_factor
+    v = v_max(component, a)
+    if v == 0:
+        v = machine_ϵ   # a completely static component counts as just above 0
+    return fac_courant*(p.boxsize/component.gridsize)/v

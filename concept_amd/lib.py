@@ -148,6 +148,12 @@ SYMBOLS = {
     'cg_render2d_minmax': (_int, [_vp, _vp, _i64, _dbl, _vp, _vp]),
     'cg_render2d_histogram': (_int, [_vp, _vp, _i64, _dbl, _vp, ctypes.c_int32, _vp]),
     'cg_render2d_apply': (_int, [_vp, _vp, _i64, _dbl, _dbl, _dbl, _dbl, _dbl, _dbl]),
+    'cg_fluid_mc_step': (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _dbl, _dbl, _int, _int]),
+    'cg_fluid_mc_finish': (_int, [_vp, _vp, _vp, _vp, _i64, _int]),
+    'cg_fluid_vacuum_detect': (_int, [_vp, _vp, _vp, _i64, _int, _dbl, _dbl, _dbl, _vp, _vp]),
+    'cg_fluid_vacuum_gather': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl]),
+    'cg_fluid_vacuum_apply': (_int, [_vp, _vp, _vp, _i64]),
+    'cg_fluid_vmax': (_int, [_vp, _vp, _vp, _vp, _i64, _dbl, _vp]),
 }
 
 if not os.path.exists(LIB_PATH):

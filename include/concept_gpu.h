@@ -727,6 +727,54 @@ int cg_render2d_histogram(cg_ctx *ctx, const double *image /*DEV n*/, int64_t n,
 int cg_render2d_apply(cg_ctx *ctx, double *image /*DEV n*/, int64_t n, double exponent,
                       double vmin, double vmax, double shift, double scale, double fill);
 
+/* --- fluid solver: the MacCormack flux terms (fluid.py:724-961, 1157-1363) -----------
+ * A fluid grid is this domain's layers double[nxl][gridsize][gridsize] (no ghosts).  Lists of
+ * grids are HOST arrays of DEV pointers.  y and z are periodic by index wrap; in x a kernel
+ * reads H layers beyond the own ones: with the lo and hi lists NULL these are the own layers
+ * across the box (one domain, nxl = gridsize), else lo[v] / hi[v] hold the H layers below /
+ * above the own ones of grid v, double[H][gridsize][gridsize] in ascending x.
+ * cg_fluid_mc_step: maccormack_step (fluid.py:841-946) for ϱ, Jx, Jy, Jz in one pass, the
+ *   prologue of fluid.py:862-870 included.  src[0..3]: the four grids the stencil reads (the
+ *   unstarred in step 0, the starred in step 1), src[4]: 𝒫 (always unstarred); H = 1.
+ *   dst[0..3]: the grids written (mc_step 0: dst = src + flux terms; 1: dst += src + flux
+ *   terms).  steps: HOST int[3] of +-1; factor: -ᔑdt['a**(3*w_eff-2)']/Δx; inv_c2:
+ *   light_speed**-2.  halve: the written values are scaled by 0.5 (fluid.py:788, for a step 1
+ *   that no vacuum sweep follows).
+ * cg_fluid_mc_finish: the epilogue of maccormack (fluid.py:788-792): grids[0..3] *= 0.5 when
+ *   halve, starred[0..3] = 0, delta[v] = 0 where given (delta or an entry may be NULL).
+ * cg_fluid_vacuum_detect: the compare of correct_vacuum (fluid.py:1265-1286) over n cells.
+ *   mode 0: a*k1 + b < threshold with fac_time = 0.5 (a - b)/(a - rho_vacuum) (first step: a =
+ *   ϱ, b = ϱˣ, k1 = 2/foresight - 1, threshold = 2/foresight*ρ_vacuum); mode 1: b < threshold
+ *   with fac_time = 1 (second step: b = ϱ, threshold = 2 ρ_vacuum); fac_time[i] = 0 where the
+ *   compare fails.  mode 2: a < threshold, fac_time untouched (check_vacuum, fluid.py:1094-1097).
+ *   flag (DEV int): 1 if any cell met the compare, else 0.
+ * cg_fluid_vacuum_gather: the pair terms of fluid.py:1289-1319 summed per receiving cell into
+ *   delta[0..3] (overwritten): var[0..3] with H = 2, fac_time with H = 1.  No atomics: the same
+ *   input gives the same bits on any number of domains.
+ * cg_fluid_vacuum_apply: var[v] += delta[v] (fluid.py:1333-1340).
+ * cg_fluid_vmax: out[0] (DEV) = max over n cells of (Jx² + Jy² + Jz²)/(ϱ + inv_c2 𝒫)²
+ *   (analysis.py:3940-3955; 0 for an all-static fluid). */
+int cg_fluid_mc_step(cg_ctx *ctx, const void *const *src /*HOST 5*/,
+                     const void *const *src_lo /*HOST 5 or NULL*/,
+                     const void *const *src_hi /*HOST 5 or NULL*/, void *const *dst /*HOST 4*/,
+                     int64_t gridsize, int64_t nxl, const int *steps /*HOST 3*/, double factor,
+                     double inv_c2, int mc_step, int halve);
+int cg_fluid_mc_finish(cg_ctx *ctx, void *const *grids /*HOST 4*/, void *const *starred /*HOST 4*/,
+                       void *const *delta /*HOST 4 or NULL*/, int64_t n, int halve);
+int cg_fluid_vacuum_detect(cg_ctx *ctx, const double *a /*DEV n*/, const double *b /*DEV n*/,
+                           int64_t n, int mode, double k1, double threshold, double rho_vacuum,
+                           double *fac_time /*DEV n*/, int *flag /*DEV 1*/);
+int cg_fluid_vacuum_gather(cg_ctx *ctx, const void *const *var /*HOST 4*/,
+                           const void *const *var_lo /*HOST 4 or NULL*/,
+                           const void *const *var_hi /*HOST 4 or NULL*/,
+                           const double *fac_time /*DEV*/, const double *fac_time_lo,
+                           const double *fac_time_hi, void *const *delta /*HOST 4*/,
+                           int64_t gridsize, int64_t nxl, double fac_smoothing);
+int cg_fluid_vacuum_apply(cg_ctx *ctx, void *const *var /*HOST 4*/,
+                          const void *const *delta /*HOST 4*/, int64_t n);
+int cg_fluid_vmax(cg_ctx *ctx, const double *rho /*DEV n*/, const double *P /*DEV n*/,
+                  const void *const *J /*HOST 3*/, int64_t n, double inv_c2, double *out /*DEV 1*/);
+
 /* --- debug fetch (parity tests) -------------------------------------------- */
 int cg_fetch(cg_ctx *ctx, int which, double *out /*HOST*/, int64_t n_doubles);
 /* CIC cell indices exactly as set_weights_CIC returns them for the deposit

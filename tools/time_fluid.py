@@ -1,0 +1,94 @@
+"""Time concept_amd.fluid.maccormack with hipEvents: ten calls at grid size 512 (default) on a
+smooth fluid, and ten on the same fluid with one void that makes the first step of every call
+sweep.  Prints one JSON line (and writes it to --out): the time per call, and the HBM time of
+the bytes the passes of a call move at 8 TB/s.
+
+    python tools/time_fluid.py [--gridsize 512] [--calls 10] [--out profiles/fluid_drift_512.json]
+
+Bytes per cell and call, FP64: a step reads five grids and writes four (72 B;
+the second step also reads the four it adds to: 104 B); detection reads two grids and writes
+fac_time after the first step (24 B), one grid after the second (16 B); the epilogue halves four grids in place (64 B) and clears the four
+starred ones (32 B).  A sweep adds the gather (fac_time and the four variables in, four Δ out:
+72 B, its neighbour reads served by the caches) and the apply (96 B)."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+HBM_PEAK = 8e12   # bytes/s
+BYTES_SMOOTH = 72 + 24 + 104 + 16 + 64 + 32   # per cell and call
+BYTES_SWEEP = 72 + 96                      # per cell and sweep
+
+
+def fields(gs, void, device):
+    q = (torch.arange(gs, dtype=torch.float64, device=device) + 0.5)*(2*np.pi/gs)
+    x, y, z = q[:, None, None], q[None, :, None], q[None, None, :]
+    ϱ = 1 + 0.3*torch.sin(x)*torch.cos(y + 0.4) + 0.1*torch.sin(2*z + x)
+    u = [0.35*torch.sin(y + 0.3) + 0.2*torch.cos(z) + 0*x, -0.3*torch.cos(x + z) + 0.1 + 0*y,
+         0.25*torch.sin(x - y) - 0.15 + 0*z]
+    J = [ϱ*u_d for u_d in u]
+    if void:
+        h = gs//2
+        ϱ[h:h + 2, h:h + 2, h:h + 2] = 0.3
+        for d in range(3):
+            J[d][h:h + 2, h:h + 2, h:h + 2] = 0
+    return ϱ.contiguous(), [j.contiguous() for j in J]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--gridsize', type=int, default=512)
+    ap.add_argument('--calls', type=int, default=10)
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    from concept_amd import commons, fluid
+    from concept_amd.species import Component
+    gs = args.gridsize
+    commons.load_params({'boxsize': float(gs)})
+    device = torch.device('cuda', torch.cuda.current_device())
+    result = {'gridsize': gs, 'calls': args.calls, 'device': torch.cuda.get_device_name(device),
+              'hbm_peak_TBps': HBM_PEAK/1e12}
+    for void in (False, True):
+        c = Component('fluid', 'matter', gridsize=gs, boltzmann_order=1)
+        ϱ, J = fields(gs, void, device)
+        c.ϱ.copy_(ϱ)
+        for d in range(3):
+            c.J[d].copy_(J[d])
+        del ϱ, J
+        # a Courant number of about 0.05 on a grid spacing of 1
+        ᔑdt = {'1': 0.1, ('a**(3*w_eff-2)', c.name): 0.1}
+        fluid.reset_steps()
+        fluid.maccormack(c, ᔑdt)   # warm-up: buffers, first launches
+        torch.cuda.synchronize()
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        sweeps = 0
+        start.record()
+        for _ in range(args.calls):
+            fluid.maccormack(c, ᔑdt)
+            sweeps += sum(c.maccormack_sweeps)
+        end.record()
+        torch.cuda.synchronize()
+        ms = start.elapsed_time(end)/args.calls
+        moved = gs**3*(BYTES_SMOOTH + BYTES_SWEEP*sweeps/args.calls)
+        hbm_ms = moved/HBM_PEAK*1e3
+        result['void' if void else 'smooth'] = {
+            'ms_per_call': round(ms, 4), 'sweeps_per_call': sweeps/args.calls,
+            'bytes_per_call': int(moved), 'hbm_ms_at_8TBps': round(hbm_ms, 4),
+            'fraction_of_hbm_rate': round(hbm_ms/ms, 4),
+            'min_rho': float(c.ϱ.min().item())}
+        del c
+        torch.cuda.empty_cache()
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        with open(args.out, 'w') as f:
+            f.write(line + '\n')
+
+
+if __name__ == '__main__':
+    main()
