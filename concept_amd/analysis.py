@@ -6,9 +6,10 @@
   get_powerspec_bins()           analysis.py:235-438, construct_powerspec_k_bin_centers
                                  analysis.py:441-496
   compute_powerspec()            analysis.py:500-579: interpolate_upstream(..., 'ρ', ...,
-                                 output_space='Fourier') (mesh.py:492-635) on mesh contexts of
-                                 their own roles, then the k-shell binning in HIP
-                                 (cg_powerspec_bin, csrc/cg_analysis.hip)
+                                 output_space='Fourier') (mesh.py:492-635; here
+                                 interactions.interpolate_upstream, the one gravity uses) on
+                                 mesh contexts of their own roles, then the k-shell binning in
+                                 HIP (cg_powerspec_bin, csrc/cg_analysis.hip)
   compute_powerspec_σ()          analysis.py:856-914
   save_powerspec()               analysis.py:796-833 with save_polyspec / get_txt_info
                                  (analysis.py:3283-3484, 3495-3751)
@@ -27,6 +28,7 @@ import torch
 
 from . import commons
 from . import comm as _comm
+from .interactions import interpolate_upstream
 from .lib import ConceptGPUError
 from .mesh import get_mesh
 
@@ -311,79 +313,6 @@ def _mesh(gridsize, role):
     return get_mesh(gridsize, p.boxsize, p.nghosts, p.cell_centered, 2, None, role=role)
 
 
-def interpolate_upstream(components, gridsizes_upstream, gridsize_global, order, deconvolve,
-                         interlace, a=1.0, role='powerspec'):
-    """interpolate_upstream(components, ..., quantity='ρ', output_space='Fourier')
-    (mesh.py:492-635) with add_upstream_to_global_slabs (mesh.py:654-711): the mesh whose
-    Fourier view holds the global slab.  The meshes are of the roles `role` and
-    `role` + ' upstream' ('powerspec' by default), apart from those of gravity()."""
-    from .interactions import (_aligned, _check_halo_reach, group_components,
-                               lattice_shifts)
-    p = commons.params
-    boxsize = p.boxsize
-    shifts = lattice_shifts(interlace, p.cell_centered)
-    slab_global = None
-
-    def upstream_mesh(g):
-        if slab_global is None and g == gridsize_global:
-            return _mesh(gridsize_global, role)
-        return _mesh(g, role + ' upstream')
-
-    def add_to_global(up, deconv_order, nlattice=1, shift=(0, 0, 0)):
-        nonlocal slab_global
-        if slab_global is None and up.gridsize == gridsize_global:
-            slab_global = up.fourier_operate(deconv_order, nlattice, shift)
-        elif slab_global is None:
-            slab_global = _mesh(gridsize_global, role)
-            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='=')
-        else:
-            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='+=')
-    for c, g in zip(components, gridsizes_upstream):
-        if c.representation == 'fluid' and c.gridsize != g:
-            raise ConceptGPUError(
-                f'add_fluid_to_grid() got component with global grid size {c.gridsize} and '
-                f'non-matching grid of global grid size {g}')
-    groups = group_components(components, gridsizes_upstream, [gridsize_global, ...])
-    for g, group in groups.items():
-        fft_factor = float(g)**(-3)  # mesh.py:582
-        fluids, particles = group.get('fluid', []), group.get('particles', [])
-        if fluids:
-            up = upstream_mesh(g)
-            for i, fluid in enumerate(fluids):
-                # add_fluid_to_grid, quantity 'ρ' (mesh.py:1713-1718)
-                factor = fft_factor
-                factor *= a**(-3*(1 + fluid.w_eff(a=a)))
-                up.fluid_add(fluid.ϱ, factor, '=' if i == 0 else '+=')
-            up.fft_forward()
-            up.nullify_nyquist()
-            add_to_global(up, 0)
-        for shift in (shifts if particles else ()):
-            up = upstream_mesh(g)
-            cloud = {1: (0, 1), 2: (0, 1), 3: (1, 2), 4: (1, 2)}[order]
-            if shift != (0, 0, 0):
-                cloud = (cloud[0] + 1, cloud[1] + 1)
-            if up.dist and up.nprocs > 1 and max(cloud) > up.ghost_layers:
-                raise ConceptGPUError('interpolation reaches beyond the 3 halo layers')
-            for c in particles:
-                _check_halo_reach(c, up, cloud, 0)
-            up.zero()
-            for c in particles:
-                # interpolate_particles, quantity 'ρ' (mesh.py:1543-1549, 1573)
-                contribution = a**(-3*(1 + c.w_eff(a=a)))
-                contribution *= c.mass
-                contribution *= fft_factor*(g/boxsize)**3
-                if order == 2 and shift == (0, 0, 0):
-                    up.deposit(c.pos, contribution)
-                else:
-                    up.deposit_general(c.pos, contribution, order, shift)
-            up.fold_ghosts(general=not (order == 2 and shift == (0, 0, 0)
-                                        and all(_aligned(c, up) for c in particles)))
-            up.fft_forward()
-            up.nullify_nyquist()
-            add_to_global(up, order*int(bool(deconvolve)), len(shifts), shift)
-    return slab_global
-
-
 def _device_bin_table(declaration, device):
     key = (id(declaration.k_bin_indices), str(device))
     t = _device_tables.get(key)
@@ -403,9 +332,11 @@ def compute_powerspec(declaration, a=1.0, timings=None):
     if timings is not None:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
+    # quantity 'ρ' (mesh.py:1543-1549, 1713-1718)
     slab = interpolate_upstream(components, gridsizes_upstream, declaration.gridsize,
-                                declaration.interpolation, declaration.deconvolve,
-                                declaration.interlace, a)
+                                lambda c: a**(-3*(1 + c.w_eff(a=a))), declaration.interpolation,
+                                declaration.deconvolve, declaration.interlace,
+                                roles=('powerspec', 'powerspec upstream'))
     if timings is not None:
         ev[1].record()
     nbins = len(declaration.k_bin_centers)
@@ -419,10 +350,7 @@ def compute_powerspec(declaration, a=1.0, timings=None):
     power = power.cpu().numpy()
     c = _comm.active()
     if c is not None and c.world > 1:
-        parts = c.all_gather_floats(power.tolist()).numpy()
-        power = parts[0].copy()
-        for r in range(1, parts.shape[0]):
-            power = power + parts[r]
+        power = c.sum_in_rank_order(power)
     # normalisation (analysis.py:567-577)
     normalization = 0
     for component in components:

@@ -210,6 +210,19 @@ class Comm:
         dist.all_gather(out, pad, group=self.group)
         return torch.cat([o[:c] for o, c in zip(out, counts)]).to(t.device)
 
+    def sum_in_rank_order(self, x):
+        """The sum of every rank's `x` (equal shapes), the parts added one after the other in
+        ascending rank order: the same bits on every rank.  A host float64 array is gathered
+        and added on the host, a device tensor on its device."""
+        if isinstance(x, torch.Tensor):
+            parts = self.all_gather_rows(x.reshape(1, -1))
+        else:
+            parts = self.all_gather_floats(x.ravel().tolist()).numpy()
+        total = parts[0]
+        for r in range(1, parts.shape[0]):
+            total = total + parts[r]
+        return total.reshape(x.shape)
+
     def any(self, flag):
         """Logical OR of a host bool over the ranks."""
         return bool(self.all_gather_ints([int(bool(flag))]).sum().item())

@@ -139,31 +139,13 @@ def particle_mesh(receivers, suppliers, gridsize_global, quantity, force, method
     deconv_order_global = (int(bool(deconvolve_upstream)) + int(bool(deconvolve_downstream)))
     deconv_order_global *= interpolation_order
     # interpolate_upstream (mesh.py:492-635): nullified grid, every supplier deposited
-    # Suppliers whose memory is in exact tile order of this mesh (Component.tile_sort)
-    # take the LDS-tiled kernel; the first of them assigns the mesh (no zero-fill pass).
     fft_factor = float(gridsize_global)**(-3)  # mesh.py:582
-    ordered = sorted(suppliers, key=lambda s: not (s.tiles_exact and s.tile_mesh is mesh))
-    mesh_started = False
-    aligned = all(_aligned(s, mesh) for s in suppliers)
-    if not aligned:  # clouds land in the halo on both sides: it must start from zero
-        for s in suppliers:
-            _check_halo_reach(s, mesh, (0, 1), 0)
-        mesh.zero()
-        mesh_started = True
-    for supplier in ordered:
-        contribution = _particle_contribution(supplier, ᔑdt, fft_factor, gridsize_global, boxsize)
-        if supplier.tiles_exact and supplier.tile_mesh is mesh:
-            mesh.deposit_tiled(supplier.pos, supplier.tile_table, contribution,
-                               accumulate=mesh_started)
-        else:
-            if not mesh_started:
-                mesh.zero()
-            mesh.deposit(supplier.pos, contribution)
-        mesh_started = True
+    general = _deposit_particles(mesh, suppliers, lambda s: _particle_contribution(
+        s, ᔑdt, fft_factor, gridsize_global, boxsize))
     # communicate_ghosts(grid, '+=') (mesh.py:609) and, after the solve, communicate_ghosts(grid,
     # '=') (interactions.py:2303-2307): posted here, both travel under the transforms (one
     # domain wraps by itself and needs neither)
-    fold = mesh.fold_ghosts_start(general=not aligned)
+    fold = mesh.fold_ghosts_start(general=general)
     # interactions.py:2092-2118 and :2302
     C, long_range, E = _potential_constants(p, potential, gridsize_global)
     mesh.poisson_solve(deconv_order_global, C, long_range, E, fold_finish=fold, fill=True)
@@ -198,13 +180,20 @@ def pm_streaming_plan(components):
             'C': C, 'long_range': long_range, 'E': E, 'force': force, 'method': method}
 
 
+def _weighted_contribution(weight, mass, fft_factor, gridsize, boxsize):
+    """interpolate_particles (mesh.py:1543-1573): what one particle adds to the mesh — the
+    dimensionless weight of the quantity, times the mass, times the FFT normalisation over the
+    cell volume, multiplied in the reference's order"""
+    contribution = weight
+    contribution *= mass
+    contribution *= fft_factor*(gridsize/boxsize)**3
+    return contribution
+
+
 def _particle_contribution(supplier, ᔑdt, fft_factor, gridsize, boxsize):
     """mesh.py:1550-1573 for quantity 'a²ρ'"""
-    contribution = ᔑdt['a**(-3*w_eff-1)', supplier.name]/ᔑdt['1']
-    contribution *= supplier.mass
-    contribution_factor = fft_factor*(gridsize/boxsize)**3
-    contribution *= contribution_factor
-    return contribution
+    return _weighted_contribution(ᔑdt['a**(-3*w_eff-1)', supplier.name]/ᔑdt['1'], supplier.mass,
+                                  fft_factor, gridsize, boxsize)
 
 
 def _potential_constants(p, potential, gridsize_global):
@@ -223,6 +212,43 @@ def _same_tiling(component, mesh):
     return (component.tile_table is not None and t is not None
             and (t is mesh or (t.gridsize, t.boxsize, t.nghosts, t.device)
                  == (mesh.gridsize, mesh.boxsize, mesh.nghosts, mesh.device)))
+
+
+def _deposit_particles(up, particles, contribution, order=2, shift=(0, 0, 0)):
+    """interpolate_particles (mesh.py:1512-1636) of every component of `particles` onto the
+    mesh `up`, one sub-lattice: contribution(component) is what one of its particles adds.
+    Components whose memory is in exact tile order of this grid (Component.tile_sort) take the
+    LDS-tiled kernel (CIC on the unshifted lattice) and go first: the first of them assigns the
+    mesh (no zero-fill pass), later ones accumulate.  Stops before communicate_ghosts(grid,
+    '+=') (mesh.py:609); returns whether that fold must be the general one."""
+    simple = order == 2 and shift == (0, 0, 0)
+    cloud = {1: (0, 1), 2: (0, 1), 3: (1, 2), 4: (1, 2)}[order]
+    if shift != (0, 0, 0):
+        cloud = (cloud[0] + 1, cloud[1] + 1)
+    if up.dist and up.nprocs > 1 and max(cloud) > up.ghost_layers:
+        raise ConceptGPUError('interpolation reaches beyond the 3 halo layers')
+
+    def tiled(c):
+        return simple and c.tiles_exact and _same_tiling(c, up)
+    aligned = all(_aligned(c, up) for c in particles)
+    started = False
+    if not aligned:  # clouds land in the halo on both sides: it must start from zero
+        for c in particles:
+            _check_halo_reach(c, up, cloud, 0)
+        up.zero()
+        started = True
+    for c in sorted(particles, key=lambda c: not tiled(c)):
+        if tiled(c):
+            up.deposit_tiled(c.pos, c.tile_table, contribution(c), accumulate=started)
+        else:
+            if not started:
+                up.zero()
+            if simple:
+                up.deposit(c.pos, contribution(c))
+            else:
+                up.deposit_general(c.pos, contribution(c), order, shift)
+        started = True
+    return not (simple and aligned)
 
 
 def _kick_particles(mesh, receiver, force, method, ᔑdt, ᔑdt_key):
@@ -287,35 +313,99 @@ def lattice_shifts(kind, cell_centered=True):
     return table[kind]
 
 
-def particle_mesh_general(receivers, suppliers, gridsize_global, quantity, force, method,
-                          potential, interpolation_order, deconvolve_upstream,
-                          deconvolve_downstream, interlace_upstream, interlace_downstream,
-                          ᔑdt, ᔑdt_key):
-    """interactions.py:1985-2335 with interpolate_upstream (mesh.py:492-635) and
-    add_upstream_to_global_slabs (mesh.py:654-711), step for step, on one GPU: one mesh
-    context per (grid size, role) plays the reference's named slabs.  Built: particle and
-    fluid suppliers / receivers, upstream / downstream grid sizes
-    different from the global one (row 1b: copy_modes), interpolation orders NGP / CIC /
-    TSC / PCS, interlacing on 'bcc' / 'fcc' lattices, finite-difference (2, 4) and
-    Fourier-space (0) gradients (row 3)."""
-    p = receivers[0].params
-    boxsize = p.boxsize
-    dev = receivers[0].device
-    if not 1 <= interpolation_order <= 4:
-        raise ConceptGPUError(
-            f'interpolate_particles() called with order = {interpolation_order} '
-            f'∉ {{1 (NGP), 2 (CIC), 3 (TSC), 4 (PCS)}}')
-    shifts_upstream = lattice_shifts(interlace_upstream, p.cell_centered)
-    gs_up = [s.potential_gridsizes[force][method].upstream for s in suppliers]
-    gs_down = [r.potential_gridsizes[force][method].downstream for r in receivers]
-    for c, g in list(zip(suppliers, gs_up)) + list(zip(receivers, gs_down)):
+def _check_fluid_gridsizes(components, gridsizes):
+    for c, g in zip(components, gridsizes):
         if c.representation == 'fluid' and c.gridsize != g:
             raise ConceptGPUError(
                 f'add_fluid_to_grid() got component with global grid size {c.gridsize} and '
                 f'non-matching grid of global grid size {g}')
 
+
+def interpolate_upstream(components, gridsizes_upstream, gridsize_global, weight, order,
+                         deconvolve, interlace, roles=('global', 'upstream'), device=None):
+    """interpolate_upstream(..., output_space='Fourier') (mesh.py:492-635) with
+    add_upstream_to_global_slabs (mesh.py:654-711), step for step: per upstream grid size (the
+    global one first), fluids then particles (once per sub-lattice of `interlace`); each
+    upstream slab is added onto the global one in Fourier space.  Returns the mesh whose
+    Fourier view holds the global slab.  weight(component) is the dimensionless factor of the
+    quantity ('a²ρ' from the step integrals for gravity, 'ρ' from the scale factor for the
+    outputs).  One mesh context per (grid size, role) plays the reference's named slabs:
+    roles = (the global slab, the upstream ones) — every caller keeps contexts of its own."""
+    if not 1 <= order <= 4:
+        raise ConceptGPUError(
+            f'interpolate_particles() called with order = {order} '
+            f'∉ {{1 (NGP), 2 (CIC), 3 (TSC), 4 (PCS)}}')
+    p = components[0].params
+    boxsize = p.boxsize
+    shifts = lattice_shifts(interlace, p.cell_centered)
+    _check_fluid_gridsizes(components, gridsizes_upstream)
+
     def mesh_for(gridsize, role):
-        return get_mesh(gridsize, boxsize, p.nghosts, p.cell_centered, 2, dev, role=role)
+        return get_mesh(gridsize, boxsize, p.nghosts, p.cell_centered, 2, device, role=role)
+    slab_global = None
+
+    def upstream_mesh(gridsize_upstream):
+        if slab_global is None and gridsize_upstream == gridsize_global:
+            return mesh_for(gridsize_global, roles[0])
+        return mesh_for(gridsize_upstream, roles[1])
+
+    def add_to_global(up, deconv_order, nlattice=1, shift=(0, 0, 0)):
+        nonlocal slab_global
+        if slab_global is None and up.gridsize == gridsize_global:
+            slab_global = up.fourier_operate(deconv_order, nlattice, shift)
+        elif slab_global is None:
+            slab_global = mesh_for(gridsize_global, roles[0])
+            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='=')
+        else:
+            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='+=')
+    groups = group_components(components, gridsizes_upstream, [gridsize_global, ...])
+    for gridsize_upstream, group in groups.items():
+        fft_factor = float(gridsize_upstream)**(-3)  # mesh.py:582
+        fluid_components = group.get('fluid', [])
+        particle_components = group.get('particles', [])
+        if fluid_components:
+            up = upstream_mesh(gridsize_upstream)
+            for i, fluid in enumerate(fluid_components):
+                # add_fluid_to_grid (mesh.py:1712-1718)
+                factor = fft_factor
+                factor *= weight(fluid)
+                up.fluid_add(fluid.ϱ, factor, '=' if i == 0 else '+=')
+            up.fft_forward()
+            up.nullify_nyquist()
+            add_to_global(up, 0)
+        for shift in (shifts if particle_components else ()):
+            up = upstream_mesh(gridsize_upstream)
+            general = _deposit_particles(
+                up, particle_components,
+                lambda c: _weighted_contribution(weight(c), c.mass, fft_factor,
+                                                 gridsize_upstream, boxsize),
+                order, shift)
+            # communicate_ghosts(grid, '+=') (mesh.py:609)
+            up.fold_ghosts(general=general)
+            up.fft_forward()
+            up.nullify_nyquist()
+            add_to_global(up, order*int(bool(deconvolve)), len(shifts), shift)
+    return slab_global
+
+
+def particle_mesh_general(receivers, suppliers, gridsize_global, quantity, force, method,
+                          potential, interpolation_order, deconvolve_upstream,
+                          deconvolve_downstream, interlace_upstream, interlace_downstream,
+                          ᔑdt, ᔑdt_key):
+    """interactions.py:1985-2335, step for step, on one GPU: one mesh context per (grid
+    size, role) plays the reference's named slabs.  Built: particle and fluid suppliers /
+    receivers, upstream / downstream grid sizes different from the
+    global one (row 1b: copy_modes), interpolation orders NGP / CIC / TSC / PCS, interlacing
+    on 'bcc' / 'fcc' lattices, finite-difference (2, 4) and Fourier-space (0) gradients
+    (row 3)."""
+    p = receivers[0].params
+    dev = receivers[0].device
+    gs_up = [s.potential_gridsizes[force][method].upstream for s in suppliers]
+    gs_down = [r.potential_gridsizes[force][method].downstream for r in receivers]
+    _check_fluid_gridsizes(receivers, gs_down)
+
+    def mesh_for(gridsize, role):
+        return get_mesh(gridsize, p.boxsize, p.nghosts, p.cell_centered, 2, dev, role=role)
     # interactions.py:2049-2080: which deconvolutions are promoted to the global one
     only_particle_suppliers = all(s.representation == 'particles' for s in suppliers)
     only_particle_receivers = all(r.representation == 'particles' for r in receivers)
@@ -329,80 +419,10 @@ def particle_mesh_general(receivers, suppliers, gridsize_global, quantity, force
         deconvolve_downstream = False
         deconv_order_global += 1
     deconv_order_global *= interpolation_order
-    # ---- interpolate_upstream (mesh.py:571-620): per upstream grid size (the global one
-    # first), fluids then particles (once per sub-lattice); each upstream slab is added
-    # onto the global one in Fourier space (add_upstream_to_global_slabs, mesh.py:654-711)
-    slab_global = None
-
-    def upstream_mesh(gridsize_upstream):
-        if slab_global is None and gridsize_upstream == gridsize_global:
-            return mesh_for(gridsize_global, 'global')
-        return mesh_for(gridsize_upstream, 'upstream')
-
-    def add_to_global(up, deconv_order, nlattice=1, shift=(0, 0, 0)):
-        nonlocal slab_global
-        if slab_global is None and up.gridsize == gridsize_global:
-            slab_global = up.fourier_operate(deconv_order, nlattice, shift)
-        elif slab_global is None:
-            slab_global = mesh_for(gridsize_global, 'global')
-            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='=')
-        else:
-            slab_global.copy_modes_from(up, deconv_order, nlattice, shift, operation='+=')
-    groups = group_components(suppliers, gs_up, [gridsize_global, ...])
-    for gridsize_upstream, group in groups.items():
-        fft_factor = float(gridsize_upstream)**(-3)  # mesh.py:582
-        fluid_components = group.get('fluid', [])
-        particle_components = group.get('particles', [])
-        if fluid_components:
-            up = upstream_mesh(gridsize_upstream)
-            for i, fluid in enumerate(fluid_components):
-                # add_fluid_to_grid, quantity 'a²ρ' (mesh.py:1712-1717)
-                factor = fft_factor
-                factor *= ᔑdt['a**(-3*w_eff-1)', fluid.name]/ᔑdt['1']
-                up.fluid_add(fluid.ϱ, factor, '=' if i == 0 else '+=')
-            up.fft_forward()
-            up.nullify_nyquist()
-            add_to_global(up, 0)
-        for shift in (shifts_upstream if particle_components else ()):
-            up = upstream_mesh(gridsize_upstream)
-            simple = interpolation_order == 2 and shift == (0, 0, 0)
-            # tile-sorted suppliers first: the LDS-tiled deposit assigns the mesh (no
-            # zero-fill pass), later ones accumulate
-            ordered = sorted(particle_components,
-                             key=lambda c: not (simple and c.tiles_exact and _same_tiling(c, up)))
-            started = False
-            aligned = all(_aligned(c, up) for c in particle_components)
-            cloud = {1: (0, 1), 2: (0, 1), 3: (1, 2), 4: (1, 2)}[interpolation_order]
-            if shift != (0, 0, 0):
-                cloud = (cloud[0] + 1, cloud[1] + 1)
-            if up.dist and up.nprocs > 1 and max(cloud) > up.ghost_layers:
-                raise ConceptGPUError('interpolation reaches beyond the 3 halo layers')
-            if not aligned:
-                for c in particle_components:
-                    _check_halo_reach(c, up, cloud, 0)
-                up.zero()
-                started = True
-            for supplier in ordered:
-                contribution = _particle_contribution(supplier, ᔑdt, fft_factor,
-                                                      gridsize_upstream, boxsize)
-                if simple and supplier.tiles_exact and _same_tiling(supplier, up):
-                    up.deposit_tiled(supplier.pos, supplier.tile_table, contribution,
-                                     accumulate=started)
-                    started = True
-                    continue
-                if not started:
-                    up.zero()
-                    started = True
-                if simple:
-                    up.deposit(supplier.pos, contribution)
-                else:
-                    up.deposit_general(supplier.pos, contribution, interpolation_order, shift)
-            # communicate_ghosts(grid, '+=') (mesh.py:609)
-            up.fold_ghosts(general=not (simple and aligned))
-            up.fft_forward()
-            up.nullify_nyquist()
-            add_to_global(up, interpolation_order*int(bool(deconvolve_upstream)),
-                          len(shifts_upstream), shift)
+    # quantity 'a²ρ' (mesh.py:1550-1553, 1712-1717)
+    slab_global = interpolate_upstream(
+        suppliers, gs_up, gridsize_global, lambda c: ᔑdt['a**(-3*w_eff-1)', c.name]/ᔑdt['1'],
+        interpolation_order, deconvolve_upstream, interlace_upstream, device=dev)
     # ---- potential (interactions.py:2092-2120)
     C, long_range, E = _potential_constants(p, potential, gridsize_global)
     slab_global.poisson_kernel(deconv_order_global, C, long_range, E)

@@ -3,7 +3,9 @@
 Counterpart of the reference's global/upstream/downstream grid buffers and
 FFTW slabs (mesh.py:492-710 interpolate_upstream, :3769-3866 get_fftw_slab,
 communication.py:1666 get_buffer): one persistent mesh per (grid size,
-device), living in HBM, reused across calls."""
+device), living in HBM, reused across calls.  The procedure itself —
+interpolate_upstream for gravity, power spectra and 2D renders alike — is
+interactions.interpolate_upstream; this module holds the steps it calls."""
 import ctypes
 import math
 import os

@@ -4,7 +4,8 @@
   get_render2D_declarations()    graphics.py:1168-1249 over analysis.get_output_declarations
                                  (graphics.py:1080-1143)
   compute_render2D()             graphics.py:1278-1336: interpolate_upstream(..., 'ρ', ...,
-                                 output_space='Fourier') on mesh contexts of the roles
+                                 output_space='Fourier') (interactions.interpolate_upstream,
+                                 the one gravity uses) on mesh contexts of the roles
                                  'render2D' and 'render2D upstream', resize_grid
                                  (mesh.py:808-933) for the terminal image, the inverse
                                  transforms, then the projection in HIP (cg_render2d_project,
@@ -34,7 +35,8 @@ import torch
 
 from . import analysis, commons
 from . import comm as _comm
-from .analysis import _components_str, _mesh, interpolate_upstream
+from .analysis import _components_str, _mesh
+from .interactions import interpolate_upstream
 
 # what a declaration holds (graphics.py:1241-1249): the components, which outputs to make,
 # the resolved options, and the projections (device tensors by output key)
@@ -176,11 +178,7 @@ def project_render2D(mesh, projection, axis, extent, a=1.0):
                           out=projection)
     c = _comm.active()
     if c is not None and c.world > 1:
-        parts = c.all_gather_rows(projection.reshape(1, -1))
-        total = parts[0]
-        for r in range(1, parts.shape[0]):
-            total = total + parts[r]
-        projection.copy_(total.reshape(projection.shape))
+        projection.copy_(c.sum_in_rank_order(projection))
     return projection
 
 
@@ -196,9 +194,11 @@ def compute_render2D(declaration, a=1.0, timings=None):
     if timings is not None:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         ev[0].record()
+    # quantity 'ρ' (mesh.py:1543-1549, 1713-1718)
     slab = interpolate_upstream(components, gridsizes_upstream, declaration.gridsize,
-                                declaration.interpolation, declaration.deconvolve,
-                                declaration.interlace, a, role='render2D')
+                                lambda c: a**(-3*(1 + c.w_eff(a=a))), declaration.interpolation,
+                                declaration.deconvolve, declaration.interlace,
+                                roles=('render2D', 'render2D upstream'))
     if timings is not None:
         ev[1].record()
     # the terminal image: a copy of the slab of terminal resolution, in real space

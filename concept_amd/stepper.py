@@ -1011,6 +1011,23 @@ class Timeloop(RungStepper):
             if streaming:
                 self._rps = [c.to_regions(self._plan['mesh']) for c in self.components]
 
+    def _dumper(self, times, output_dir, output_base, write):
+        """The on_dump callback of the three dumpers below: at a dump time that is among
+        `times` ({'a': [...], 't': [...]}; None: at every dump) it calls
+        write(loop, name, dump_time) with name = <output_dir>/<output_base>_<a|t>=<value>, the
+        value with just enough digits (_dump_ndigits)."""
+        ndigits = self._dump_ndigits()
+        sep = '_' if output_base else ''
+
+        def on_dump(loop, dump_time):
+            value = dump_time.a if dump_time.time_param == 'a' else dump_time.t
+            if times is not None and not any(abs(value - v) <= 1e-12*max(abs(v), 1e-300)
+                                             for v in times[dump_time.time_param]):
+                return
+            write(loop, f'{output_dir}/{output_base}{sep}{dump_time.time_param}='
+                        f'{value:.{ndigits}f}', dump_time)
+        return on_dump
+
     def snapshot_dumper(self, output_dir, output_base='snapshot', only_snapshot_times=False,
                         **save_options):
         """An on_dump callback that writes a GADGET snapshot per dump time (main.dump,
@@ -1021,18 +1038,9 @@ class Timeloop(RungStepper):
         only_snapshot_times: write at the times output_times lists for 'snapshot' only (the
         other output kinds' times are dumps of the loop too)."""
         from . import snapshot
-        p = self.params
-        ndigits = self._dump_ndigits()
-        sep = '_' if output_base else ''
         self.snapshots_written = []
 
-        def on_dump(loop, dump_time):
-            value = dump_time.a if dump_time.time_param == 'a' else dump_time.t
-            if only_snapshot_times and not any(
-                    abs(value - v) <= 1e-12*max(abs(v), 1e-300)
-                    for v in p.snapshot_times[dump_time.time_param]):
-                return
-            name = f'{output_dir}/{output_base}{sep}{dump_time.time_param}={value:.{ndigits}f}'
+        def write(loop, name, dump_time):
             # GADGET snapshots hold particles: fluid components (riding along through
             # fluid_drift) are left out, as the reference's writer leaves them out
             # (snapshot.py: GadgetSnapshot.populate keeps the particle components)
@@ -1048,7 +1056,8 @@ class Timeloop(RungStepper):
             fn = snapshot.save(particles, name, a=loop.cosmo.a,
                                **{'output_base': output_base or 'snapshot', **save_options})
             loop.snapshots_written.append(fn)
-        return on_dump
+        return self._dumper(self.params.snapshot_times if only_snapshot_times else None,
+                            output_dir, output_base, write)
 
     def _dump_ndigits(self):
         """just enough digits that neighbouring dumps and the initial time differ in the
@@ -1075,20 +1084,12 @@ class Timeloop(RungStepper):
         <output_dir>/<output_base>_<a|t>=<value> with the digits of snapshot_dumper (main.dump,
         main.py:1676-1700)."""
         from . import analysis
-        p = self.params
-        ndigits = self._dump_ndigits()
-        sep = '_' if output_base else ''
         self.powerspecs_written = []
 
-        def on_dump(loop, dump_time):
-            value = dump_time.a if dump_time.time_param == 'a' else dump_time.t
-            if not any(abs(value - v) <= 1e-12*max(abs(v), 1e-300)
-                       for v in p.powerspec_times[dump_time.time_param]):
-                return
-            name = f'{output_dir}/{output_base}{sep}{dump_time.time_param}={value:.{ndigits}f}'
+        def write(loop, name, dump_time):
             analysis.powerspec(loop.components, name, a=loop.cosmo.a, t=loop.cosmo.t)
             loop.powerspecs_written.append(name)
-        return on_dump
+        return self._dumper(self.params.powerspec_times, output_dir, output_base, write)
 
     def render2D_dumper(self, output_dir, output_base='render2D', stream=None):
         """An on_dump callback that writes the 2D renders render2D_select asks for
@@ -1096,21 +1097,13 @@ class Timeloop(RungStepper):
         lists for 'render2D', named <output_dir>/<output_base>_<a|t>=<value> plus the extension,
         with the digits of snapshot_dumper (main.dump, main.py:1676-1700)."""
         from . import render
-        p = self.params
-        ndigits = self._dump_ndigits()
-        sep = '_' if output_base else ''
         self.renders2D_written = []
 
-        def on_dump(loop, dump_time):
-            value = dump_time.a if dump_time.time_param == 'a' else dump_time.t
-            if not any(abs(value - v) <= 1e-12*max(abs(v), 1e-300)
-                       for v in p.render2D_times[dump_time.time_param]):
-                return
-            name = f'{output_dir}/{output_base}{sep}{dump_time.time_param}={value:.{ndigits}f}'
+        def write(loop, name, dump_time):
             _, files = render.render2D(loop.components, name, a=loop.cosmo.a, t=loop.cosmo.t,
                                        stream=stream)
             loop.renders2D_written.extend(files)
-        return on_dump
+        return self._dumper(self.params.render2D_times, output_dir, output_base, write)
 
     # -- main.timeloop (main.py:102-471) ---------------------------------------------------
     def run(self):

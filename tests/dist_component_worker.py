@@ -100,6 +100,9 @@ def main():
         interp, lattice, diff = arg.split(',')
         test_gpu_general_interp.test_gravity_pm_on_tile_sorted_blobs_vs_oracle(interp, lattice,
                                                                               int(diff))
+    elif case == 'blobs_powerspec':
+        import test_gpu_general_interp
+        test_gpu_general_interp.test_powerspec_cic_sorted_equals_shuffled()
     elif case == 'config4':
         import test_gpu_fluid
         n_side, gs = (int(v) for v in arg.split(','))

@@ -256,6 +256,8 @@ COMPONENT_CASES = [
     # tile-sorted blobs through interlaced TSC: the LDS boxes of the general deposit and gather
     # on slabs (layers mapped through the halo)
     ('blobs', 'TSC,bcc,2'),
+    # ... and through the power spectrum's CIC deposit: tiled for sorted particles, direct else
+    ('blobs_powerspec', '-'),
 ]
 
 

@@ -670,3 +670,51 @@ def test_powerspec_sorted_equals_shuffled():
     rel = np.abs(P_sorted - P_shuffled)/np.abs(P_shuffled)
     print(f'\npower spectrum sorted vs shuffled: {rel.max():.3g}')
     assert rel.max() <= 1e-12, rel.max()
+
+
+def test_powerspec_cic_sorted_equals_shuffled():
+    """compute_powerspec with CIC on the 'sc' lattice, where tile-sorted components — what
+    Timeloop hands to a dump after a drift — take the LDS-tiled deposit (it assigns the mesh:
+    no zero-fill pass, no global atomics) and shuffled ones the direct deposit onto a zeroed
+    mesh: the same power to 1e-12, the bar of the power-spectrum goldens, and the same mode
+    counts.  A 32^3 grid is two 16-cell tiles per axis, the smallest on which a tile has a
+    lower neighbour and a wrapped one.  Also run over 2 and 4 domains."""
+    import warnings
+    from concept_amd import analysis, commons
+    from concept_amd.mesh import PotentialMesh
+    from concept_amd.species import Component
+    gs = 32
+    p = commons.load_params({
+        'boxsize': L_BOX,
+        'potential_options': {'gridsize': {'global': {'gravity': {'pm': gs}}}},
+        'select_forces': {'all': {'gravity': 'pm'}},
+        'powerspec_options': {'gridsize': gs, 'interpolation': 'CIC', 'interlace': False},
+        'powerspec_select': {'matter': True}})
+    pos = blob_positions(n_blob=5000, gridsize=gs)
+    n = pos.shape[0]
+    results = []
+    for sort in (True, False):
+        c = Component('matter', 'matter', N=n, mass=p.ρ_mbar*L_BOX**3/n)
+        c.populate(pos, 'pos')
+        c.populate(np.zeros((n, 3)), 'mom')
+        if sort:
+            c.tile_sort()
+        calls = []
+        with pytest.MonkeyPatch.context() as mp, warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            for name in ('zero', 'deposit', 'deposit_tiled', 'deposit_general'):
+                def counted(self, *args, _name=name, _method=getattr(PotentialMesh, name), **kw):
+                    calls.append(_name)
+                    return _method(self, *args, **kw)
+                mp.setattr(PotentialMesh, name, counted)
+            decl = analysis.get_powerspec_declarations([c])[0]
+            analysis.compute_powerspec(decl)
+        assert decl.interpolation == 2 and decl.gridsize == gs
+        assert calls == (['deposit_tiled'] if sort else ['zero', 'deposit']), calls
+        results.append((decl.power.copy(), np.array(decl.n_modes).copy()))
+    (P_sorted, modes_sorted), (P_shuffled, modes_shuffled) = results
+    np.testing.assert_array_equal(modes_sorted, modes_shuffled)
+    assert np.all(np.isfinite(P_shuffled)) and np.all(P_shuffled > 0)
+    rel = np.abs(P_sorted - P_shuffled)/np.abs(P_shuffled)
+    print(f'\npower spectrum CIC sorted vs shuffled: {rel.max():.3g}')
+    assert rel.max() <= 1e-12, rel.max()

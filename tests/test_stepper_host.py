@@ -1,13 +1,14 @@
 """Host logic of the rung loop (no GPU): the step integrals worked out when read and the
 ᔑdt_rungs arrays filled in when read (stepper._LazyIntegrals, _RungIntegrals) give what the
 eager forms give (get_time_step_integrals, main.py:998-1073; the arrays of main.py:1480-1552);
-the integrals' cache; bench.py's link model."""
+the integrals' cache; bench.py's link model; the on_dump callbacks of the three dumpers."""
 import json
 import os
 import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -80,6 +81,79 @@ def test_integrals_cache_prefetch():
     assert len(n) == 2
     assert c(1.0, 2.0) == {'1': 1.0} and len(n) == 2      # from the cache
     assert c(2.0, 3.0) == {'1': 1.0} and len(n) == 3
+
+
+def _dump_loop(stepper, components=()):
+    """a Timeloop as far as the dumpers look at it: begins at a = 0.1, t = 0.5; the dump times
+    need four digits to differ (0.1251 / 0.1254)"""
+    import types
+    loop = object.__new__(stepper.Timeloop)
+    loop.cosmo = types.SimpleNamespace(a=0.1, t=0.5)
+    loop.components = list(components)
+    loop.params = types.SimpleNamespace(
+        output_times={'a': (0.1251, 0.1254, 0.5), 't': (13.5,)},
+        snapshot_times={'a': (0.1254,), 't': (13.5,)},
+        powerspec_times={'a': (0.1251, 0.5), 't': ()},
+        render2D_times={'a': (0.5,), 't': (13.5,)})
+    assert loop._dump_ndigits() == 4
+    dumps = [stepper.DumpTime('a', t=1.0, a=0.1251), stepper.DumpTime('a', t=1.1, a=0.1254),
+             stepper.DumpTime('a', t=9.0, a=0.5*(1 + 5e-13)), stepper.DumpTime('t', t=13.5, a=0.9)]
+    return loop, dumps
+
+
+def test_dumpers_name_match_and_record(monkeypatch):
+    """snapshot_dumper, powerspec_dumper and render2D_dumper: the names <dir>/<base>_<a|t>=
+    <value> with the digits of _dump_ndigits, dump times outside their list skipped (matched to
+    1e-12), the *_written lists filled."""
+    import types
+    from concept_amd import analysis, render, snapshot, stepper
+    calls = []
+    monkeypatch.setattr(snapshot, 'save', lambda components, name, **kw: (
+        calls.append(('snapshot', [c.name for c in components], name, kw)), name + '.0')[1])
+    monkeypatch.setattr(analysis, 'powerspec', lambda components, name, **kw: calls.append(
+        ('powerspec', [c.name for c in components], name, kw)))
+    monkeypatch.setattr(render, 'render2D', lambda components, name, **kw: (
+        calls.append(('render2D', [c.name for c in components], name, kw)),
+        (None, [name + '.png', name + '.hdf5']))[1])
+    matter = types.SimpleNamespace(name='matter', representation='particles')
+    gas = types.SimpleNamespace(name='gas', representation='fluid')
+    loop, dumps = _dump_loop(stepper, [matter, gas])
+
+    def run(dumper):
+        calls.clear()
+        for dump_time in dumps:
+            dumper(loop, dump_time)
+        return list(calls)
+    # power spectra: at a = 0.1251 and 0.5 (the latter matched within 1e-12), not at 0.1254, t
+    assert run(loop.powerspec_dumper('out/dir')) == [
+        ('powerspec', ['matter', 'gas'], 'out/dir/powerspec_a=0.1251', {'a': 0.1, 't': 0.5}),
+        ('powerspec', ['matter', 'gas'], 'out/dir/powerspec_a=0.5000', {'a': 0.1, 't': 0.5})]
+    assert loop.powerspecs_written == ['out/dir/powerspec_a=0.1251', 'out/dir/powerspec_a=0.5000']
+    # renders: at a = 0.5 and t = 13.5; the stream is handed on; an empty base drops the '_'
+    assert run(loop.render2D_dumper('r', '', stream='tty')) == [
+        ('render2D', ['matter', 'gas'], 'r/a=0.5000', {'a': 0.1, 't': 0.5, 'stream': 'tty'}),
+        ('render2D', ['matter', 'gas'], 'r/t=13.5000', {'a': 0.1, 't': 0.5, 'stream': 'tty'})]
+    assert loop.renders2D_written == ['r/a=0.5000.png', 'r/a=0.5000.hdf5', 'r/t=13.5000.png',
+                                      'r/t=13.5000.hdf5']
+    # snapshots: every dump unless only_snapshot_times; particle components only, one warning
+    with pytest.warns(UserWarning, match='GADGET snapshots hold particle components only: gas'):
+        got = run(loop.snapshot_dumper('s', 'snap', snapformat=2))
+    kw = {'a': 0.1, 'output_base': 'snap', 'snapformat': 2}
+    assert got == [('snapshot', ['matter'], f's/snap_{stamp}', kw)
+                   for stamp in ('a=0.1251', 'a=0.1254', 'a=0.5000', 't=13.5000')]
+    assert loop.snapshots_written == [f's/snap_{stamp}.0' for stamp in (
+        'a=0.1251', 'a=0.1254', 'a=0.5000', 't=13.5000')]
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter('error')   # (warned once per loop)
+        got = run(loop.snapshot_dumper('s', '', only_snapshot_times=True))
+    kw = {'a': 0.1, 'output_base': 'snapshot'}
+    assert got == [('snapshot', ['matter'], 's/a=0.1254', kw),
+                   ('snapshot', ['matter'], 's/t=13.5000', kw)]
+    assert loop.snapshots_written == ['s/a=0.1254.0', 's/t=13.5000.0']
+    # nothing but fluids: nothing written
+    loop.components = [gas]
+    assert run(loop.snapshot_dumper('s')) == [] and loop.snapshots_written == []
 
 
 def test_link_model_prediction():
