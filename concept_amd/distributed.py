@@ -27,7 +27,6 @@ memory; the next step starts by waiting for that copy, after which every
 message size is known and the whole step is enqueued without another round
 trip.
 """
-import ctypes
 import os
 
 import torch
@@ -35,11 +34,6 @@ import torch
 from . import lib
 from .comm import Comm
 from .mesh import PotentialMesh
-
-
-
-def _vp(t):
-    return ctypes.c_void_p(t.data_ptr())
 
 
 class SlabDomain:
@@ -369,11 +363,8 @@ class ParticleStore:
         """Right after the gather-kick that listed the leavers of the coming drift: count them
         per destination on the device, swap the counts with the peers, start their copy to
         pinned memory.  Nothing here waits for the GPU."""
-        m = self.mesh
-        lib.check(lib.raw().cg_emigrant_dest(
-            m._ctx, _vp(self.cols['pos']), _vp(self.cols['mom']), _vp(self.emig_idx),
-            _vp(self.meta), self.emig_idx.numel(), float(dt_over_mass), _vp(self.emig_dest),
-            _vp(self.meta[1:])))
+        self.mesh.emigrant_dest(self.cols['pos'], self.cols['mom'], self.emig_idx, self.meta,
+                                dt_over_mass, self.emig_dest, self.meta[1:])
         P = self.comm.world
         self.comm.all_to_all(self.meta[1 + P:1 + 2*P], self.meta[1:1 + P])
         self.meta_host.copy_(self.meta, non_blocking=True)
@@ -507,6 +498,14 @@ def ship_boundary_positions(mesh, pos, margin):
     return from_prev, from_next
 
 
+def with_boundary_positions(mesh, pos, margin):
+    """`pos` followed by the ring neighbours' particles within `margin` of this domain's slab
+    (a supplier's cell list: rows 0..N_local-1 ARE the own particles, the sweep's `same`)"""
+    if mesh.nprocs == 1:
+        return pos
+    return torch.cat([pos] + list(ship_boundary_positions(mesh, pos, margin))).contiguous()
+
+
 def check_shortrange_fits(mesh, range_):
     cell = mesh.boxsize/mesh.gridsize
     slab_w = mesh.nxl*cell
@@ -526,28 +525,17 @@ def shortrange_kick(domain, particles, *, scale, range_, tilesize, tablesize, so
     particles in the boundary tiles") and runs the one-sided tile sweep for its own
     particles; because the sweep is one-sided no Δmom travels back (the reference
     returns it because its pair update is symmetric).  Returns Δmom (n, 3)."""
-    from . import commons, shortrange
+    from . import shortrange
     m = domain.mesh
-    L = m.boxsize
-    nt = int((L/1)/tilesize*(1 + commons.machine_ϵ))  # global tiling, species.py:3943-3950
-    if nt < 4:
-        raise lib.ConceptGPUError(
-            'The global gravity tiling needs to have at least 4 tiles across the box in every '
-            'direction (species.py:3971)')
+    nt, ext = shortrange.global_tiling(m.boxsize, tilesize)
     check_shortrange_fits(m, range_)
     pos = particles.view('pos')
-    n = pos.shape[0]
-    if m.nprocs == 1:
-        ghosts = []
-    else:
-        ghosts = list(ship_boundary_positions(m, pos, range_*(1 + 1e-9) + 1e-9*L))
-    supp = torch.cat([pos] + ghosts).contiguous()
-    ext = L/nt
+    supp = with_boundary_positions(m, pos, range_*(1 + 1e-9) + 1e-9*m.boxsize)
     cells_r = m.shortrange_cells(pos.contiguous(), nt, ext)
-    cells_s = m.shortrange_cells(supp, nt, ext) if ghosts else cells_r
+    cells_s = m.shortrange_cells(supp, nt, ext) if m.nprocs > 1 else cells_r
     table, maxr2 = shortrange.get_shortrange_table(softening, scale, range_, tablesize, kernel,
                                                    pos.device)
-    dmom = torch.zeros((n, 3), dtype=torch.float64, device=pos.device)
+    dmom = torch.zeros((pos.shape[0], 3), dtype=torch.float64, device=pos.device)
     m.shortrange_sweep_cells(cells_r, dmom, cells_s, nt, table, (tablesize - 1)/maxr2, range_**2,
                              factor)
     return dmom
@@ -677,18 +665,17 @@ class RegionParticles:
         start_out, count_out = self.tables[o]
         m.predict_regions(self.start, self.count, start_out)
         if self.multi:
-            lib.check(lib.raw().cg_set_emigrant_rows(m._ctx, _vp(self.rows), _vp(self.meta),
-                                                     self.rows.shape[0]))
-        lib.check(lib.raw().cg_set_momentum_sum(m._ctx, _vp(self.m2)))
+            m.set_emigrant_rows(self.rows, self.meta)
+        m.set_momentum_sum(self.m2)
         try:
             m.gather_kick_drift_scatter(self.pos[c], self.mom[c], self.ids[c], self.start, self.count,
                                         self.pos[o], self.mom[o], self.ids[o], start_out,
                                         count_out, diff_order, kick_factor, dt_over_mass,
                                         aux_in=self.aux[c], aux_out=self.aux[o])
         finally:
-            lib.check(lib.raw().cg_set_momentum_sum(m._ctx, None))
+            m.set_momentum_sum(None)
             if self.multi:
-                lib.check(lib.raw().cg_set_emigrant_rows(m._ctx, None, None, 0))
+                m.set_emigrant_rows(None, None)
         self.m2_host.copy_(self.m2, non_blocking=True)
         self.m2_event.record()
         self.m2_valid = True
@@ -697,9 +684,7 @@ class RegionParticles:
             # destinations and counts on the device, counts swapped with the peers, copy to
             # pinned memory started: nothing here waits for the GPU
             P = self.comm.world
-            lib.check(lib.raw().cg_emigrant_rows_dest(
-                m._ctx, _vp(self.rows), _vp(self.meta), self.rows.shape[0], _vp(self.rows_dest),
-                _vp(self.meta[1:])))
+            m.emigrant_rows_dest(self.rows, self.meta, self.rows_dest, self.meta[1:])
             self.comm.all_to_all(self.meta[1 + P:1 + 2*P], self.meta[1:1 + P])
             self.meta_host.copy_(self.meta, non_blocking=True)
             self.meta_event.record()
@@ -740,10 +725,9 @@ class RegionParticles:
         self.emigrants_total += cnt
         if m_in:
             c = self.cur
-            lib.check(lib.raw().cg_region_insert(
-                m._ctx, _vp(inc), m_in, _vp(self.start), _vp(self.count), _vp(self.pos[c]),
-                _vp(self.mom[c]), _vp(self.ids[c]) if self.has_ids else None,
-                _vp(self.aux[c]) if self.has_aux else None, self.cap))
+            m.region_insert(inc, self.start, self.count, self.pos[c], self.mom[c],
+                            self.ids[c] if self.has_ids else None,
+                            self.aux[c] if self.has_aux else None, self.cap)
 
     def snapshot(self):
         """The present order (which buffer set, its region tables): kick_drift_sort writes the

@@ -27,7 +27,7 @@ import warnings
 import torch
 
 from .commons import is_selected, machine_ϵ, ρ_vacuum
-from .lib import ConceptGPUError, check, raw
+from .lib import ConceptGPUError, _ptr, check, raw
 
 _L = raw()
 
@@ -45,11 +45,10 @@ def reset_steps():
 
 
 def _ptrs(tensors):
+    """an array of the tensors' addresses; None stays None, like lib._ptr"""
+    if tensors is None:
+        return None
     return (ctypes.c_void_p*len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
 def _state(component):
@@ -114,8 +113,7 @@ def maccormack_step(component, ᔑdt, steps, mc_step, halve=False):
     factor = -ᔑdt['a**(3*w_eff-2)', component.name]/Δx
     lo, hi = _neighbour_layers(component, src, 1)
     check(_L.cg_fluid_mc_step(
-        _ctx(component), _ptrs(src), _ptrs(list(lo)) if lo is not None else None,
-        _ptrs(list(hi)) if hi is not None else None, _ptrs(dst), component.gridsize,
+        _ctx(component), _ptrs(src), _ptrs(lo), _ptrs(hi), _ptrs(dst), component.gridsize,
         component.nxl, (ctypes.c_int*3)(*[int(s) for s in steps]), float(factor),
         float(p.light_speed**(-2)), int(mc_step), int(bool(halve))))
 
@@ -156,8 +154,7 @@ def correct_vacuum(component, mc_step, record=None):
     lo, hi = _neighbour_layers(component, var, 2)
     ft_lo, ft_hi = _neighbour_layers(component, [st.fac_time], 1)
     check(_L.cg_fluid_vacuum_gather(
-        ctx, _ptrs(var), _ptrs(list(lo)) if lo is not None else None,
-        _ptrs(list(hi)) if hi is not None else None, _ptr(st.fac_time),
+        ctx, _ptrs(var), _ptrs(lo), _ptrs(hi), _ptr(st.fac_time),
         _ptr(ft_lo[0]) if ft_lo is not None else None,
         _ptr(ft_hi[0]) if ft_hi is not None else None, _ptrs(st.Δ), component.gridsize,
         component.nxl, float(fac_smoothing)))
@@ -180,8 +177,7 @@ def finish(component, halve=True):
     values of all variables, and the starred and Δ buffers are left with no junk"""
     st = _state(component)
     check(_L.cg_fluid_mc_finish(_ctx(component), _ptrs(_grids(component)), _ptrs(st.starred),
-                                _ptrs(st.Δ) if st.Δ is not None else None,
-                                component.ϱ.numel(), int(bool(halve))))
+                                _ptrs(st.Δ), component.ϱ.numel(), int(bool(halve))))
 
 
 def maccormack(component, ᔑdt, a_next=-1, record=None):

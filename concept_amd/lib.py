@@ -178,3 +178,8 @@ def check(rc):
 
 def raw():
     return _lib
+
+
+def _ptr(t):
+    """a tensor's address as a pointer argument; None stays None (a null pointer)"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())

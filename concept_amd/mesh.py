@@ -9,13 +9,14 @@ interactions.interpolate_upstream; this module holds the steps it calls."""
 import ctypes
 import math
 import os
+import typing
 
 import numpy as np
 import torch
 
 from . import comm as _comm
 from . import lib
-from .lib import cg_params, check
+from .lib import _ptr, cg_params, check
 
 _L = lib.raw()
 _meshes = {}
@@ -23,8 +24,16 @@ _stage_buffers = {}  # (device, doubles) -> transpose staging buffer shared by t
 _cm_plans = {}
 
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
+class CellList(typing.NamedTuple):
+    """What shortrange_cells() makes.  A sub-step's list (nact, the active rows per cell, is
+    not None) has them first in every cell; rung, lowest: the rungs it was made for."""
+    order: torch.Tensor
+    offset: torch.Tensor
+    pos_sorted: torch.Tensor
+    nact: typing.Optional[torch.Tensor] = None
+    jumps_sorted: typing.Optional[torch.Tensor] = None
+    rung: typing.Optional[torch.Tensor] = None
+    lowest: int = 0
 
 
 class PotentialMesh:
@@ -562,17 +571,13 @@ class PotentialMesh:
         if kernel not in kernels:
             raise lib.ConceptGPUError(f'Softening kernel "{kernel}" not understood')
         gs = 0 if ewald_grid is None else int(ewald_grid.shape[0])
-        eg = None if ewald_grid is None else _ptr(ewald_grid)
-        if rungs is None:
-            f = r = rj = None
-            low = 0
-        else:
-            factors, rung, rung_jumped, low = rungs
+        factors, rung, rung_jumped, low = rungs if rungs is not None else (None, None, None, 0)
+        if rungs is not None:
             self._check_rungs(n_r, rung, rung_jumped)
-            f, r, rj = _ptr(factors), _ptr(rung), _ptr(rung_jumped)
         check(_L.cg_pp_kick(self._ctx, _ptr(pos_r), n_r, _ptr(dmom_r), _ptr(pos_s), n_s,
-                            int(bool(same)), eg, gs, float(softening), kernels[kernel],
-                            float(factor), f, r, rj, int(low)))
+                            int(bool(same)), _ptr(ewald_grid), gs, float(softening),
+                            kernels[kernel], float(factor), _ptr(factors), _ptr(rung),
+                            _ptr(rung_jumped), int(low)))
 
     def copy_from(self, other):
         """slab_downstream_subgroup[...] = slab_downstream (interactions.py:2242-2245): the
@@ -620,9 +625,7 @@ class PotentialMesh:
                 torch.zeros(8*self.ntiles, dtype=torch.int32, device=self.device))
 
     def predict_regions(self, start_in, count_in, start_out):
-        check(_L.cg_predict_regions(self._ctx, _ptr(start_in),
-                                    _ptr(count_in) if count_in is not None else None,
-                                    _ptr(start_out)))
+        check(_L.cg_predict_regions(self._ctx, _ptr(start_in), _ptr(count_in), _ptr(start_out)))
 
     def tile_order(self):
         """cg_tile_order_read: the heavy tiles the tile kernels run first (numpy uint32, in
@@ -641,13 +644,11 @@ class PotentialMesh:
                                   mom_out, ids_out, start_out, count_out, diff_order, factor,
                                   dt_over_mass, aux_in=None, aux_out=None):
         """cg_gather_kick_drift_scatter (see concept_gpu.h): nothing is written in place"""
-        opt = lambda t: _ptr(t) if t is not None else None
         check(_L.cg_gather_kick_drift_scatter(
-            self._ctx, _ptr(pos_in), _ptr(mom_in), _ptr(ids_in) if ids_in is not None else None,
-            _ptr(start_in), _ptr(count_in) if count_in is not None else None, _ptr(pos_out),
-            _ptr(mom_out), _ptr(ids_out) if ids_out is not None else None, _ptr(start_out),
-            _ptr(count_out), int(diff_order), float(factor), float(dt_over_mass), opt(aux_in),
-            opt(aux_out), int(pos_out.shape[0])))
+            self._ctx, _ptr(pos_in), _ptr(mom_in), _ptr(ids_in), _ptr(start_in), _ptr(count_in),
+            _ptr(pos_out), _ptr(mom_out), _ptr(ids_out), _ptr(start_out), _ptr(count_out),
+            int(diff_order), float(factor), float(dt_over_mass), _ptr(aux_in), _ptr(aux_out),
+            int(pos_out.shape[0])))
 
     def check_errors(self):
         flags = self.error_flags()
@@ -703,9 +704,8 @@ class PotentialMesh:
         if getattr(self, '_measure_buf', None) is None:
             self._measure_buf = torch.empty(2048 + 2, dtype=torch.float64, device=self.device)
         buf = self._measure_buf
-        check(_L.cg_measure_momentum_regions(
-            self._ctx, _ptr(mom), _ptr(start), _ptr(count) if count is not None else None,
-            _ptr(buf[2048:]), _ptr(buf)))
+        check(_L.cg_measure_momentum_regions(self._ctx, _ptr(mom), _ptr(start), _ptr(count),
+                                             _ptr(buf[2048:]), _ptr(buf)))
         s, m = buf[2048:].tolist()
         return s, m
 
@@ -714,10 +714,8 @@ class PotentialMesh:
         if tile_offset is None:
             tile_offset = self.new_tile_table()
         self._check_table(tile_offset)
-        check(_L.cg_sort_particles(
-            self._ctx, _ptr(pos), _ptr(mom), _ptr(ids) if ids is not None else None,
-            _ptr(pos_out), _ptr(mom_out), _ptr(ids_out) if ids_out is not None else None, n,
-            _ptr(tile_offset)))
+        check(_L.cg_sort_particles(self._ctx, _ptr(pos), _ptr(mom), _ptr(ids), _ptr(pos_out),
+                                   _ptr(mom_out), _ptr(ids_out), n, _ptr(tile_offset)))
         return tile_offset
 
     def permute_rows(self, perm, pairs):
@@ -745,21 +743,20 @@ class PotentialMesh:
         if tile_offset is None:
             tile_offset = self.new_tile_table()
         self._check_table(tile_offset)
-        check(_L.cg_drift_sort(
-            self._ctx, _ptr(pos), _ptr(mom), _ptr(ids) if ids is not None else None,
-            _ptr(pos_out), _ptr(mom_out), _ptr(ids_out) if ids_out is not None else None, n,
-            float(dt_over_mass), _ptr(tile_offset)))
+        check(_L.cg_drift_sort(self._ctx, _ptr(pos), _ptr(mom), _ptr(ids), _ptr(pos_out),
+                               _ptr(mom_out), _ptr(ids_out), n, float(dt_over_mass),
+                               _ptr(tile_offset)))
         return tile_offset
 
     # -- debug / parity -----------------------------------------------------
     # -- P3M short range -----------------------------------------------------------
     def shortrange_cells(self, pos, nt, tile_extent, rungs=None, sorted_jumps=False):
         """Cell list at half-tile granularity with the positions copied in cell order
-        (cg_shortrange_cells): (order, offset, pos_sorted).  rungs = (rung int8, rung_jumped
-        int8, lowest_active_rung) with lowest_active_rung > 0 makes the list of a sub-step
+        (cg_shortrange_cells): a CellList.  rungs = (rung int8, rung_jumped int8,
+        lowest_active_rung) with lowest_active_rung > 0 makes the list of a sub-step
         (cg_shortrange_cells_rungs): the particles on active rungs first in every cell, and the
-        tuple continues with (nact, rung_jumped_sorted, rung, lowest_active_rung) — what
-        shortrange_sweep_cells() needs to take the active rows as its receivers."""
+        fields from nact on are set — what shortrange_sweep_cells() needs to take the active
+        rows as its receivers."""
         n = self._check_particles(pos)
         order = torch.empty(max(n, 1), dtype=torch.int32, device=pos.device)
         offset = torch.empty(8*nt**3 + 1, dtype=torch.int32, device=pos.device)
@@ -777,11 +774,11 @@ class PotentialMesh:
             check(_L.cg_shortrange_cells_rungs(
                 self._ctx, _ptr(pos), n, int(nt), float(tile_extent), _ptr(rung),
                 _ptr(rung_jumped), int(lowest), _ptr(order), _ptr(offset), _ptr(pos_sorted),
-                _ptr(nact), _ptr(rj_sorted) if rj_sorted is not None else None))
-            return order, offset, pos_sorted, nact, rj_sorted, rung, int(lowest)
+                _ptr(nact), _ptr(rj_sorted)))
+            return CellList(order, offset, pos_sorted, nact, rj_sorted, rung, int(lowest))
         check(_L.cg_shortrange_cells(self._ctx, _ptr(pos), n, int(nt), float(tile_extent),
                                      _ptr(order), _ptr(offset), _ptr(pos_sorted)))
-        return order, offset, pos_sorted
+        return CellList(order, offset, pos_sorted)
 
     def shortrange_sweep_cells(self, cells_r, dmom_r, cells_s, nt, table, r2_index_scaling,
                                r2_max, factor, rungs=None, n_active=None):
@@ -794,6 +791,7 @@ class PotentialMesh:
         n = self._check_particles(dmom_r)
         if table.dtype != torch.float64 or not table.is_cuda:
             raise lib.ConceptGPUError('short-range table must be a float64 CUDA tensor')
+        cells_r, cells_s = CellList(*cells_r), CellList(*cells_s)  # (plain 3-tuples too)
         order_r, off_r, pos_r = cells_r[:3]
         _, off_s, pos_s = cells_s[:3]
         if rungs is None:
@@ -804,17 +802,16 @@ class PotentialMesh:
             return
         factors, rung, rung_jumped, lowest = rungs
         self._check_rungs(n, rung, rung_jumped)
-        if len(cells_r) > 3:
-            nact, rj_sorted, rung_list, lowest_list = cells_r[3:]
-            if rung_list.data_ptr() != rung.data_ptr() or lowest_list != int(lowest):
+        if cells_r.nact is not None:
+            if cells_r.rung.data_ptr() != rung.data_ptr() or cells_r.lowest != int(lowest):
                 raise lib.ConceptGPUError(
                     'shortrange_sweep_cells: the receivers\' list was made for other rungs')
             check(_L.cg_shortrange_sweep_cells_active(
-                self._ctx, _ptr(pos_r), _ptr(order_r), _ptr(off_r), _ptr(nact),
-                _ptr(rj_sorted) if rj_sorted is not None else None,
-                _ptr(dmom_r), _ptr(pos_s), _ptr(off_s), int(nt), _ptr(table), table.numel(),
-                float(r2_index_scaling), float(r2_max), _ptr(factors), _ptr(rung),
-                _ptr(rung_jumped), int(lowest), -1 if n_active is None else int(n_active)))
+                self._ctx, _ptr(pos_r), _ptr(order_r), _ptr(off_r), _ptr(cells_r.nact),
+                _ptr(cells_r.jumps_sorted), _ptr(dmom_r), _ptr(pos_s), _ptr(off_s), int(nt),
+                _ptr(table), table.numel(), float(r2_index_scaling), float(r2_max), _ptr(factors),
+                _ptr(rung), _ptr(rung_jumped), int(lowest),
+                -1 if n_active is None else int(n_active)))
             return
         check(_L.cg_shortrange_sweep_cells_rungs(
             self._ctx, _ptr(pos_r), _ptr(order_r), _ptr(off_r), _ptr(dmom_r), _ptr(pos_s),
@@ -834,8 +831,8 @@ class PotentialMesh:
         if rung is not None:
             self._check_rungs(n, rung)
         check(_L.cg_shortrange_tiles(self._ctx, _ptr(pos), n, int(nt), float(tile_extent),
-                                     _ptr(rung) if rung is not None else None, int(lowest),
-                                     _ptr(order), _ptr(offset), _ptr(pos_sorted)))
+                                     _ptr(rung), int(lowest), _ptr(order), _ptr(offset),
+                                     _ptr(pos_sorted)))
         return order, offset, pos_sorted
 
     def shortrange_stats(self, enable):
@@ -874,8 +871,7 @@ class PotentialMesh:
         check(_L.cg_shortrange_sparse(
             self._ctx, _ptr(pos_r), _ptr(active), int(k), _ptr(dmom_r), _ptr(pos_s),
             pos_s.shape[0], _ptr(table), table.numel(), float(r2_index_scaling), float(r2_max),
-            float(factor), _ptr(factors) if factors is not None else None,
-            _ptr(rung_jumped) if rung_jumped is not None else None))
+            float(factor), _ptr(factors), _ptr(rung_jumped)))
 
     # -- A16: momentum buffers and adaptive rungs -------------------------------------
     @staticmethod
@@ -886,13 +882,11 @@ class PotentialMesh:
 
     def dmom_nullify(self, dmom, rung=None, lowest_active_rung=0):
         n = self._check_particles(dmom)
-        check(_L.cg_dmom_nullify(self._ctx, _ptr(dmom), _ptr(rung) if rung is not None else None,
-                                 n, int(lowest_active_rung)))
+        check(_L.cg_dmom_nullify(self._ctx, _ptr(dmom), _ptr(rung), n, int(lowest_active_rung)))
 
     def dmom_apply(self, mom, dmom, rung=None, lowest_active_rung=0):
         n = self._check_particles(mom, dmom)
-        check(_L.cg_dmom_apply(self._ctx, _ptr(mom), _ptr(dmom),
-                               _ptr(rung) if rung is not None else None, n,
+        check(_L.cg_dmom_apply(self._ctx, _ptr(mom), _ptr(dmom), _ptr(rung), n,
                                int(lowest_active_rung)))
 
     def dmom_to_acc(self, dmom, rung, rung_jumped, lowest_active_rung, conversion_factors,
@@ -931,11 +925,10 @@ class PotentialMesh:
         self._check_rungs(n, rung, rung_jumped)
         tab = (ctypes.c_double*(3*N_rungs - 1))(*[float(v) for v in integrals_1]) if flag else None
         check(_L.cg_substep_begin(
-            self._ctx, _ptr(pos), _ptr(mom), _ptr(dmom) if dmom is not None else None, _ptr(rung),
+            self._ctx, _ptr(pos), _ptr(mom), _ptr(dmom), _ptr(rung),
             _ptr(rung_jumped), n, int(dt_over_mass is not None), float(dt_over_mass or 0.0),
             int(bool(flag)), int(lowest_active_rung), tab, float(rf_up), float(rf_down),
-            int(N_rungs), _ptr(any_out),
-            _ptr(counts_after) if counts_after is not None else None, int(bool(defer))))
+            int(N_rungs), _ptr(any_out), _ptr(counts_after), int(bool(defer))))
 
     def substep_flush(self):
         check(_L.cg_substep_flush(self._ctx))
@@ -950,9 +943,9 @@ class PotentialMesh:
         tab = ((ctypes.c_double*(3*N_rungs - 1))(*[float(v) for v in conversion_factors])
                if apply else None)
         check(_L.cg_substep_end(
-            self._ctx, _ptr(mom), _ptr(dmom) if dmom is not None else None, _ptr(rung),
+            self._ctx, _ptr(mom), _ptr(dmom), _ptr(rung),
             _ptr(rung_jumped), n, int(bool(apply)), int(lowest_active_rung), tab, int(N_rungs),
-            _ptr(counts) if counts is not None else None))
+            _ptr(counts)))
 
     def apply_rung_jumps(self, rung, rung_jumped, N_rungs):
         n = rung.numel()
@@ -995,10 +988,30 @@ class PotentialMesh:
         """gather_kick_tiled_prepare also lists (int64 row numbers into `idx`, their number into
         the one-element uint32/int32 tensor `count`) the particles its prepared drift takes out
         of this domain's slab; None, None switches the list off."""
-        if idx is None:
-            check(_L.cg_set_emigrant_list(self._ctx, None, None, 0))
-        else:
-            check(_L.cg_set_emigrant_list(self._ctx, _ptr(idx), _ptr(count), int(idx.numel())))
+        check(_L.cg_set_emigrant_list(self._ctx, _ptr(idx), _ptr(count),
+                                      0 if idx is None else int(idx.numel())))
+
+    def emigrant_dest(self, pos, mom, idx, count, dt_over_mass, dest_out, counts_out):
+        check(_L.cg_emigrant_dest(self._ctx, _ptr(pos), _ptr(mom), _ptr(idx), _ptr(count),
+                                  idx.numel(), float(dt_over_mass), _ptr(dest_out),
+                                  _ptr(counts_out)))
+
+    def set_emigrant_rows(self, rows, count):
+        """None, None switches the rows off"""
+        check(_L.cg_set_emigrant_rows(self._ctx, _ptr(rows), _ptr(count),
+                                      0 if rows is None else rows.shape[0]))
+
+    def emigrant_rows_dest(self, rows, count, dest_out, counts_out):
+        check(_L.cg_emigrant_rows_dest(self._ctx, _ptr(rows), _ptr(count), rows.shape[0],
+                                       _ptr(dest_out), _ptr(counts_out)))
+
+    def set_momentum_sum(self, out):
+        """Σ mom² of the particles gather_kick_drift_scatter kicks, into `out`; None: off"""
+        check(_L.cg_set_momentum_sum(self._ctx, _ptr(out)))
+
+    def region_insert(self, rows, start, count, pos, mom, ids, aux, capacity):
+        check(_L.cg_region_insert(self._ctx, _ptr(rows), rows.shape[0], _ptr(start), _ptr(count),
+                                  _ptr(pos), _ptr(mom), _ptr(ids), _ptr(aux), int(capacity)))
 
     def owner_rank(self, pos):
         n = self._check_particles(pos)

@@ -16,7 +16,7 @@ import torch
 
 from . import commons
 from .lib import ConceptGPUError
-from .mesh import get_mesh
+from .mesh import PotentialMesh, get_mesh
 
 _tables = {}
 PAIR_KEY = 'a**(-3*w_eff₀-3*w_eff₁-1)'
@@ -112,6 +112,106 @@ def deferred_active_checks():
         _deferred_checks -= 1
 
 
+def global_tiling(boxsize, tilesize, range_=None):
+    """(nt, tile_extent) of the global gravity tiling (species.py:3943-3950, :607-609), at
+    least 4 tiles across; range_: tiles narrower than this force range are refused too."""
+    nt = int((boxsize/1)/tilesize*(1 + commons.machine_ϵ))
+    if nt < 4:
+        raise ConceptGPUError(
+            'The global gravity tiling needs to have at least 4 tiles across the box in every '
+            'direction. Consider lowering shortrange_params["gravity"]["tilesize"].')
+    if range_ is not None and tilesize < range_*(1 - 1e-12):
+        raise ConceptGPUError('shortrange_params: tilesize must be at least the range')
+    return nt, boxsize/nt
+
+
+def sweep_form(rec, multi):
+    """Which sweep kicks the receiver `rec`, and the bound on its active rows where the sweep
+    takes one: 'plain' (no rungs, or every rung active: then the rung sweep over a plain list),
+    'sparse' (a handful, one domain: no cell list), 'by_cell' (by active receiver) or 'blocks'
+    (the jumped rungs copied into list order).  rungs_N counts the active rows without looking
+    (over all domains: an upper bound of this domain's, which is all the sweeps ask for).  The
+    list a receiver gets and the sweep over it both follow from this one answer."""
+    if not rec.use_rungs or rec.lowest_active_rung <= 0:
+        return 'plain', None
+    n_active = int(sum(rec.rungs_N[rec.lowest_active_rung:]))
+    if not multi and n_active <= PotentialMesh.SHORTRANGE_SPARSE_MAX:
+        return 'sparse', None
+    if n_active <= PotentialMesh.SHORTRANGE_BY_CELL_MAX*rec.N:
+        return 'by_cell', n_active
+    return 'blocks', None
+
+
+class _PairSweeps:
+    """The state of one component_component() call: the components' cell lists, the suppliers'
+    lists where they differ (several domains) and the rows of the sweeps without a list."""
+
+    def __init__(self, mesh, receivers, multi, nt, tile_extent, G_Newton, ᔑdt_rungs):
+        self.mesh, self.receivers, self.multi = mesh, receivers, multi
+        self.nt, self.tile_extent = nt, tile_extent
+        self.G_Newton, self.ᔑdt_rungs = G_Newton, ᔑdt_rungs
+        self.cells, self.supp_cells, self.sparse_rows = {}, {}, {}
+
+    def cells_of(self, c):
+        """the component's cell list (built when a sweep first asks for it: a sub-step that
+        kicks a handful of particles needs none)"""
+        if id(c) not in self.cells:
+            # (the sub-step's first pass over the particles, if the time loop left it to this
+            # list: run by the list's counting pass on the particles it bins)
+            taken = c.take_begin(self.mesh)
+            # a receiver's list of a sub-step has the active rows first in every cell; the
+            # sweep in blocks wants the jumped rung indices in list order too
+            rungs, in_blocks = None, False
+            if c.use_rungs and c in self.receivers:
+                rungs = (c.rung_indices, c.rung_indices_jumped, c.lowest_active_rung)
+                in_blocks = sweep_form(c, self.multi)[0] == 'blocks'
+            self.cells[id(c)] = self.mesh.shortrange_cells(c.pos, self.nt, self.tile_extent,
+                                                           rungs, in_blocks)
+            if taken:
+                c.begin_queued()
+            self.supp_cells.setdefault(id(c), self.cells[id(c)])
+        return self.cells[id(c)]
+
+    def sweep(self, rec, sup, table, scaling, r2_max):
+        mesh = self.mesh
+        # compute_factors (gravity.py:51-64): G*m_r*m_s*ᔑdt_rungs[...][k] per rung k
+        integrals = _pair_integrals(self.ᔑdt_rungs, rec, sup)
+        if not rec.use_rungs:
+            rc = self.cells_of(rec)
+            self.cells_of(sup)
+            mesh.shortrange_sweep_cells(
+                rc, rec.Δmom, self.supp_cells[id(sup)], self.nt, table, scaling, r2_max,
+                self.G_Newton*rec.mass*sup.mass*float(integrals[0]))
+            return
+        factors = commons.upload(self.G_Newton*rec.mass*sup.mass*integrals, rec.device)
+        form, n_active = sweep_form(rec, self.multi)
+        if form == 'sparse':
+            # the sub-steps for the highest rungs (main.py:1347-1624).  Which rows is found on
+            # the GPU, not trusted to the populations: every row on an active rung is swept
+            # (none claimed too: the kernels leave at once when no row is valid), and more
+            # than the sweep can take raise CG_ERR_ACTIVE_OVERFLOW
+            if id(rec) not in self.sparse_rows:
+                self.sparse_rows[id(rec)] = commons.sparse_rows(
+                    rec.rung_indices >= rec.lowest_active_rung, mesh.SHORTRANGE_SPARSE_MAX)
+            global sparse_sweeps
+            sparse_sweeps += 1
+            rec.flush_begin()
+            sup.flush_begin()
+            by_receiver_meshes[id(mesh)] = mesh
+            mesh.shortrange_sparse(rec.pos, self.sparse_rows[id(rec)], rec.Δmom, sup.pos,
+                                   table, scaling, r2_max, 0.0,
+                                   (factors, rec.rung_indices_jumped), overflow_slot=True)
+            return
+        self.cells_of(sup)
+        rc = self.cells_of(rec)
+        if form == 'by_cell':
+            by_receiver_meshes[id(mesh)] = mesh
+        mesh.shortrange_sweep_cells(
+            rc, rec.Δmom, self.supp_cells[id(sup)], self.nt, table, scaling, r2_max, 0.0,
+            (factors, rec.rung_indices, rec.rung_indices_jumped, rec.lowest_active_rung),
+            n_active)
+
+
 def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
     """Short-range gravity of every (receiver, supplier) component pair, accumulated
     into the components' Δmom buffers (the caller applies them, main.py:1253-1262)."""
@@ -119,14 +219,7 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
         raise ConceptGPUError(f'short-range force "{force}" is not built')
     p = receivers[0].params
     sr = commons.resolve_shortrange(p, gridsize)
-    nt = int((p.boxsize/1)/sr['tilesize']*(1 + commons.machine_ϵ))  # species.py:3943-3950
-    if nt < 4:
-        raise ConceptGPUError(
-            'The global gravity tiling needs to have at least 4 tiles across the box in every '
-            'direction. Consider lowering shortrange_params["gravity"]["tilesize"].')
-    if sr['tilesize'] < sr['range']*(1 - 1e-12):
-        raise ConceptGPUError('shortrange_params: tilesize must be at least the range')
-    tile_extent = p.boxsize/nt  # species.py:607-609
+    nt, tile_extent = global_tiling(p.boxsize, sr['tilesize'], sr['range'])
     mesh = get_mesh(gridsize, p.boxsize, p.nghosts, p.cell_centered, 2, receivers[0].device)
     involved = list({id(c): c for c in list(receivers) + list(suppliers)}.values())
     for c in involved:
@@ -136,71 +229,25 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
         # pass the time loop has left to this call's cell list)
         if 'Δmom' not in c._store.cols:
             c.Δmom = torch.zeros_like(c.mom)
-    # On several domains every supplier component is extended by the neighbour ranks'
-    # particles within the force range of this rank's slab (sendrecv_component,
-    # communication.py:847-1130: "supplier particles in the boundary tiles").  Positions only:
-    # the sweep is one-sided, every rank kicks its OWN receivers with their own rung factors,
-    # so neither the suppliers' rung indices nor any Δmom crosses the wire.
     multi = mesh.dist and mesh.nprocs > 1
-    cells, supp_pos, supp_cells = {}, {}, {}
+    sweeps = _PairSweeps(mesh, receivers, multi, nt, tile_extent, p.G_Newton, ᔑdt_rungs)
     if multi:
-        from .distributed import check_shortrange_fits, ship_boundary_positions
+        # On several domains every supplier component is extended by the neighbour ranks'
+        # particles within the force range of this rank's slab (sendrecv_component,
+        # communication.py:847-1130); positions only (see ship_boundary_positions).
+        from .distributed import check_shortrange_fits, with_boundary_positions
         # (components own their particles by the slabs of their own grids: the faces of two
         # components differ by less than half a cell of the coarser one)
         slack = max(c._store.mesh.boxsize/c._store.mesh.gridsize for c in involved)
         for c in involved:
             check_shortrange_fits(c._store.mesh, sr['range'] + slack)
-    build = mesh.shortrange_cells
-    def get_cells(c):
-        """the component's cell list (built when a sweep first asks for it: a sub-step that
-        kicks a handful of particles needs none, see sweep() below)"""
-        if id(c) not in cells:
-            # a sub-step (lowest active rung > 0): the particles on active rungs first in every
-            # cell, so that the sweep takes its receivers without looking at the rungs again
-            # (the sub-step's first pass over the particles, if the time loop left it to this
-            # list: run by the list's counting pass on the particles it bins)
-            taken = c.take_begin(mesh)
-            rungs = ((c.rung_indices, c.rung_indices_jumped, c.lowest_active_rung)
-                     if c.use_rungs and c in receivers else None)
-            # (many active receivers: the sweep goes in blocks and wants the jumped rung
-            # indices in list order)
-            in_blocks = (rungs is not None and c.lowest_active_rung > 0 and
-                         sum(c.rungs_N[c.lowest_active_rung:]) > mesh.SHORTRANGE_BY_CELL_MAX*c.N)
-            cells[id(c)] = build(c.pos, nt, tile_extent, rungs, in_blocks)
-            if taken:
-                c.begin_queued()
-            supp_cells.setdefault(id(c), cells[id(c)])
-        return cells[id(c)]
-    for c in involved:
-        # every involved component can act as supplier: s of sweep(r, s), and r of the
-        # reciprocal sweep(s, r) when s is also a receiver
-        if multi:
-            get_cells(c)
-            ghosts = ship_boundary_positions(c._store.mesh, c.pos,
-                                             sr['range']*(1 + 1e-9) + slack + 1e-9*p.boxsize)
-            # rows 0..N_local-1 ARE the component's own particles (the sweep's `same`
-            # convention), the ghosts follow
-            supp_pos[id(c)] = torch.cat([c.pos] + list(ghosts)).contiguous()
-            supp_cells[id(c)] = build(supp_pos[id(c)], nt, tile_extent)
-
-    def active_rows(rec):
-        """rows of the receiver's particles on active rungs when the populations say they are
-        few (one domain: rungs_N counts them without looking), else None.  What the rows are is
-        found on the GPU (commons.sparse_rows), not trusted to the populations: every row on an
-        active rung is swept, however many the populations claim, and more than the sweep can
-        take raise CG_ERR_ACTIVE_OVERFLOW"""
-        if multi or not rec.use_rungs or rec.lowest_active_rung <= 0:
-            return None
-        n_active = sum(rec.rungs_N[rec.lowest_active_rung:])
-        if n_active > mesh.SHORTRANGE_SPARSE_MAX:
-            return None
-        key_ = (id(rec), rec.lowest_active_rung)
-        if key_ not in sparse_rows:
-            sparse_rows[key_] = commons.sparse_rows(rec.rung_indices >= rec.lowest_active_rung,
-                                                    mesh.SHORTRANGE_SPARSE_MAX)
-        return sparse_rows[key_]
-    sparse_rows = {}
-    key = 'a**(-3*w_eff₀-3*w_eff₁-1)'
+        for c in involved:
+            # every involved component can act as supplier: s of sweep(r, s), and r of the
+            # reciprocal sweep(s, r) when s is also a receiver
+            sweeps.cells_of(c)
+            supp_pos = with_boundary_positions(
+                c._store.mesh, c.pos, sr['range']*(1 + 1e-9) + slack + 1e-9*p.boxsize)
+            sweeps.supp_cells[id(c)] = mesh.shortrange_cells(supp_pos, nt, tile_extent)
     done = set()
     for r in receivers:
         for s in suppliers:
@@ -213,56 +260,10 @@ def component_component(force, receivers, suppliers, ᔑdt_rungs, gridsize):
                                                 sr['tablesize'], p.softening_kernel, r.device)
             scaling = (sr['tablesize'] - 1)/maxr2  # gravity.py:288
             r2_max = sr['range']**2                # gravity.py:286
-            same = r is s
-
-            def sweep(rec, sup, same_):
-                # compute_factors (gravity.py:51-64): G*m_r*m_s*ᔑdt_rungs[...][k] per rung k
-                integrals = _pair_integrals(ᔑdt_rungs, rec, sup)
-                if rec.use_rungs:
-                    factors = commons.upload(p.G_Newton*rec.mass*sup.mass*integrals, rec.device)
-                    rows = active_rows(rec)
-                    if rows is not None:
-                        # the sub-steps for the highest rungs (main.py:1347-1624): a handful
-                        # of receivers against all suppliers, no cell list
-                        # (launched when the populations claim none too: the kernels leave at
-                        # once when no row is valid)
-                        global sparse_sweeps
-                        sparse_sweeps += 1
-                        rec.flush_begin()
-                        sup.flush_begin()
-                        by_receiver_meshes[id(mesh)] = mesh
-                        mesh.shortrange_sparse(rec.pos, rows, rec.Δmom,
-                                               supp_pos[id(sup)] if multi else sup.pos,
-                                               table, scaling, r2_max, 0.0,
-                                               (factors, rec.rung_indices_jumped),
-                                               overflow_slot=True)
-                        return
-                    get_cells(sup)
-                    rc = get_cells(rec)
-                    rungs = (factors, rec.rung_indices, rec.rung_indices_jumped,
-                             rec.lowest_active_rung)
-                    # few receivers on active rungs (rungs_N counts them — over all domains: an
-                    # upper bound of this domain's, which is all the sweep asks for): the sweep
-                    # by active receiver
-                    n_active = None
-                    if rec.lowest_active_rung > 0:
-                        n_active = int(sum(rec.rungs_N[rec.lowest_active_rung:]))
-                        if n_active > mesh.SHORTRANGE_BY_CELL_MAX*rec.N:
-                            n_active = None
-                    if n_active is not None:
-                        by_receiver_meshes[id(mesh)] = mesh
-                    mesh.shortrange_sweep_cells(rc, rec.Δmom, supp_cells[id(sup)], nt, table,
-                                                scaling, r2_max, 0.0, rungs, n_active)
-                else:
-                    rc = get_cells(rec)
-                    get_cells(sup)
-                    mesh.shortrange_sweep_cells(
-                        rc, rec.Δmom, supp_cells[id(sup)], nt, table, scaling, r2_max,
-                        p.G_Newton*rec.mass*sup.mass*float(integrals[0]))
-            sweep(r, s, same)
-            if not same and s in receivers:
+            sweeps.sweep(r, s, table, scaling, r2_max)
+            if r is not s and s in receivers:
                 # the reference kicks both partners of a pair (Δmom_s -= ..., gravity.py:341-349)
-                sweep(s, r, False)
+                sweeps.sweep(s, r, table, scaling, r2_max)
     # a sweep bounded by the populations met more active receivers than they said: an error,
     # not a kick silently lost (one wait for the GPU; the rung loop defers it)
     if not _deferred_checks and by_receiver_meshes.pop(id(mesh), None) is not None:

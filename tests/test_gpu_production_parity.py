@@ -262,7 +262,7 @@ def test_p3m_kick_vs_oracle(npart, N):
     assert np.abs(out - ref).max() <= 1e-12*big
     assert np.abs(out.sum(0)).max() <= 1e-10*big
     # cell list: a permutation, positions copied in cell order, every particle in its cell
-    order, offset, pos_sorted = cells
+    order, offset, pos_sorted = cells[:3]
     o = order.long()
     assert torch.equal(torch.sort(o)[0], torch.arange(n, device='cuda'))
     assert torch.equal(pos_sorted, p1[o])

@@ -397,7 +397,7 @@ def _spy(monkeypatch):
         # (dmom_r, cells_s, nt, table, r2_index_scaling, r2_max, factor, rungs, n_active)
         rungs = kw.get('rungs', a[7] if len(a) > 7 else None)
         n_active = kw.get('n_active', a[8] if len(a) > 8 else None)
-        if rungs is None or len(cells_r) == 3:
+        if rungs is None or cells_r.nact is None:
             taken.append('plain')
         else:
             taken.append('blocks' if n_active is None else 'by receiver')
