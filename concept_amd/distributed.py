@@ -729,6 +729,10 @@ class RegionParticles:
                             self.ids[c] if self.has_ids else None,
                             self.aux[c] if self.has_aux else None, self.cap)
 
+    def abandon_exchange(self):
+        """drop the exchange still pending from the last pass, its leavers with it"""
+        self.pending = False
+
     def snapshot(self):
         """The present order (which buffer set, its region tables): kick_drift_sort writes the
         other set only, so restore(snapshot) undoes a pass whose regions overflowed."""
@@ -737,7 +741,7 @@ class RegionParticles:
 
     def restore(self, snap):
         self.cur, self.start, self.count = snap
-        self.pending = False  # (the leavers of the undone pass are dropped with it)
+        self.abandon_exchange()   # (the leavers of the undone pass are dropped with it)
         self.m2_valid = False
 
     # -- bookkeeping ------------------------------------------------------------------

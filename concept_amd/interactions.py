@@ -38,6 +38,8 @@ PotentialInfo = collections.namedtuple(
     'PotentialInfo', ('gridsize', 'interpolation_order', 'deconvolve', 'interlace'))
 Deconvolve = collections.namedtuple('Deconvolve', ('upstream', 'downstream'))
 Interlace = collections.namedtuple('Interlace', ('upstream', 'downstream'))
+StreamingPlan = collections.namedtuple(   # what pm_streaming_plan() answers
+    'StreamingPlan', 'mesh gridsize deconv_order C long_range E force method')
 
 
 def get_potential_specs(force, method, receivers, suppliers):
@@ -176,8 +178,8 @@ def pm_streaming_plan(components):
         return None
     deconv = (int(bool(specs.deconvolve.upstream)) + int(bool(specs.deconvolve.downstream)))
     C, long_range, E = _potential_constants(p, 'gravity', specs.gridsize)
-    return {'mesh': mesh, 'gridsize': specs.gridsize, 'deconv_order': deconv*specs.interpolation_order,
-            'C': C, 'long_range': long_range, 'E': E, 'force': force, 'method': method}
+    return StreamingPlan(mesh, specs.gridsize, deconv*specs.interpolation_order, C, long_range, E,
+                         force, method)
 
 
 def _weighted_contribution(weight, mass, fft_factor, gridsize, boxsize):

@@ -171,7 +171,7 @@ class Component:
         is abandoned, its leavers with it."""
         from .distributed import ParticleStore
         if not collective:
-            rp.pending = False
+            rp.abandon_exchange()
         cols = rp.columns()
         old = self._store
         if 'ids' not in cols:   # (keep_order = False: the rows are renumbered as they lie)

@@ -10,7 +10,14 @@ reduced to what fixes the order of kicks and drifts:
 The time-step integrals ᔑdt[...] (main.get_time_step_integrals, integration.py:712-827)
 are inputs: the cosmological background and the Δt limiters are outside the path, the
 caller supplies plain numbers with the reference's keys."""
-from . import interactions, lib
+import collections
+import contextlib
+import math
+
+import numpy as np
+
+from . import commons, interactions, lib
+from .integration import Cosmology
 from .lib import ConceptGPUError
 
 
@@ -55,10 +62,15 @@ def timeloop(components, n_steps, integrals, rung_integrals=None, on_step=None):
     if on_step is None and not p3m and n_steps > 0:
         # nobody looks at the particles between a long-range kick and the drift after it: the
         # default PM configuration then takes both in one pass (same kicks and drifts, same
-        # order: K½ D K D ... K; drift bit-exact, kick to summation order)
+        # order: K½ D K D ... K as n_steps + 1 passes; drift bit-exact, kick to summation order)
         plan = interactions.pm_streaming_plan(components)
         if plan is not None:
-            return _timeloop_streaming(components, n_steps, integrals, plan)
+            with StreamingPM(plan, components) as stream:
+                for step in range(n_steps + 1):
+                    stream.kick_drift(integrals('init' if step == 0 else 'full'),
+                                      integrals('full') if step < n_steps else None,
+                                      f'in step {step}')
+            return
     kick_long(components, integrals('init'))
     if p3m:
         kick_short(components, rung_integrals('init'))
@@ -73,112 +85,122 @@ def timeloop(components, n_steps, integrals, rung_integrals=None, on_step=None):
             on_step(step)
 
 
-stream_replays = 0  # steps the streaming loop had to undo and take on the exact path
-
-
+stream_replays = 0  # passes the streaming loop had to undo and take on the exact path
 force_replays = 0   # test hook: that many of the next streaming passes are replayed
 
 
-def _streaming_pass(plan, components, rps, ᔑdt_kick, ᔑdt_drift, label='', drift_on_replay=True):
-    """One pass of the streaming form over particles kept in tile regions: every
-    component deposited from its regions (mesh.py:1512-1636), one Poisson solve
-    (interactions.py:2092-2118), then per component cg_gather_kick_drift_scatter with the kick's
-    ᔑdt['a**(-3*w_eff)', name] and the following drift's ᔑdt['a**(-2)'].  ᔑdt_drift None: a kick
-    only (the particles keep their places); ᔑdt_kick None: a drift only (kick factor 0: the
-    momenta pass through unchanged, bit for bit).  `rps` is updated in place.  Returns True if the
-    pass overflowed and was taken again on the exact path — the entries of `rps` are then NEW
-    objects (snapshots of the old ones no longer apply); with drift_on_replay=False the replay
-    takes the kick only and leaves the drift to the caller (a pass whose drift is a guess)."""
-    mesh = plan['mesh']
-    fft_factor = float(plan['gridsize'])**(-3)
-    p = components[0].params
-    if ᔑdt_kick is not None:
-        for k, (c, rp) in enumerate(zip(components, rps)):
-            rp.deposit(interactions._particle_contribution(
-                c, ᔑdt_kick, fft_factor, plan['gridsize'], p.boxsize), accumulate=k > 0)
-        fold = mesh.fold_ghosts_start()
-        mesh.poisson_solve(plan['deconv_order'], plan['C'], plan['long_range'], plan['E'],
-                           fold_finish=fold, fill=True)
-        plan['solved'] = True
-    elif not plan.get('solved'):
-        # a drift before any kick: the gather multiplies what the mesh holds by 0 — make sure
-        # that is a number
-        mesh.zero()
-        plan['solved'] = True
-    before = [rp.snapshot() for rp in rps]
-    for c, rp in zip(components, rps):
-        order = c.potential_differentiations[plan['force']][plan['method']]
-        Δt_over_mass = (ᔑdt_drift['a**(-2)']/c.mass) if ᔑdt_drift is not None else 0.0
-        factor = c.mass*(-ᔑdt_kick['a**(-3*w_eff)', c.name]) if ᔑdt_kick is not None else 0.0
-        rp.kick_drift_sort(order, factor, Δt_over_mass)
-    # On several domains: ship the leavers and seat the arrivals now (into the new buffer
-    # set), so that everything that can go wrong with this pass is known before the next one
-    # starts.
-    for rp in rps:
-        rp.finish_exchange()
-    # The regions of the new order were sized from the present populations; a (tile, bucket)
-    # that grew beyond that in one step — by the drift or by arrivals from other domains — or
-    # more leavers than the row buffer holds have dropped particles.  The pass and the exchange
-    # wrote the other buffer set only: undo them and take the step on the exact path (the
-    # potential is still on the mesh), then go on streaming.
-    flags = mesh.error_flags()   # reads AND clears the sticky bits
-    other = flags & ~(lib.CG_ERR_BUCKET_OVERFLOW | lib.CG_ERR_NOT_IN_TILE)
-    if other:
-        # e.g. CG_ERR_STALE_HISTOGRAM of a drift_sort on the replay path: that sort has
-        # dropped particles, nothing to recover from here
-        raise ConceptGPUError(f'streaming time loop: device error flags {other:#x} {label}')
-    overflow = bool(flags & (lib.CG_ERR_BUCKET_OVERFLOW | lib.CG_ERR_NOT_IN_TILE))
-    global force_replays
-    if force_replays > 0:   # (tests: treat this pass as overflowed)
-        force_replays -= 1
-        overflow = True
-    if mesh.comm is not None:
-        overflow = mesh.comm.any(overflow)
-    if overflow:
-        global stream_replays
-        stream_replays += 1
-        for i, c in enumerate(components):
-            rps[i].restore(before[i])
-            c.from_regions(rps[i])
-            if ᔑdt_kick is not None:
-                interactions._kick_particles(mesh, c, plan['force'], plan['method'],
-                                             ᔑdt_kick, ('a**(-3*w_eff)', 'component'))
-            if ᔑdt_drift is not None and drift_on_replay:
-                c.drift_sort(ᔑdt_drift, mesh=mesh)
-            rps[i] = c.to_regions(mesh)
-    return overflow
+class StreamingPM:
+    """The streaming form of the PM time loop and all of its state: the plan
+    (interactions.pm_streaming_plan), {component: its particles in tile regions
+    (distributed.RegionParticles)}, whether the mesh holds a solved potential, the snapshots the
+    last pass took.  A context manager: takes the particles, hands them back at the end."""
 
+    def __init__(self, plan, components):
+        self.plan, self.components, self.solved = plan, list(components), False
+        self._take()
 
-def _timeloop_streaming(components, n_steps, integrals, plan):
-    """timeloop() for the default PM configuration with the kick of one step and the drift of
-    the next fused: K½ D K D ... K as n_steps + 1 passes of _streaming_pass."""
-    mesh = plan['mesh']
-    rps = [c.to_regions(mesh) for c in components]
-    try:
-        for step in range(n_steps + 1):
-            ᔑdt_kick = integrals('init' if step == 0 else 'full')
-            ᔑdt_drift = integrals('full') if step < n_steps else None
-            _streaming_pass(plan, components, rps, ᔑdt_kick, ᔑdt_drift, f'in step {step}')
-    except BaseException:
-        # unwinding: hand the particles back without the collective part of from_regions (the
-        # other domains may not be unwinding), then let the exception travel
-        for c, rp in zip(components, rps):
+    def _take(self):
+        self.regions = {c: c.to_regions(self.plan.mesh) for c in self.components}
+        self.snapshots = None   # (those of earlier region objects describe buffers now gone)
+
+    def close(self, collective=True):
+        """Hand the particles back.  collective=False (unwinding; the other domains may not be):
+        without from_regions' collective part, and a failure for one component skips no other."""
+        regions, self.regions, self.snapshots = self.regions or {}, None, None
+        for c, rp in regions.items():
             try:
-                c.from_regions(rp, collective=False)
+                c.from_regions(rp, collective=collective)
             except Exception:
-                pass
-        raise
-    for c, rp in zip(components, rps):
-        c.from_regions(rp)
+                if collective:
+                    raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, exc_type, exc, traceback):
+        self.close(collective=exc_type is None)
+
+    @contextlib.contextmanager
+    def lend(self):
+        """the particles in the Components' own arrays for the length of the block (a dump)"""
+        self.close()
+        yield
+        self._take()
+
+    def undo(self):
+        """Put the regions back to where the last pass started (it wrote the other buffer set
+        only).  Not after a replay or a lend: the regions are new objects then."""
+        if self.snapshots is None:
+            raise ConceptGPUError('StreamingPM.undo(): the regions are not those of a last pass')
+        for rp, snap in zip(self.regions.values(), self.snapshots):
+            rp.restore(snap)
+        self.snapshots = None
+
+    def kick_drift(self, ᔑdt_kick, ᔑdt_drift, label='', drift_on_replay=True):
+        """One pass: every component deposited from its regions (mesh.py:1512-1636), one Poisson
+        solve (interactions.py:2092-2118), then per component cg_gather_kick_drift_scatter with
+        the kick's ᔑdt['a**(-3*w_eff)', name] and the following drift's ᔑdt['a**(-2)'].
+        ᔑdt_drift None: a kick only (the particles keep their places); ᔑdt_kick None: a drift
+        only (kick factor 0: the momenta pass through bit for bit).  Returns True if the pass
+        overflowed and was replayed on the exact path (drift_on_replay=False, for a guessed
+        drift: the replay takes the kick only)."""
+        global force_replays, stream_replays
+        plan, mesh, regions = self.plan, self.plan.mesh, self.regions
+        if ᔑdt_kick is not None:
+            fft_factor, boxsize = float(plan.gridsize)**(-3), self.components[0].params.boxsize
+            for k, (c, rp) in enumerate(regions.items()):
+                rp.deposit(interactions._particle_contribution(
+                    c, ᔑdt_kick, fft_factor, plan.gridsize, boxsize), accumulate=k > 0)
+            fold = mesh.fold_ghosts_start()
+            mesh.poisson_solve(plan.deconv_order, plan.C, plan.long_range, plan.E,
+                               fold_finish=fold, fill=True)
+        elif not self.solved:
+            mesh.zero()   # a drift before any kick: the gather multiplies it by 0, a number then
+        self.solved = True
+        self.snapshots = [rp.snapshot() for rp in regions.values()]
+        for c, rp in regions.items():
+            order = c.potential_differentiations[plan.force][plan.method]
+            Δt_over_mass = (ᔑdt_drift['a**(-2)']/c.mass) if ᔑdt_drift is not None else 0.0
+            factor = c.mass*(-ᔑdt_kick['a**(-3*w_eff)', c.name]) if ᔑdt_kick is not None else 0.0
+            rp.kick_drift_sort(order, factor, Δt_over_mass)
+        # Several domains: ship the leavers and seat the arrivals now (into the new buffer set),
+        # so that all that can go wrong with this pass is known before the next one starts.
+        for rp in regions.values():
+            rp.finish_exchange()
+        # The new regions were sized from the present populations; a (tile, bucket) that outgrew
+        # that in one step (the drift, arrivals from other domains) or more leavers than the row
+        # buffer holds have dropped particles.  Pass and exchange wrote the other buffer set only:
+        # undo them, take the step on the exact path (the potential is still on the mesh), go on.
+        recoverable = lib.CG_ERR_BUCKET_OVERFLOW | lib.CG_ERR_NOT_IN_TILE
+        flags = mesh.error_flags()   # reads AND clears the sticky bits
+        if flags & ~recoverable:
+            # (e.g. CG_ERR_STALE_HISTOGRAM: a drift_sort of the replay path has dropped particles)
+            raise ConceptGPUError('streaming time loop: device error flags '
+                                  f'{flags & ~recoverable:#x} {label}')
+        overflow = bool(flags & recoverable)
+        if force_replays > 0:   # (tests: treat this pass as overflowed)
+            force_replays -= 1
+            overflow = True
+        if mesh.comm is not None:
+            overflow = mesh.comm.any(overflow)
+        if overflow:
+            stream_replays += 1
+            for c, snap in zip(self.components, self.snapshots):
+                regions[c].restore(snap)
+                c.from_regions(regions[c])
+                if ᔑdt_kick is not None:
+                    interactions._kick_particles(mesh, c, plan.force, plan.method, ᔑdt_kick,
+                                                 ('a**(-3*w_eff)', 'component'))
+                if ᔑdt_drift is not None and drift_on_replay:
+                    c.drift_sort(ᔑdt_drift, mesh=mesh)
+                regions[c] = c.to_regions(mesh)
+            self.snapshots = None   # (of the region objects just replaced)
+        return overflow
 
 
 # ---------------------------------------------------------------------------
 # Adaptive rungs: the reference's kick_short / driftkick_short state machine
 # ---------------------------------------------------------------------------
-import numpy as np
-
-from . import commons
-
 PAIR_KEY = 'a**(-3*w_eff₀-3*w_eff₁-1)'
 
 
@@ -583,11 +605,6 @@ class RungStepper:
 # ---------------------------------------------------------------------------
 # main.timeloop() with the cosmic clock: base time step control, synchronisations, dumps
 # ---------------------------------------------------------------------------
-import collections
-import math
-
-from .integration import Cosmology
-
 DumpTime = collections.namedtuple('DumpTime', ('time_param', 't', 'a'))
 ထ = math.inf
 
@@ -627,7 +644,7 @@ class Timeloop(RungStepper):
     Streaming (streaming = None: whenever the configuration allows; False: never).  The default
     PM configuration (interactions.pm_streaming_plan) with no short-range force takes every long
     kick together with the drift that follows it as ONE pass over the particles (DESIGN.md
-    §4a).  The drift's interval is known when the kick is asked for: inside a segment K½ D K D
+    §4).  The drift's interval is known when the kick is asked for: inside a segment K½ D K D
     ... K it depends on t, Δt and the dump times only — what get_base_timestep_size measures
     after kick n decides the LENGTH OF KICK n + 1 and whether a synchronisation follows, never
     drift n + 1 — and the last kick of a segment is followed by no drift.  The one exception is
@@ -692,7 +709,8 @@ class Timeloop(RungStepper):
         self.Δt = 0.0
         self.history = []   # (time_step, t, a, Δt) at the beginning of every time step
         self.streaming = streaming
-        self._plan = self._rps = self._spec = self._next_drift = None
+        # (the StreamingPM while the loop streams; kick ᔑdt and drift interval of its guess)
+        self.stream = self._guess = self._next_drift = None
         self.stream_passes = self.stream_wrong_guesses = 0
         dumpers = []
         if on_dump is None and p.output_dirs.get('snapshot') and (
@@ -746,23 +764,20 @@ class Timeloop(RungStepper):
         return self.cosmo.get_time_step_integrals(t_start, t_end, self.components, (key,))[key]
 
     # -- the streaming form of the loop ----------------------------------------------------
-    def _stream_begin(self):
+    def _begin_streaming(self):
         if self.streaming is False or self._shortrange_interactions():
             return
         plan = interactions.pm_streaming_plan(self.components)
-        if plan is None:
-            if self.streaming:
-                raise ConceptGPUError('Timeloop(streaming=True): not the default PM '
-                                      'configuration (interactions.pm_streaming_plan)')
-            return
-        self._plan = plan
-        self._rps = [c.to_regions(plan['mesh']) for c in self.components]
+        if plan is not None:
+            self.stream = StreamingPM(plan, self.components)
+        elif self.streaming:
+            raise ConceptGPUError('Timeloop(streaming=True): not the default PM '
+                                  'configuration (interactions.pm_streaming_plan)')
 
-    def _stream_end(self, collective=True):
-        if self._rps is not None:
-            for c, rp in zip(self.components, self._rps):
-                c.from_regions(rp, collective=collective)
-        self._plan = self._rps = self._spec = None
+    def _end_streaming(self, collective=True):
+        stream, self.stream, self._guess = self.stream, None, None
+        if stream is not None:
+            stream.close(collective)
 
     def _predict_drift(self, step_type, Δt, sync_time, dump_time):
         """the drift that follows the long kick about to be asked for, as (t_start, t_end), or
@@ -780,47 +795,36 @@ class Timeloop(RungStepper):
         return (t, t_end) if t_end != t else None
 
     def kick_long(self, Δt, sync_time, step_type):
-        if self._rps is None:
+        if self.stream is None:
             return super().kick_long(Δt, sync_time, step_type)
         t_start = self.t
         t_end = self._clip(t_start + (Δt/2 if step_type == 'init' else Δt), Δt, sync_time)
         if t_start == t_end:
             return
-        ᔑdt = self.integrals(t_start, t_end)
-        drift = self._next_drift
-        before = [rp.snapshot() for rp in self._rps]
-        replayed = _streaming_pass(self._plan, self.components, self._rps, ᔑdt,
-                                   self.integrals(*drift) if drift is not None else None,
-                                   f'at t = {t_start}', drift_on_replay=False)
+        ᔑdt, drift = self.integrals(t_start, t_end), self._next_drift
+        replayed = self.stream.kick_drift(
+            ᔑdt, self.integrals(*drift) if drift is not None else None, f'at t = {t_start}',
+            drift_on_replay=False)
         self.stream_passes += 1
-        if replayed:
-            # the pass overflowed: the kick has been taken on the exact path, the drift not at
-            # all, and the region objects are new ones — `before` describes buffers that no
-            # longer exist.  No guess is outstanding: the loop's next driftkick_short() takes
-            # its drift as a pass of its own.
-            self._spec = None
-        else:
-            self._spec = {'kick': ᔑdt, 'drift': drift, 'before': before}
+        # (a replay took the kick and no drift: the next driftkick_short() takes its drift itself)
+        self._guess = (ᔑdt, drift) if drift is not None and not replayed else None
 
     def driftkick_short(self, Δt, sync_time):
-        if self._rps is None:
+        if self.stream is None:
             return super().driftkick_short(Δt, sync_time)
         t_start = self.t
         t_end = self._clip(t_start + Δt, Δt, sync_time)
-        spec, self._spec = self._spec, None
-        if spec is not None and spec['drift'] is not None:
-            if t_start == t_end or spec['drift'] != (t_start, t_end):
-                # the guess was wrong: undo the pass, take the kick alone
-                self.stream_wrong_guesses += 1
-                for rp, snap in zip(self._rps, spec['before']):
-                    rp.restore(snap)
-                _streaming_pass(self._plan, self.components, self._rps, spec['kick'], None)
-            else:
+        guess, self._guess = self._guess, None
+        if guess is not None:
+            if t_start != t_end and guess[1] == (t_start, t_end):
                 return   # this drift was taken with the kick before it
+            # the guess was wrong: undo the pass, take the kick alone
+            self.stream_wrong_guesses += 1
+            self.stream.undo()
+            self.stream.kick_drift(guess[0], None)
         if t_start == t_end:
             return
-        _streaming_pass(self._plan, self.components, self._rps, None,
-                        self.integrals(t_start, t_end))
+        self.stream.kick_drift(None, self.integrals(t_start, t_end))
 
     # -- main.prepare_for_output (main.py:2188-2310), the dump times -----------------------
     def dump_times(self):
@@ -902,8 +906,8 @@ class Timeloop(RungStepper):
         """rms velocity of a component, measured once per call of get_base_timestep_size
         (on the regions when the loop streams); a static component counts as just above 0"""
         if c not in state['v_rms']:
-            rp = self._rps[self.components.index(c)] if self._rps is not None else None
-            state['v_rms'][c] = measure(c, 'v_rms', state['a'], rp)
+            regions = self.stream.regions[c] if self.stream is not None else None
+            state['v_rms'][c] = measure(c, 'v_rms', state['a'], regions)
         v_rms = state['v_rms'][c]
         return commons.machine_ϵ if v_rms < commons.machine_ϵ else v_rms
 
@@ -1003,13 +1007,8 @@ class Timeloop(RungStepper):
 
     def _dump(self, dump_time):
         if self.on_dump is not None:
-            streaming = self._rps is not None
-            if streaming:   # the callback looks at the Components' own arrays
-                for c, rp in zip(self.components, self._rps):
-                    c.from_regions(rp)
-            self.on_dump(self, dump_time)
-            if streaming:
-                self._rps = [c.to_regions(self._plan['mesh']) for c in self.components]
+            with self.stream.lend() if self.stream is not None else contextlib.nullcontext():
+                self.on_dump(self, dump_time)
 
     def _dumper(self, times, output_dir, output_base, write):
         """The on_dump callback of the three dumpers below: at a dump time that is among
@@ -1110,14 +1109,9 @@ class Timeloop(RungStepper):
         try:
             self._run()
         except BaseException:
-            # unwinding: hand the particles back without the collective part (the other
-            # domains may not be unwinding), then let the exception travel
-            try:
-                self._stream_end(collective=False)
-            except Exception:
-                pass
+            self._end_streaming(collective=False)   # (unwinding: StreamingPM.close)
             raise
-        self._stream_end()
+        self._end_streaming()
 
     def _run(self):
         cosmo, components = self.cosmo, self.components
@@ -1129,7 +1123,7 @@ class Timeloop(RungStepper):
             dump_times.pop(0)
             if not dump_times:
                 return
-        self._stream_begin()
+        self._begin_streaming()
         self.initial_fac_times.add(cosmo.t)
         Δt_max, bottleneck = self.get_base_timestep_size()
         Δt_begin = Δt_max

@@ -229,7 +229,7 @@ def test_timeloop_overflow_of_the_speculative_pass(golden):
                 loop.params.Δa_max_early *= 0.3
                 loop.params.Δa_max_late *= 0.3
                 # the next pass is the init kick after the synchronisation this causes
-                if loop._rps is not None:
+                if loop.stream is not None:
                     stepper.force_replays = 1
         loop = stepper.Timeloop([c], on_step=on_step, streaming=streaming)
         replays = stepper.stream_replays
