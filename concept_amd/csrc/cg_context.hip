@@ -208,16 +208,16 @@ __global__ __launch_bounds__(256) void k_dist_rows(double2 *__restrict__ slab,
     }
 }
 
-static int dist_generic(cg_ctx *c, int what, double2 *buf, int deconv_order, double C,
+static int dist_generic(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, double C,
                         int long_range, double E, i64 layer0, i64 nlayers) {
     const i64 cp = c->pad / 2, N = c->N, nxl = c->xmap.nxl, JB = N / c->p.nprocs;
     if (nlayers < 0) nlayers = nxl - layer0;
     double2 *m = (double2 *)c->mesh0;
-    if (what == 0 || what == 1) {
+    if (op == SlabOp::ZYForward || op == SlabOp::ZYBackward) {
         rocfft_plan pf, pb;
         if (dist_plans_2d(c, nlayers, &pf, &pb)) return 1;
         void *io[1] = {(void *)(m + layer0 * c->ny * cp)};
-        if (what == 0) {
+        if (op == SlabOp::ZYForward) {
             if (dist_work(c, pf)) return 1;
             CG_FFT(rocfft_execute(pf, io, nullptr, c->dist_plans->info));
             hipLaunchKernelGGL((k_dist_rows<true>), dim3((unsigned)(nlayers * N)), dim3(256), 0,
@@ -238,11 +238,11 @@ static int dist_generic(cg_ctx *c, int what, double2 *buf, int deconv_order, dou
     }
     if (dist_plans_x(c)) return 1;
     void *io[1] = {(void *)buf};
-    if (what == 2 || what == 3) {
+    if (op == SlabOp::XSolve || op == SlabOp::XForward) {
         if (dist_work(c, c->dist_plans->x_fwd)) return 1;
         CG_FFT(rocfft_execute(c->dist_plans->x_fwd, io, nullptr, c->dist_plans->info));
     }
-    if (what == 2) {
+    if (op == SlabOp::XSolve) {
         // the Poisson / deconvolution kernel on the rows of this domain (the Fourier view of
         // cg_dist_bind_fourier, for the duration of the call on `buf`)
         double2 *four = c->four;
@@ -256,11 +256,19 @@ static int dist_generic(cg_ctx *c, int what, double2 *buf, int deconv_order, dou
         c->four = four, c->f_si = f_si, c->f_j0 = f_j0, c->f_nj = f_nj;
         if (rc) return rc;
     }
-    if (what == 2 || what == 4) {
+    if (op == SlabOp::XSolve || op == SlabOp::XBackward) {
         if (dist_work(c, c->dist_plans->x_bwd)) return 1;
         CG_FFT(rocfft_execute(c->dist_plans->x_bwd, io, nullptr, c->dist_plans->info));
     }
     return 0;
+}
+
+// one piece of the slab transform on the context's backend
+static int dist_fft(cg_ctx *c, SlabOp op, const double *buf, int deconv_order, double C,
+                    int long_range, double E, i64 layer0, i64 nlayers) {
+    double2 *b = (double2 *)const_cast<double *>(buf);
+    return (c->custom_fft ? cgk_fft_dist : dist_generic)(c, op, b, deconv_order, C, long_range, E,
+                                                         layer0, nlayers);
 }
 
 static void dist_plans_destroy(cg_ctx *c) {
@@ -398,6 +406,11 @@ static int ctx_init(cg_ctx *c) {
         const char *env = getenv("CONCEPT_GPU_FFT");
         bool force_rocfft = env && std::string(env) == "rocfft";
         c->custom_fft = cgk_fft_supported(c->N) && !force_rocfft;
+        // what the hand-written passes' plans depend on, read once here (cg_fft_plan.h)
+        CG_HIP(hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, p->device));
+        CG_CHECK(c->ncu > 0, "cg_create: device %d reports %d compute units", p->device, c->ncu);
+        env = getenv("CONCEPT_GPU_FFT_SPLIT");
+        c->fft_split = env ? atoi(env) : 1;
     }
     if (c->custom_fft) {
         std::vector<double> tw(2 * c->N);
@@ -666,7 +679,7 @@ extern "C" int cg_poisson_forward(cg_ctx *c, int deconv_order, double C, int lon
     CG_CHECK(deconv_order >= 0 && deconv_order <= 8, "cg_poisson_forward: deconv_order %d",
              deconv_order);
     if (c->custom_fft) {
-        if (cgk_fft(c, 0, 0, 0.0, 0, 0.0)) return 1;
+        if (cgk_fft(c, FftOp::Forward, 0, 0.0, 0, 0.0)) return 1;
     } else {
         CG_FFT(rocfft_execution_info_set_stream(c->info_fwd, c->stream));
         void *buf[1] = {c->mesh};
@@ -687,7 +700,7 @@ extern "C" int cg_poisson_kernel(cg_ctx *c, int deconv_order, double C, int long
 extern "C" int cg_poisson_backward(cg_ctx *c) {
     CG_CHECK(c, "cg_poisson_backward: null context");
     CG_CHECK(c->p.nprocs == 1, "cg_poisson_backward: single-domain entry point; x-slab domains use cg_dist_fft_*");
-    if (c->custom_fft) return cgk_fft(c, 1, 0, 0.0, 0, 0.0);
+    if (c->custom_fft) return cgk_fft(c, FftOp::Backward, 0, 0.0, 0, 0.0);
     CG_FFT(rocfft_execution_info_set_stream(c->info_bwd, c->stream));
     void *buf[1] = {c->mesh};
     CG_FFT(rocfft_execute(c->plan_bwd, buf, nullptr, c->info_bwd));
@@ -700,7 +713,7 @@ extern "C" int cg_poisson_solve(cg_ctx *c, int deconv_order, double C, int long_
     CG_CHECK(deconv_order >= 0 && deconv_order <= 8, "cg_poisson_solve: deconv_order %d",
              deconv_order);
     // hand-written FFT: the k-space kernel is fused into the x pass (5 passes in all)
-    if (c->custom_fft) return cgk_fft(c, 2, deconv_order, C, long_range, E);
+    if (c->custom_fft) return cgk_fft(c, FftOp::Solve, deconv_order, C, long_range, E);
     if (cg_poisson_forward(c, deconv_order, C, long_range, E, 1)) return 1;
     return cg_poisson_backward(c);
 }
@@ -1294,8 +1307,7 @@ extern "C" int cg_layers_write(cg_ctx *c, int64_t layer0, int64_t nlayers, const
 
 extern "C" int cg_dist_fft_forward(cg_ctx *c, double *send_buf) {
     CG_CHECK(c && send_buf, "cg_dist_fft_forward: null argument");
-    if (!c->custom_fft) return dist_generic(c, 0, (double2 *)send_buf, 0, 0.0, 0, 0.0, 0, -1);
-    return cgk_fft_dist_forward(c, send_buf, 0, -1);
+    return dist_fft(c, SlabOp::ZYForward, send_buf, 0, 0.0, 0, 0.0, 0, -1);
 }
 extern "C" int cg_dist_fft_forward_layers(cg_ctx *c, double *send_buf, int64_t layer0,
                                           int64_t nlayers) {
@@ -1303,18 +1315,14 @@ extern "C" int cg_dist_fft_forward_layers(cg_ctx *c, double *send_buf, int64_t l
     CG_CHECK(layer0 >= 0 && nlayers >= 1 && layer0 + nlayers <= c->xmap.nxl,
              "cg_dist_fft_forward_layers: layers [%lld, %lld) outside the %lld owned ones",
              (long long)layer0, (long long)(layer0 + nlayers), (long long)c->xmap.nxl);
-    if (!c->custom_fft)
-        return dist_generic(c, 0, (double2 *)send_buf, 0, 0.0, 0, 0.0, layer0, nlayers);
-    return cgk_fft_dist_forward(c, send_buf, layer0, nlayers);
+    return dist_fft(c, SlabOp::ZYForward, send_buf, 0, 0.0, 0, 0.0, layer0, nlayers);
 }
 extern "C" int cg_dist_fft_xsolve(cg_ctx *c, double *buf, int deconv_order, double C,
                                   int long_range, double E) {
     CG_CHECK(c && buf, "cg_dist_fft_xsolve: null argument");
     CG_CHECK(deconv_order >= 0 && deconv_order <= 8, "cg_dist_fft_xsolve: deconv_order %d",
              deconv_order);
-    if (!c->custom_fft)
-        return dist_generic(c, 2, (double2 *)buf, deconv_order, C, long_range, E, 0, -1);
-    return cgk_fft_dist_xsolve(c, buf, deconv_order, C, long_range, E);
+    return dist_fft(c, SlabOp::XSolve, buf, deconv_order, C, long_range, E, 0, -1);
 }
 extern "C" int cg_dist_bind_fourier(cg_ctx *c, double *buf) {
     CG_CHECK(c, "cg_dist_bind_fourier: null context");
@@ -1336,9 +1344,7 @@ extern "C" int cg_dist_bind_fourier(cg_ctx *c, double *buf) {
 }
 extern "C" int cg_dist_fft_x(cg_ctx *c, double *buf, int inverse) {
     CG_CHECK(c && buf, "cg_dist_fft_x: null argument");
-    if (!c->custom_fft)
-        return dist_generic(c, inverse ? 4 : 3, (double2 *)buf, 0, 0.0, 0, 0.0, 0, -1);
-    return cgk_fft_dist_x(c, buf, inverse ? 1 : 0);
+    return dist_fft(c, inverse ? SlabOp::XBackward : SlabOp::XForward, buf, 0, 0.0, 0, 0.0, 0, -1);
 }
 extern "C" int cg_emigrant_dest(cg_ctx *c, const double *pos, const double *mom,
                                 const int64_t *idx, const uint32_t *count, int64_t cap,
@@ -1349,9 +1355,7 @@ extern "C" int cg_emigrant_dest(cg_ctx *c, const double *pos, const double *mom,
 }
 extern "C" int cg_dist_fft_backward(cg_ctx *c, const double *recv_buf) {
     CG_CHECK(c && recv_buf, "cg_dist_fft_backward: null argument");
-    if (!c->custom_fft)
-        return dist_generic(c, 1, (double2 *)const_cast<double *>(recv_buf), 0, 0.0, 0, 0.0, 0, -1);
-    return cgk_fft_dist_backward(c, recv_buf, 0, -1);
+    return dist_fft(c, SlabOp::ZYBackward, recv_buf, 0, 0.0, 0, 0.0, 0, -1);
 }
 extern "C" int cg_dist_fft_backward_layers(cg_ctx *c, const double *recv_buf, int64_t layer0,
                                            int64_t nlayers) {
@@ -1359,10 +1363,7 @@ extern "C" int cg_dist_fft_backward_layers(cg_ctx *c, const double *recv_buf, in
     CG_CHECK(layer0 >= 0 && nlayers >= 1 && layer0 + nlayers <= c->xmap.nxl,
              "cg_dist_fft_backward_layers: layers [%lld, %lld) outside the %lld owned ones",
              (long long)layer0, (long long)(layer0 + nlayers), (long long)c->xmap.nxl);
-    if (!c->custom_fft)
-        return dist_generic(c, 1, (double2 *)const_cast<double *>(recv_buf), 0, 0.0, 0, 0.0,
-                            layer0, nlayers);
-    return cgk_fft_dist_backward(c, recv_buf, layer0, nlayers);
+    return dist_fft(c, SlabOp::ZYBackward, recv_buf, 0, 0.0, 0, 0.0, layer0, nlayers);
 }
 extern "C" int cg_owner_rank(cg_ctx *c, const double *pos, int64_t n, int32_t *owner_out) {
     if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)

@@ -957,11 +957,12 @@ __global__ __launch_bounds__(NT) void k_fft_strided_h(const double2 *__restrict_
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
+#include "cg_fft_plan.h"  // chunks of layers and the form of a strided pass: plain arithmetic
+
 template <int LOGN>
-static int run_z(cg_ctx *c, bool inverse, i64 layer0 = 0, i64 nlayers = -1) {
+static int run_z(cg_ctx *c, bool inverse, i64 layer0, i64 nlayers) {
     constexpr int N = 1 << LOGN;
     constexpr int NT = (N / 8) < 64 ? 64 : ((N / 8) > 256 ? 256 : (N / 8));
-    if (nlayers < 0) nlayers = c->xmap.nxl;  // owned layers only
     unsigned rows = (unsigned)(nlayers * c->N);
     double *base = c->mesh0 + layer0 * c->ny * c->pad;
     if (!inverse)
@@ -974,268 +975,132 @@ static int run_z(cg_ctx *c, bool inverse, i64 layer0 = 0, i64 nlayers = -1) {
     return 0;
 }
 
-template <int LOGN, int MODE, int W, bool R16>
-static int run_strided_r(cg_ctx *c, const double2 *src, double2 *dst, PencilMap smap,
-                         PencilMap dmap, i64 nouter, i64 o_off, const KspaceParams &P) {
-    constexpr int N = 1 << LOGN;
-    // lanes: radix 4: N*W/8 (two butterflies per lane and pass); radix 16: N*W/16 (one);
-    // 64..1024
-    constexpr int NTW = N * W / (R16 ? 16 : 8);
-    constexpr int NT = NTW < 64 ? 64 : (NTW > 1024 ? 1024 : NTW);
-    const int nkb = (int)((c->N / 2 + 1 + W - 1) / W);
-    size_t lds = sizeof(double2) * N * W;
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        CG_HIP(hipGetDeviceProperties(&prop, c->p.device));
-        ncu = prop.multiProcessorCount;
+// Launch KERN with the numbers of the choice.  More than 64 KB of dynamic LDS have to be allowed
+// once per kernel and device (one process may drive several).
+template <auto KERN, typename... Args>
+static int launch_pass(cg_ctx *c, const StridedChoice &s, Args... args) {
+    static bool allowed[64] = {};
+    bool &done = allowed[c->p.device & 63];
+    if (!done && s.lds > 64 * 1024) {
+        CG_HIP(hipFuncSetAttribute((const void *)KERN, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)s.lds));
+        done = true;
     }
-    const i64 ntiles = nouter * nkb;
-    // persistent form: tables in LDS on top of the tile; only where that fits the 160 KB
-    // and pays (many tiles per CU)
-    constexpr size_t lds_p = sizeof(double2) * N * W + sizeof(double2) * (N / 2) +
-                             (MODE == 2 ? sizeof(double) * N : 0);
-    // per-lane offsets are 32-bit byte offsets: (NT/W) pencil points must span < 4 GB
-    // (2048 points x 4 pencils + tables = exactly 160 KB in the fused pass)
-    constexpr bool can_persist = R16 && LOGN <= 11 && N * W == 16 * NT && NT % W == 0 &&
-                                 lds_p <= 160 * 1024;
-    if constexpr (can_persist) {
-        if (ntiles >= 4 * (i64)ncu && smap.sh == 31 && dmap.sh == 31) {
-            auto kern = k_fft_strided_p<LOGN, NT, MODE, W>;
-            static bool attr_set_p[64] = {};  // per device: one process may drive several
-            const int dev_p = c->p.device & 63;
-            if (!attr_set_p[dev_p] && lds_p > 64 * 1024) {
-                CG_HIP(hipFuncSetAttribute((const void *)kern,
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p));
-                attr_set_p[dev_p] = true;
-            }
-            // workgroups per CU the LDS footprint allows
-            int per_cu = (int)((160 * 1024) / lds_p);
-            if (per_cu < 1) per_cu = 1;
-            if (per_cu > 4) per_cu = 4;
-            hipLaunchKernelGGL(kern, dim3((unsigned)(ncu * per_cu)), dim3(NT), lds_p, c->stream,
-                               src, dst, smap.ostride, smap.es, dmap.ostride, dmap.es, nkb,
-                               ntiles, o_off, (const double2 *)c->fft_tw, P);
-            CG_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    auto kern = k_fft_strided<LOGN, NT, MODE, W, R16>;
-    static bool attr_set[64] = {};
-    const int dev = c->p.device & 63;
-    if (!attr_set[dev] && lds > 64 * 1024) {
-        CG_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        attr_set[dev] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nouter * nkb)), dim3(NT), lds, c->stream, src, dst,
-                       smap, dmap, nkb, o_off, (const double2 *)c->fft_tw, P);
+    hipLaunchKernelGGL(KERN, dim3((unsigned)s.grid), dim3(s.NT), (size_t)s.lds, c->stream, args...);
     CG_LAUNCH_CHECK();
     return 0;
 }
 
-// The split pass (k_fft_strided_h): plain pencil maps, enough tiles to keep every CU busy.
-template <int LOGN, int MODE>
-static int run_strided_h(cg_ctx *c, const double2 *src, double2 *dst, PencilMap smap,
-                         PencilMap dmap, i64 nouter, i64 o_off, const KspaceParams &P, bool *done) {
-    constexpr int N = 1 << LOGN, W = 8, NT = (N / 2) * W / 16;
-    *done = false;
-    static int enabled = -1, ncu = 0;
-    if (enabled < 0) {
-        // CONCEPT_GPU_FFT_SPLIT=0: the whole-pencil passes everywhere (what small meshes and the
-        // blocked maps of narrow slabs take anyway: the tests run them at size this way);
-        // 2: the split pass at 512 points too (it does not pay there: 0.48 against 0.46 ms)
-        const char *env = getenv("CONCEPT_GPU_FFT_SPLIT");
-        enabled = env ? atoi(env) : 1;
-        if (LOGN < 10 && enabled < 2) enabled = 0;
-        hipDeviceProp_t prop;
-        CG_HIP(hipGetDeviceProperties(&prop, c->p.device));
-        ncu = prop.multiProcessorCount;
-    }
-    const int nkb = (int)((c->N / 2 + 1 + W - 1) / W);
-    const i64 ntiles = nouter * nkb;
-    // per-lane offsets are 32-bit byte offsets: rows 2 ml (ml < NT/W) must span < 4 GB
-    const i64 reach = ((2 * (i64)(NT / W - 1)) * (smap.es > dmap.es ? smap.es : dmap.es) + W) * 16;
-    // blocked maps (fft_dist): whole multiples of the 2*(NT/W) rows a lane spans per block
-    auto blocks_ok = [](const PencilMap &m) { return m.sh == 31 || (1 << m.sh) >= 2 * (NT / W); };
-    if (!enabled || ntiles < 2 * (i64)ncu || !blocks_ok(smap) || !blocks_ok(dmap) ||
-        reach >= ((i64)1 << 32) || (i64)nkb * W > c->pad / 2)
-        return 0;
-    constexpr size_t lds = sizeof(double2) * (N / 2) * W + sizeof(double2) * (N / 4) +
-                           (MODE == 2 ? sizeof(double) * N : 0) + sizeof(double2) * (NT / W);
-    static_assert(lds <= 160 * 1024, "split pass: LDS");
-    const bool blocked = smap.sh != 31 || dmap.sh != 31;
-    auto kern = blocked ? k_fft_strided_h<LOGN, NT, MODE, true> : k_fft_strided_h<LOGN, NT, MODE, false>;
-    static bool attr_set[64][2] = {};
-    const int dev = c->p.device & 63;
-    if (!attr_set[dev][blocked]) {
-        CG_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                   (int)lds));
-        attr_set[dev][blocked] = true;
-    }
-    // workgroups per CU the LDS footprint allows (2048: one; 1024: two, each the other's cover)
-    const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
-    hipLaunchKernelGGL(kern, dim3((unsigned)(ncu * per_cu)), dim3(NT), lds, c->stream, src, dst,
-                       smap, dmap, nkb, ntiles, o_off, (const double2 *)c->fft_tw, P);
-    CG_LAUNCH_CHECK();
-    *done = true;
-    return 0;
-}
-
-// (radix-16 schedule of the in-LDS transform: the radix-4 one of round 1 lost)
-template <int LOGN, int MODE, int W>
-static int run_strided_w(cg_ctx *c, const double2 *src, double2 *dst, PencilMap smap,
-                         PencilMap dmap, i64 nouter, i64 o_off, const KspaceParams &P) {
-    return run_strided_r<LOGN, MODE, W, true>(c, src, dst, smap, dmap, nouter, o_off, P);
-}
-
-// W adjacent kk per workgroup.  Measured at 1024^3 (ms per y pass / fused x pass):
-//   W = 2 (32 B row segments, 4 workgroups per CU)  9.4 / 9.6
-//   W = 4 (64 B, 2 per CU)                          4.6 / 7.9
-//   W = 8 (128 B = one full cache line, 1 per CU)   3.95 / 7.4
-// The row-segment width, not the occupancy, decides: default 8 (N <= 1024; 8 pencils of
-// 2048 points exceed the 160 KB LDS, so 4 there).
+// One strided pass in the form strided_choice (cg_fft_plan.h) picks: this only turns the form
+// into the kernel's instantiation.  (radix-16 schedule of the in-LDS transform, R16 = true: the
+// radix-4 one of round 1 lost)
 template <int LOGN, int MODE>
 static int run_strided(cg_ctx *c, const double2 *src, double2 *dst, PencilMap smap,
                        PencilMap dmap, i64 nouter, i64 o_off, const KspaceParams &P) {
-    if constexpr (LOGN >= 9 && LOGN <= 11) {  // the even/odd split pass (k_fft_strided_h)
-        bool done = false;
-        if (int rc = run_strided_h<LOGN, MODE>(c, src, dst, smap, dmap, nouter, o_off, P, &done))
-            return rc;
-        if (done) return 0;
+    constexpr int N = 1 << LOGN, W = whole_W(LOGN), NT = whole_NT(LOGN);
+    const StridedChoice s = strided_choice(LOGN, MODE, c->N, c->pad, c->ncu, c->fft_split, nouter,
+                                           {smap.es, smap.sh}, {dmap.es, dmap.sh});
+    const double2 *tw = c->fft_tw;
+    if constexpr (can_split(LOGN)) {
+        constexpr int NTH = split_NT(LOGN);
+        static_assert(split_lds(LOGN, MODE) ==
+                          (i64)(sizeof(double2) * (N / 2) * kSplitW + sizeof(double2) * (N / 4) +
+                                (MODE == 2 ? sizeof(double) * N : 0) +
+                                sizeof(double2) * (NTH / kSplitW)) &&
+                          split_lds(LOGN, MODE) <= kFftLdsBytes, "split pass: LDS");
+        if (s.form == PassForm::Split)
+            return launch_pass<k_fft_strided_h<LOGN, NTH, MODE, false>>(
+                c, s, src, dst, smap, dmap, s.nkb, s.ntiles, o_off, tw, P);
+        if (s.form == PassForm::SplitBlocked)
+            return launch_pass<k_fft_strided_h<LOGN, NTH, MODE, true>>(
+                c, s, src, dst, smap, dmap, s.nkb, s.ntiles, o_off, tw, P);
     }
-    if (LOGN <= 10)  // 8 pencils of 2048 points would not fit the 160 KB LDS
-        return run_strided_w<(LOGN <= 10 ? LOGN : 10), MODE, 8>(c, src, dst, smap, dmap, nouter,
-                                                                o_off, P);
-    return run_strided_w<LOGN, MODE, 4>(c, src, dst, smap, dmap, nouter, o_off, P);
+    if constexpr (can_persist(LOGN, MODE)) {
+        static_assert(persistent_lds(LOGN, MODE) ==
+                          (i64)(sizeof(double2) * N * W + sizeof(double2) * (N / 2) +
+                                (MODE == 2 ? sizeof(double) * N : 0)), "persistent pass: LDS");
+        if (s.form == PassForm::Persistent)
+            return launch_pass<k_fft_strided_p<LOGN, NT, MODE, W>>(
+                c, s, src, dst, smap.ostride, smap.es, dmap.ostride, dmap.es, s.nkb, s.ntiles,
+                o_off, tw, P);
+    }
+    static_assert(plain_lds(LOGN) == (i64)(sizeof(double2) * N * W), "plain pass: LDS");
+    CG_CHECK(s.form == PassForm::Plain, "FFT pass: form %d has no kernel at %d points",
+             (int)s.form, N);
+    return launch_pass<k_fft_strided<LOGN, NT, MODE, W, true>>(c, s, src, dst, smap, dmap, s.nkb,
+                                                               o_off, tw, P);
 }
 
 static PencilMap plain_map(i64 ostride, i64 es) { return PencilMap{ostride, es, 0, 31}; }
 
-// Layers per chunk of the interleaved z / y passes.  Measured at 1024^3 (8.5 MB per layer, ms
-// for z + y forward and inverse together): 16 layers 13.4, 24: 12.2, 27: 11.6, 28: 11.7,
-// 31: 11.3, 32: 11.9, 36: 13.2, 40: 13.6, no chunks: 14.4 — the chunk must fit the 256 MB
-// infinity cache (the cliff sits just above 32 layers = 273 MB), and among the sizes that do,
-// those whose tile count nl*ceil((N/2+1)/8) fills whole rounds of the persistent y pass (one
-// workgroup per CU) win: 31 layers = 2015 tiles = 7.9 rounds of 256 beats 32 = 8.1 rounds.
-static i64 zy_chunk_layers(cg_ctx *c) {
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop;
-        ncu = hipGetDeviceProperties(&prop, c->p.device) == hipSuccess ? prop.multiProcessorCount
-                                                                        : 256;
+// The z and y passes of the layers [layer0, layer0 + nlayers), interleaved over chunks of
+// layers that fit the 256 MB infinity cache (zy_chunk_layers; one chunk when everything fits):
+// forward z then y, inverse y then z.  The second pass of a chunk reads what the first just
+// wrote from the cache, and its own stores overwrite those (still cached, dirty) lines — per
+// chunk HBM sees one read and one write instead of two of each.  1024^3: z + y 7.3 -> 5.9 ms
+// forward, 7.1 -> 5.8 ms inverse with 28 layers (238 MB) per chunk; 36 layers and the gain is
+// gone.  z works in place on the mesh; the y pass of layer l goes from ysrc + l*sls (map smap)
+// to ydst + l*dls (map dmap).
+//   from_end: the forward y pass walks a chunk from its end, where z just stopped and the
+//     tail is still cached (3.73 -> 3.62 ms unchunked).  The fused solve sets it, nobody else.
+//   ev >= 0: pass_events[ev] separates the two passes when there is one chunk; with more the
+//     passes cannot be told apart and it is recorded behind them, so that pass_ms[ev] is ~0
+//     and the caller reports the pair as one (bench.py reads it that way).
+template <int LOGN>
+static int zy_walk(cg_ctx *c, bool inverse, i64 layer0, i64 nlayers, const double2 *ysrc,
+                   double2 *ydst, PencilMap smap, PencilMap dmap, i64 sls, i64 dls,
+                   const KspaceParams &P, bool from_end, int ev) {
+    KspaceParams Py = P;
+    if (from_end && !inverse) Py.long_range |= 2;
+    const ChunkPlan plan(nlayers, zy_chunk_layers(c->N, c->ny, c->pad, c->ncu));
+    auto mark = [&](bool here) {
+        if (here && ev >= 0 && c->pass_events) (void)hipEventRecord(c->pass_events[ev], c->stream);
+    };
+    for (i64 ci = 0; ci < plan.n; ci++) {
+        const i64 l0 = layer0 + plan.begin(ci), nl = plan.begin(ci + 1) - plan.begin(ci);
+        if (!inverse && run_z<LOGN>(c, false, l0, nl)) return 1;
+        if (!inverse) mark(plan.n == 1);
+        const double2 *src = ysrc + l0 * sls;
+        double2 *dst = ydst + l0 * dls;
+        if (inverse ? run_strided<LOGN, 1>(c, src, dst, smap, dmap, nl, 0, Py)
+                    : run_strided<LOGN, 0>(c, src, dst, smap, dmap, nl, 0, Py))
+            return 1;
+        if (inverse) mark(plan.n == 1);
+        if (inverse && run_z<LOGN>(c, true, l0, nl)) return 1;
     }
-    const i64 plane_bytes = c->ny * c->pad * 8;
-    i64 cap = 266000000ll / plane_bytes;
-    if (cap < 1) cap = 1;
-    if (cap >= c->N) return c->N + 1;  // the whole mesh fits: no chunks
-    const i64 nkb = (c->N / 2 + 1 + 7) / 8;
-    i64 best = cap;
-    double best_eff = 0;
-    for (i64 nl = cap; nl >= cap - cap / 4 && nl >= 1; nl--) {
-        i64 tiles = nl * nkb, rounds = (tiles + ncu - 1) / ncu;
-        double eff = (double)tiles / (double)(rounds * ncu);
-        if (eff > best_eff + 1e-9) {
-            best_eff = eff;
-            best = nl;
-        }
-    }
-    return best;
+    mark(plan.n > 1);
+    return 0;
 }
 
-// Split `total` layers into chunks of about `chunk` layers whose sizes differ by at most one
-// (no tiny last chunk): chunk i covers [chunk_begin(i), chunk_begin(i + 1)).
-struct ChunkPlan {
-    i64 n, base, extra;
-    ChunkPlan(i64 total, i64 chunk) {
-        n = chunk >= total ? 1 : (total + chunk / 2) / chunk;
-        if (n < 1) n = 1;
-        base = total / n;
-        extra = total % n;
-    }
-    i64 begin(i64 i) const { return i * base + (i < extra ? i : extra); }
-};
-
+// single domain
 template <int LOGN>
-static int fft3d(cg_ctx *c, int what, const KspaceParams &P) {
-    // single domain.  what: 0 forward, 1 backward, 2 forward + kernel + backward (fused x)
-    const i64 cp = c->pad / 2, N = c->N;
+static int fft3d(cg_ctx *c, FftOp op, const KspaceParams &P) {
+    const i64 cp = c->pad / 2, N = c->N, ls = cp * c->ny;  // complex elements per row, layer
     double2 *m = (double2 *)c->mesh0;
     // y pencils: one per (layer, kk) with stride cp; x pencils: one per (row, kk) with the
     // layer stride cp*ny (ny rows per layer, cg_ctx::ny)
-    PencilMap ymap = plain_map(cp * c->ny, cp), xmap = plain_map(cp, cp * c->ny);
-    if (what == 0 || what == 1) {
-        const i64 chunk0 = zy_chunk_layers(c), ls0 = cp * c->ny;
-        if (what == 1 && run_strided<LOGN, 1>(c, m, m, xmap, xmap, N, 0, P)) return 1;
-        const ChunkPlan plan0(N, chunk0);  // one chunk = the whole mesh when it fits
-        for (i64 ci = 0; ci < plan0.n; ci++) {
-            const i64 l0 = plan0.begin(ci), nl = plan0.begin(ci + 1) - l0;
-            if (what == 0) {
-                if (run_z<LOGN>(c, false, l0, nl)) return 1;
-                if (run_strided<LOGN, 0>(c, m + l0 * ls0, m + l0 * ls0, ymap, ymap, nl, 0, P))
-                    return 1;
-            } else {
-                if (run_strided<LOGN, 1>(c, m + l0 * ls0, m + l0 * ls0, ymap, ymap, nl, 0, P))
-                    return 1;
-                if (run_z<LOGN>(c, true, l0, nl)) return 1;
-            }
-        }
-        if (what == 0) return run_strided<LOGN, 0>(c, m, m, xmap, xmap, N, 0, P);
-        return 0;
-    }
-    auto mark = [&](int i) {
-        if (c->pass_events) (void)hipEventRecord(c->pass_events[i], c->stream);
+    PencilMap ymap = plain_map(ls, cp), xmap = plain_map(cp, ls);
+    const bool solve = op == FftOp::Solve;
+    auto mark = [&](int i) {  // (cg_poisson_solve_timed: around the 5 passes of the solve)
+        if (solve && c->pass_events) (void)hipEventRecord(c->pass_events[i], c->stream);
     };
-    const i64 chunk = zy_chunk_layers(c);
-    if (chunk < N) {
-        // z and y passes interleaved over chunks of layers that fit the 256 MB infinity
-        // cache: the second pass of a chunk reads what the first just wrote from the cache,
-        // and its own stores overwrite those (still cached, dirty) lines — per chunk HBM sees
-        // one read and one write instead of two of each.  1024^3: z + y 7.3 -> 5.9 ms forward,
-        // 7.1 -> 5.8 ms inverse with 28 layers (238 MB) per chunk; 36 layers and the gain is
-        // gone.  The two entries of pass_ms that the chunks merge are reported as one.
-        const i64 ls = cp * c->ny;  // complex elements per layer
-        KspaceParams Pr = P;
-        Pr.long_range |= 2;  // y forward walks a chunk from its end, where z just stopped
-        const ChunkPlan plan(N, chunk);
+    if (op != FftOp::Backward) {
         mark(0);
-        for (i64 ci = 0; ci < plan.n; ci++) {
-            const i64 l0 = plan.begin(ci), nl = plan.begin(ci + 1) - l0;
-            if (run_z<LOGN>(c, false, l0, nl)) return 1;
-            if (run_strided<LOGN, 0>(c, m + l0 * ls, m + l0 * ls, ymap, ymap, nl, 0, Pr)) return 1;
-        }
-        mark(1);
+        if (zy_walk<LOGN>(c, false, 0, N, m, m, ymap, ymap, ls, ls, P, solve, solve ? 1 : -1))
+            return 1;
         mark(2);
-        if (run_strided<LOGN, 2>(c, m, m, xmap, xmap, N, 0, P)) return 1;
+    }
+    if (op == FftOp::Forward ? run_strided<LOGN, 0>(c, m, m, xmap, xmap, N, 0, P)
+        : solve              ? run_strided<LOGN, 2>(c, m, m, xmap, xmap, N, 0, P)  // fused x
+                             : run_strided<LOGN, 1>(c, m, m, xmap, xmap, N, 0, P))
+        return 1;
+    if (op != FftOp::Forward) {
         mark(3);
-        for (i64 ci = 0; ci < plan.n; ci++) {
-            const i64 l0 = plan.begin(ci), nl = plan.begin(ci + 1) - l0;
-            if (run_strided<LOGN, 1>(c, m + l0 * ls, m + l0 * ls, ymap, ymap, nl, 0, P)) return 1;
-            if (run_z<LOGN>(c, true, l0, nl)) return 1;
-        }
-        mark(4);
+        if (zy_walk<LOGN>(c, true, 0, N, m, m, ymap, ymap, ls, ls, P, false, solve ? 4 : -1))
+            return 1;
         mark(5);
-        return 0;
     }
-    mark(0);
-    if (run_z<LOGN>(c, false)) return 1;
-    mark(1);
-    {
-        // the y pass walks the layers from the end, where the z pass just stopped: the tail
-        // of the mesh is still in the 256 MB infinity cache (3.73 -> 3.62 ms); the inverse z
-        // pass does the same after the inverse y pass
-        KspaceParams Pr = P;
-        Pr.long_range |= 2;
-        if (run_strided<LOGN, 0>(c, m, m, ymap, ymap, N, 0, Pr)) return 1;
-    }
-    mark(2);
-    if (run_strided<LOGN, 2>(c, m, m, xmap, xmap, N, 0, P)) return 1;
-    mark(3);
-    if (run_strided<LOGN, 1>(c, m, m, ymap, ymap, N, 0, P)) return 1;
-    mark(4);
-    int rc = run_z<LOGN>(c, true);
-    mark(5);
-    return rc;
+    return 0;
 }
 
 // x-slab domains (one per GPU).  The local slab complex[nxl][N][cp] is
@@ -1246,7 +1111,7 @@ static int fft3d(cg_ctx *c, int what, const KspaceParams &P) {
 // and the x pass is again a plain strided pencil (stride JB*cp).  The way back
 // mirrors it: the inverse y pass reads the blocked layout.
 template <int LOGN>
-static int fft_dist(cg_ctx *c, int what, double2 *buf, const KspaceParams &P, i64 layer0,
+static int fft_dist(cg_ctx *c, SlabOp op, double2 *buf, const KspaceParams &P, i64 layer0,
                     i64 nlayers) {
     const i64 cp = c->pad / 2, N = c->N, nxl = c->xmap.nxl, JB = N / c->p.nprocs;
     if (nlayers < 0) nlayers = nxl - layer0;  // [layer0, layer0 + nlayers) of the owned layers
@@ -1256,36 +1121,24 @@ static int fft_dist(cg_ctx *c, int what, double2 *buf, const KspaceParams &P, i6
     int sh = 0;
     while ((1 << sh) < JB) sh++;
     double2 *m = (double2 *)c->mesh0;
-    PencilMap ymap = plain_map(cp * c->ny, cp);
-    PencilMap bmap{JBp * cp, cp, nxl * JBp * cp, sh};
-    const i64 chunk = zy_chunk_layers(c), ls = cp * c->ny, lb = JBp * cp;
-    if (what == 0) {  // forward z, forward y -> send buffer, chunk by chunk (see fft3d)
-        const ChunkPlan plan(nlayers, chunk);
-        for (i64 ci = 0; ci < plan.n; ci++) {
-            const i64 l0 = layer0 + plan.begin(ci), nl = plan.begin(ci + 1) - plan.begin(ci);
-            if (run_z<LOGN>(c, false, l0, nl)) return 1;
-            if (run_strided<LOGN, 0>(c, m + l0 * ls, buf + l0 * lb, ymap, bmap, nl, 0, P)) return 1;
-        }
-        return 0;
+    const i64 ls = cp * c->ny, lb = JBp * cp;
+    PencilMap ymap = plain_map(ls, cp), bmap{lb, cp, nxl * lb, sh};
+    // the x pass on complex[N][JB][cp] (alone for the general particle_mesh: the Fourier slab
+    // is operated on between the two)
+    PencilMap xmap = plain_map(cp, lb);
+    const i64 j0 = (i64)c->p.rank * JB;
+    switch (op) {
+        case SlabOp::ZYForward:  // -> send buffer
+            return zy_walk<LOGN>(c, false, layer0, nlayers, m, buf, ymap, bmap, ls, lb, P, false,
+                                 -1);
+        case SlabOp::ZYBackward:  // from the returned buffer
+            return zy_walk<LOGN>(c, true, layer0, nlayers, buf, m, bmap, ymap, lb, ls, P, false,
+                                 -1);
+        case SlabOp::XSolve: return run_strided<LOGN, 2>(c, buf, buf, xmap, xmap, JB, j0, P);
+        case SlabOp::XForward: return run_strided<LOGN, 0>(c, buf, buf, xmap, xmap, JB, j0, P);
+        case SlabOp::XBackward: return run_strided<LOGN, 1>(c, buf, buf, xmap, xmap, JB, j0, P);
     }
-    if (what == 2) {  // fused x pass on complex[N][JB][cp]
-        PencilMap xmap = plain_map(cp, JBp * cp);
-        return run_strided<LOGN, 2>(c, buf, buf, xmap, xmap, JB, (i64)c->p.rank * JB, P);
-    }
-    if (what == 3 || what == 4) {  // the x pass alone (general particle_mesh: the Fourier slab
-        PencilMap xmap = plain_map(cp, JBp * cp);  // is operated on between the two)
-        if (what == 3)
-            return run_strided<LOGN, 0>(c, buf, buf, xmap, xmap, JB, (i64)c->p.rank * JB, P);
-        return run_strided<LOGN, 1>(c, buf, buf, xmap, xmap, JB, (i64)c->p.rank * JB, P);
-    }
-    // backward y from the returned buffer, backward z
-    const ChunkPlan plan(nlayers, chunk);
-    for (i64 ci = 0; ci < plan.n; ci++) {
-        const i64 l0 = layer0 + plan.begin(ci), nl = plan.begin(ci + 1) - plan.begin(ci);
-        if (run_strided<LOGN, 1>(c, buf + l0 * lb, m + l0 * ls, bmap, ymap, nl, 0, P)) return 1;
-        if (run_z<LOGN>(c, true, l0, nl)) return 1;
-    }
-    return 0;
+    return 1;
 }
 
 bool cgk_fft_supported(i64 N) { return N >= 16 && N <= 2048 && (N & (N - 1)) == 0; }
@@ -1304,24 +1157,12 @@ bool cgk_fft_supported(i64 N) { return N >= 16 && N <= 2048 && (N & (N - 1)) == 
     cg_set_error("grid size %lld not supported by the hand-written FFT", (long long)c->N);    \
     return 1;
 
-int cgk_fft(cg_ctx *c, int what, int deconv_order, double C, int long_range, double E) {
+int cgk_fft(cg_ctx *c, FftOp op, int deconv_order, double C, int long_range, double E) {
     KspaceParams P{c->ktab_n, c->ktab_s, c->ktab_q, deconv_order, long_range, C, E};
-    CG_FFT_DISPATCH(fft3d, c, what, P)
+    CG_FFT_DISPATCH(fft3d, c, op, P)
 }
-int cgk_fft_dist_forward(cg_ctx *c, double *send_buf, i64 layer0, i64 nlayers) {
-    KspaceParams P{c->ktab_n, c->ktab_s, c->ktab_q, 0, 0, 0.0, 0.0};
-    CG_FFT_DISPATCH(fft_dist, c, 0, (double2 *)send_buf, P, layer0, nlayers)
-}
-int cgk_fft_dist_xsolve(cg_ctx *c, double *buf, int deconv_order, double C, int long_range,
-                        double E) {
+int cgk_fft_dist(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, double C, int long_range,
+                 double E, i64 layer0, i64 nlayers) {
     KspaceParams P{c->ktab_n, c->ktab_s, c->ktab_q, deconv_order, long_range, C, E};
-    CG_FFT_DISPATCH(fft_dist, c, 2, (double2 *)buf, P, 0, -1)
-}
-int cgk_fft_dist_x(cg_ctx *c, double *buf, int inverse) {
-    KspaceParams P{c->ktab_n, c->ktab_s, c->ktab_q, 0, 0, 0.0, 0.0};
-    CG_FFT_DISPATCH(fft_dist, c, inverse ? 4 : 3, (double2 *)buf, P, 0, -1)
-}
-int cgk_fft_dist_backward(cg_ctx *c, const double *recv_buf, i64 layer0, i64 nlayers) {
-    KspaceParams P{c->ktab_n, c->ktab_s, c->ktab_q, 0, 0, 0.0, 0.0};
-    CG_FFT_DISPATCH(fft_dist, c, 1, (double2 *)recv_buf, P, layer0, nlayers)
+    CG_FFT_DISPATCH(fft_dist, c, op, buf, P, layer0, nlayers)
 }

@@ -158,6 +158,8 @@ struct cg_ctx {
     // hand-written FFT (cg_fft.hip): twiddles exp(-2 pi i k/N) as double2[N]
     bool custom_fft = false;
     cg_buf<double2> fft_tw;
+    // what its plans (cg_fft_plan.h) depend on: the device's CU count and CONCEPT_GPU_FFT_SPLIT
+    int ncu = 0, fft_split = 1;
 
     // ---- tiles, sort and regions ----
     TileGeom tiles{};
@@ -280,14 +282,17 @@ int cgk_fluid_kick(cg_ctx *c, double *J, const double *rho, const double *P, int
                    int diff_order, double minus_dt, double inv_c2);
 
 // ---- cg_fft.hip: the hand-written FFT ----
+// the single-domain solve: Solve = forward + Poisson kernel + backward with the x pass fused
+enum class FftOp { Forward, Backward, Solve };
+// its pieces on x-slab domains, around the two transposes (also of the rocFFT backend,
+// cg_context.hip): z and y of owned layers into / out of the transpose buffer, x on that buffer
+enum class SlabOp { ZYForward, XSolve, XForward, XBackward, ZYBackward };
 bool cgk_fft_supported(i64 N);
-int cgk_fft_dist_forward(cg_ctx *c, double *send_buf, i64 layer0, i64 nlayers);
-int cgk_fft_dist_xsolve(cg_ctx *c, double *buf, int deconv_order, double C, int long_range,
-                        double E);
-int cgk_fft_dist_backward(cg_ctx *c, const double *recv_buf, i64 layer0, i64 nlayers);
-int cgk_fft_dist_x(cg_ctx *c, double *buf, int inverse);
-// what: 0 forward, 1 backward, 2 forward + Poisson kernel + backward (fused)
-int cgk_fft(cg_ctx *c, int what, int deconv_order, double C, int long_range, double E);
+int cgk_fft(cg_ctx *c, FftOp op, int deconv_order, double C, int long_range, double E);
+// layers [layer0, layer0 + nlayers) of the owned ones (nlayers < 0: from layer0 on) for the ZY
+// pieces; deconv_order, C, long_range, E for XSolve
+int cgk_fft_dist(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, double C, int long_range,
+                 double E, i64 layer0, i64 nlayers);
 
 // ---- cg_particles.hip: drift, tile sort, regions ----
 // out[i] = in[0] + ... + in[i-1] for i < n, on c->stream (temporary storage: c->scan_tmp)

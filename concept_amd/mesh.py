@@ -104,7 +104,7 @@ class PotentialMesh:
         npieces = max(1, min(want, self.nxl//8))
         if npieces > 1:
             # a piece should also fit the 256 MB infinity cache, like the chunks of the
-            # single-GPU schedule (cg_fft.hip zy_chunk_layers): its y pass then reads what its
+            # single-GPU schedule (zy_chunk_layers, cg_fft_plan.h): its y pass then reads what its
             # z pass wrote from the cache
             cache_layers = max(1, int(266e6//(per*8)))
             npieces = min(max(npieces, -(-self.nxl//cache_layers)), max(1, self.nxl//8))

@@ -421,6 +421,81 @@ def test_handwritten_fft_vs_numpy_and_rocfft(torch_cuda, N, monkeypatch):
     assert np.abs(phi_fused - phi_roc).max() <= 1e-12*np.abs(phi_roc).max()
 
 
+def test_fft_512_chunked_walk_vs_rocfft(torch_cuda, monkeypatch):
+    """512^3 is the smallest grid whose mesh exceeds the cache bound of the z / y chunk walk
+    (cg_fft_plan.h: six chunks of 85 or 86 layers, persistent y passes k_fft_strided_p<9,256,*,8>):
+    the hand-written backend against rocFFT's 3-D plan on the same density, with the bars of
+    test_gpu_production_parity.test_fft_1024_vs_rocfft, and the event bookkeeping of
+    cg_poisson_solve_timed as bench.py reads it (chunked: entries 1 and 4 are empty, the pair is
+    timed as one; one chunk, 256^3: they are passes of their own)."""
+    torch = torch_cuda
+    from concept_amd.mesh import PotentialMesh
+    N, L, n = 512, 512.0, 2**21
+
+    def view(mesh, cols):  # the owned layers as a (N, N, cols) device tensor (a copy)
+        per = mesh.layer_doubles
+        buf = torch.empty(N*per, dtype=torch.float64, device='cuda')
+        mesh.layers_read(0, N, buf)
+        return buf.view(N, per//mesh.pad, mesh.pad)[:, :N, :cols]
+
+    def trms(t):
+        return float((t**2).mean().sqrt())
+    gen = torch.Generator(device='cuda').manual_seed(13)
+    pos = torch.rand((n, 3), dtype=torch.float64, device='cuda', generator=gen)
+    pos[:, 0] = pos[:, 0]**2  # clustered along x so that the spectrum is not flat
+    pos.mul_(L*(1 - 1e-13))
+    monkeypatch.delenv('CONCEPT_GPU_FFT', raising=False)
+    own = PotentialMesh(N, L)
+    monkeypatch.setenv('CONCEPT_GPU_FFT', 'rocfft')
+    roc = PotentialMesh(N, L)
+    monkeypatch.delenv('CONCEPT_GPU_FFT', raising=False)
+    own.zero()
+    own.deposit(pos, 1.0)
+    roc.copy_from(own)  # (the direct deposit adds with atomics: two runs differ by rounding)
+    dens = view(own, N).clone()
+    assert torch.equal(dens, view(roc, N))
+    # unfused forward
+    own.poisson_forward(0, 1.0, False, 0.0, apply_kernel=False)
+    roc.poisson_forward(0, 1.0, False, 0.0, apply_kernel=False)
+    a, b = view(own, N + 2), view(roc, N + 2)
+    err, scale = float((a - b).abs().max()), trms(b)
+    print(f'forward: max deviation {err:.3e}, rms mode {scale:.3e}, ratio {err/scale:.3e}')
+    assert err <= 4e-12*scale, (err, scale)
+    del a, b
+    # round trip: unnormalised, N^3 * identity
+    own.poisson_backward()
+    err = float((view(own, N)/N**3 - dens).abs().max())
+    print(f'round trip: {err:.3e} of max {float(dens.abs().max()):.3e}')
+    assert err <= 1e-12*float(dens.abs().max())
+    # fused solve against rocFFT + the stand-alone k-space kernel
+    C, E = -L**2/np.pi, -(2*np.pi/L*1.25)**2
+    for long_range in (False, True):
+        own.zero()
+        own.deposit(pos, 1.0)
+        roc.copy_from(own)
+        own.poisson_solve(4, C, long_range, E)
+        roc.poisson_forward(4, C, long_range, E, apply_kernel=True)
+        roc.poisson_backward()
+        a, b = view(own, N), view(roc, N)
+        err, scale = float((a - b).abs().max()), trms(b - b.mean())
+        print(f'solve long_range={long_range}: {err:.3e}, rms {scale:.3e}, ratio {err/scale:.3e}')
+        assert err <= 1e-12*scale, (long_range, err, scale)
+        del a, b
+    roc.close()
+    # the events: bench.py takes pass_ms[1] < 0.05*pass_ms[0] for "z and y timed as one"
+    ms = own.poisson_solve_timed(4, C, False, 0.0)
+    print('pass_ms 512:', ms)
+    assert ms[1] < 0.05*ms[0] and ms[4] < 0.05*ms[3], ms
+    own.close()
+    small = PotentialMesh(256, L)
+    small.zero()
+    small.deposit(pos, 1.0)
+    ms = small.poisson_solve_timed(4, C, False, 0.0)
+    print('pass_ms 256:', ms)
+    assert ms[1] >= 0.05*ms[0] and ms[4] >= 0.05*ms[3], ms
+    small.close()
+
+
 def test_fft_2048_roundtrip(torch_cuda):
     """The largest grid of BASELINE.json (2048^3, config 4's mesh; 69 GB on one GPU):
     forward then backward = N^3 * identity, and the fused solve equals the split one."""
