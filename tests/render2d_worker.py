@@ -3,7 +3,8 @@ cuda:0 and talk over gloo (test only; production is one GPU per rank over RCCL).
 projects its own layers — its own columns of the image for the axes y and z, a partial image
 for axis x — and the images are summed in rank order, so every rank holds the render, which
 must agree with the reference's (and so with one domain) and be the same on all ranks bit for
-bit."""
+bit.  Arguments: names of goldens, or synthetic:N for the projections of a seeded mesh of size N
+against a direct host sum (check_synthetic_on_domains of the test module)."""
 import os
 import sys
 import warnings
@@ -25,6 +26,11 @@ def main():
     c = comm.active()
     import test_gpu_render2d as t
     for name in sys.argv[1:]:
+        if name.startswith('synthetic:'):
+            # a seeded global array, every rank its own layers, against a direct host sum
+            t.check_synthetic_on_domains(int(name.split(':')[1]), c)
+            print(f'rank {rank}: {name} ok', flush=True)
+            continue
         g = t.golden(name)
         comps = t.golden_components(g)
         with warnings.catch_warnings():

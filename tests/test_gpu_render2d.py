@@ -1,6 +1,7 @@
 """2D renders on the GPU (concept_amd.render, csrc/cg_render.hip): against the reference's own
 results (tests/golden/render2d_*.npz), the PNG, the device histogram against numpy, properties
-of the projection, the time loop's dumps and the utility, a 1024³ run, and x-slab domains.
+of the projection, the projection past one tile against a direct weighted sum of the mesh, the
+time loop's dumps and the utility, a 1024³ run, and x-slab domains.
 
 Bars.  The 'data' projection: |Δ| <= 1e-12·max|golden| for every pixel (the project's bar for
 mesh values).  The images: the exponent of the search equals the golden's; the pixel tolerance
@@ -269,6 +270,146 @@ def test_projection_properties():
         assert torch.equal(e1, e2) and float(e1.min()) < float(e1.max())
 
 
+# -- the projection against a direct weighted sum, past one tile --------------------------------
+# k_project_along_z gives a wave 64 rows j at a time and walks the planes with k += 64;
+# k_project_across works in tiles of 64 k by 16 d0.  N = 72 has two j-blocks and two k-blocks (the
+# second with 8 live entries) and a partial d0 tile (72 % 16 = 8); N = 136 has three blocks and
+# up to 136 planes, a third trip.  The mesh holds seeded values of both signs (NaN in the padding,
+# which no projection may read); the reference is the kernel's contract restated on the host,
+#     P[d0, d1] = factor · Σ_s w_s · M[…],   image = flipud(P.T),
+# summed in np.longdouble, with w = frac_bgn on plane_bgn, frac_end on plane_end - 1 and 1
+# between them (a one-plane range: frac_bgn), and (d0, d1, s) = (y, z, x), (x, z, y), (x, y, z).
+#
+# Bar per pixel: n·2⁻⁵³·factor·Σ_s |w_s·M|, n the number of planes.  Every term takes at most
+# one rounding in w_s·M and at most n - 1 in the additions, whatever their order (the sum over
+# the domains' images included), and the factor is a power of two here, so multiplying by it
+# rounds nothing: n roundings in all, each 2⁻⁵³ relative to a partial sum that Σ |w_s·M| bounds.
+SYNTHETIC_FACTOR = 0.125
+SYNTHETIC_RANGES = {
+    72: ((0, 72, 1.0, 1.0),
+         (5, 69, 0.25, 0.6),     # exactly 64 planes
+         (7, 72, 0.25, 0.6),     # 65 planes
+         (3, 70, 0.9, 0.1),
+         (40, 41, 0.37, 0.0),
+         (40, 42, 0.8, 0.0),     # an extent of at most one cell (projection_planes)
+         (71, 72, 1.0, 1.0)),
+    136: ((0, 136, 1.0, 1.0),
+          (1, 131, 0.5, 0.5)),   # 130 planes: 2 live lanes in the third trip
+}
+# on x-slab domains of 18 layers: the clipping of cg_render2d_project for axis x
+DOMAIN_RANGES = {
+    'x': ((17, 19, 0.75, 0.0),   # the two planes of an extent <= 1 cell on different ranks
+          (18, 37, 0.3, 0.6),    # from a rank's first layer to a lone plane two ranks on
+          (35, 36, 0.5, 0.0),    # one plane: three ranks have none
+          (10, 60, 0.2, 0.7)),
+    'y': ((3, 70, 0.9, 0.1),),
+    'z': ((3, 70, 0.9, 0.1),),
+}
+_synthetic_fields = {}
+_synthetic_meshes = {}
+
+
+def _synthetic_field(N):
+    """the seeded global array [x][y][z], made once per N and left unchanged"""
+    if N not in _synthetic_fields:
+        _synthetic_fields[N] = np.random.default_rng(1000 + N).normal(0, 1, (N, N, N))
+    return _synthetic_fields[N]
+
+
+def _synthetic_mesh(N):
+    """a mesh of size N (one x-slab domain under comm.init()) holding this domain's layers of
+    _synthetic_field(N); the test's own, so that free_meshes() of another test leaves it alone"""
+    import torch
+    from concept_amd import comm
+    from concept_amd.mesh import PotentialMesh
+    mesh = _synthetic_meshes.get(N)
+    if mesh is None:
+        mesh = PotentialMesh(N, 100.0, comm=comm.active())
+        per, pad, nxl = mesh.layer_doubles, mesh.pad, mesh.nxl
+        buf = np.full((nxl, per), np.nan)
+        buf[:, :N*pad].reshape(nxl, N, pad)[:, :, :N] = _synthetic_field(N)[mesh.x0:mesh.x0 + nxl]
+        mesh.layers_write(0, nxl, torch.tensor(buf.reshape(-1), device='cuda'))
+        _synthetic_meshes[N] = mesh
+    return mesh
+
+
+def direct_projection(field, axis, planes, factor):
+    """(image, bar) of the contract above: the longdouble weighted sum and the per-pixel bar"""
+    bgn, end, frac_bgn, frac_end = planes
+    w = np.ones(end - bgn, dtype=np.longdouble)
+    w[-1] = frac_end
+    w[0] = frac_bgn   # a one-plane range counts with frac_bgn
+    terms = np.moveaxis(field, 'xyz'.index(axis), -1)[..., bgn:end].astype(np.longdouble)*w
+    P = factor*terms.sum(-1)
+    bar = (end - bgn)*2.0**-53*factor*np.abs(terms).sum(-1)
+    return np.flipud(P.T), np.flipud(bar.T)
+
+
+def check_synthetic_projection(N, axis, planes, comm=None, tag=''):
+    """render2D_project of the synthetic mesh (summed over the domains of `comm` the way
+    project_render2D sums them) against direct_projection.  Returns the device image."""
+    mesh = _synthetic_mesh(N)
+    image = mesh.render2D_project(axis, *planes, SYNTHETIC_FACTOR)
+    if comm is not None and comm.world > 1:
+        image.copy_(comm.sum_in_rank_order(image))
+    want, bar = direct_projection(_synthetic_field(N), axis, planes, SYNTHETIC_FACTOR)
+    got = image.cpu().numpy()
+    assert got.shape == want.shape == (N, N)
+    assert np.all(np.isfinite(got)), f'{tag}axis {axis} {planes}: the image is not finite'
+    assert np.all(bar > 0)
+    ratio = np.abs(got.astype(np.longdouble) - want)/bar
+    print(f'{tag}N = {N}, axis {axis}, planes {planes}: worst |Δ| = '
+          f'{float(np.max(np.abs(got - want))):.3e}, worst ratio to the bar = '
+          f'{float(ratio.max()):.3f}')
+    assert ratio.max() <= 1, (axis, planes, float(ratio.max()))
+    return image
+
+
+@pytest.mark.parametrize('N, planes', [(N, planes) for N in SYNTHETIC_RANGES
+                                       for planes in SYNTHETIC_RANGES[N]])
+def test_projection_matches_a_direct_sum(N, planes):
+    import torch
+    for axis in 'xyz':
+        image = check_synthetic_projection(N, axis, planes)
+        again = _synthetic_mesh(N).render2D_project(axis, *planes, SYNTHETIC_FACTOR)
+        assert torch.equal(image, again), axis
+
+
+@pytest.mark.parametrize('n_bins', [25, 20000])
+def test_enhancement_of_a_projected_image(n_bins):
+    """the device minimum, maximum and histogram of a real projected image (N = 136, both signs)
+    against numpy's of the same image, exactly"""
+    from concept_amd import render
+    N = 136
+    mesh = _synthetic_mesh(N)
+    image = mesh.render2D_project('z', *SYNTHETIC_RANGES[N][1], SYNTHETIC_FACTOR)
+    host = image.cpu().numpy()
+    assert host.min() < 0 < host.max()
+    assert render._minmax(mesh, image) == (np.min(host), np.max(host))
+    counts, bin_edges = render._histogram(mesh, image, 1.0, n_bins)
+    want, want_edges = np.histogram(host, n_bins)
+    np.testing.assert_array_equal(bin_edges, want_edges)
+    np.testing.assert_array_equal(counts, want)
+    print(f'N = {N}, {n_bins} bins: {int(np.count_nonzero(want))} bins filled, the fullest '
+          f'holds {int(want.max())} of {host.size} pixels; counts, edges, min and max equal '
+          f"numpy's")
+    assert counts.sum() == host.size
+
+
+def check_synthetic_on_domains(N, comm):
+    """One rank's part of the synthetic projections on x-slab domains: every rank writes its own
+    layers of the same global array and projects them; the summed images meet the bar of one
+    domain against the same host sum and are the same on all ranks bit for bit."""
+    import torch
+    assert N == 72 and comm.world == 4
+    for axis, ranges in DOMAIN_RANGES.items():
+        for planes in ranges:
+            image = check_synthetic_projection(N, axis, planes, comm, tag=f'rank {comm.rank} ')
+            rows = comm.all_gather_rows(image.reshape(1, -1))
+            assert all(torch.equal(rows[r], rows[0]) for r in range(comm.world)), \
+                'the ranks hold different images'
+
+
 # -- the time loop's dumps and the utility ------------------------------------------------------
 def test_timeloop_dumps_render2D_files(tmp_path):
     import torch
@@ -447,11 +588,13 @@ def test_render2D_on_domains(world):
     port = s.getsockname()[1]
     s.close()
     procs = []
+    # four domains of 18 layers also project the synthetic mesh of size 72 (DOMAIN_RANGES)
+    cases = list(GOLDEN[:3]) + (['synthetic:72'] if world == 4 else [])
     for r in range(world):
         env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR='127.0.0.1',
                    MASTER_PORT=str(port))
         procs.append(subprocess.Popen(
-            [sys.executable, os.path.join(HERE, 'render2d_worker.py')] + list(GOLDEN[:3]),
+            [sys.executable, os.path.join(HERE, 'render2d_worker.py')] + cases,
             env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
     outs = [p.communicate(timeout=600)[0].decode() for p in procs]
     for r, p in enumerate(procs):
