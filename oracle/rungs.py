@@ -77,11 +77,15 @@ class Particles:
     def get_rung_factor(self, dt, fac_softening):
         return 0.5*np.log2(dt**2/(2*fac_softening*self.softening_length))
 
+    # species.py:2346-2353: rung_index_float (-inf where the acceleration vanishes)
+    def rung_index_float(self, rung_factor):
+        with np.errstate(divide='ignore', over='ignore'):
+            acc2 = self.dmom[:, 0]**2 + self.dmom[:, 1]**2 + self.dmom[:, 2]**2
+            return acc2, rung_factor + 0.25*np.log2(acc2)
+
     # species.py:2341-2363, vectorised
     def get_rung(self, rung_factor):
-        acc2 = self.dmom[:, 0]**2 + self.dmom[:, 1]**2 + self.dmom[:, 2]**2
-        with np.errstate(divide='ignore'):
-            f = rung_factor + 0.25*np.log2(acc2)
+        acc2, f = self.rung_index_float(rung_factor)
         out = np.where(f < 0, 0, np.where(f > self.N_rungs - 1, self.N_rungs - 1,
                                           1 + np.where(np.isfinite(f), f, 0).astype(np.int8)))
         return np.where(acc2 == 0, self.rung, out).astype(np.int8)
@@ -94,11 +98,16 @@ class Particles:
         self.set_rungs_N()
 
     # species.py:2463-2513
-    def flag_rung_jumps(self, dt, dt_jump_fac, fac_softening, dt_rungs):
+    # rung_factors = (up, down): the two rung factors themselves instead of dt, dt_jump_fac and
+    # fac_softening (a test that hands a kernel and this method the very same doubles)
+    def flag_rung_jumps(self, dt, dt_jump_fac, fac_softening, dt_rungs, rung_factors=None):
         integrals = dt_rungs[KEY_1]
         nr = self.N_rungs
-        ought_up = self.get_rung(self.get_rung_factor(dt*dt_jump_fac, fac_softening))
-        ought_down = self.get_rung(self.get_rung_factor(dt/dt_jump_fac, fac_softening))
+        if rung_factors is None:
+            rung_factors = (self.get_rung_factor(dt*dt_jump_fac, fac_softening),
+                            self.get_rung_factor(dt/dt_jump_fac, fac_softening))
+        ought_up = self.get_rung(rung_factors[0])
+        ought_down = self.get_rung(rung_factors[1])
         r = self.rung.astype(np.int64)
         consider = (r >= self.lowest_active_rung) if self.lowest_active_rung > 0 \
             else np.ones(self.N, dtype=bool)
