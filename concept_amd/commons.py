@@ -655,6 +655,45 @@ def _load_fluid_params(p, user):
     mc['foresight_select'] = {key: int(np.round(val)) for key, val in mc['foresight_select'].items()}
     mc['smoothing_select'] = {key: float(val) for key, val in mc['smoothing_select'].items()}
     p.fluid_options = opts
+    _load_eos_params(p, user)
+
+
+def _load_eos_params(p, user):
+    """select_eos_w (commons.py:3712-3721), select_boltzmann_closure and select_approximations
+    (commons.py:3850-3861).  Only a constant numeric w is implemented (the reference's
+    w_type 'constant'); where the reference defaults to 'class' (w from the CLASS background,
+    0 for matter-like species without it) the default here is 0.  Likewise the closure
+    defaults to 'truncate': 'class' needs CLASS realisations and is refused by the fluid
+    solver.  The approximation names are folded per component (species.Component)."""
+    given = user.get('select_eos_w')
+    sel = {}
+    if given is not None and given != {}:
+        sel = dict(given) if isinstance(given, dict) else {'all': given}
+    eos = {}
+    for key, val in sel.items():
+        if isinstance(val, (bool, str)) or not isinstance(val, (int, float, np.integer,
+                                                                np.floating)):
+            raise ValueError(
+                f'select_eos_w[{key!r}] = {val!r}: only a constant numeric w is implemented '
+                "(w given as 'class', 'default', an expression or a table is not implemented)")
+        eos[key] = float(val)
+    eos['default'] = 0.0
+    p.select_eos_w = eos
+    given = user.get('select_boltzmann_closure')
+    sel = {}
+    if given:
+        sel = dict(given) if isinstance(given, dict) else {'all': given}
+    sel['default'] = 'truncate'
+    p.select_boltzmann_closure = {key: str(val).lower() for key, val in sel.items()}
+    sel = {}
+    if user.get('select_approximations'):
+        sel = dict(user['select_approximations'])
+        key = tuple(sel.keys())[0]
+        if isinstance(key, str) and '=' in key:
+            sel = {'all': sel}
+        sel = {key: dict(val) for key, val in sel.items()}
+    sel['default'] = {'P=wρ': False}
+    p.select_approximations = sel
 
 
 def is_selected(component, d, accumulate=False, default=None):

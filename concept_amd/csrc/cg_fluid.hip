@@ -7,6 +7,9 @@
 //   k_vacuum_gather   the pair terms of the 3x3x3 blocks, as a gather     fluid.py:1289-1319
 //   k_vacuum_apply    variable += Δ                                       fluid.py:1333-1340
 //   k_vmax            max (Jx² + Jy² + Jz²)/(ϱ + c⁻²𝒫)²                   analysis.py:3940-3955
+//   k_pressure_sources  𝒫 = ϱ (c²w) and the pressure term of the Euler equation, one pass
+//                                                         ic.py:503-508, fluid.py:1044-1057, mesh.py:4966-4970
+//   k_realize_P       𝒫 = ϱ (c²w) alone                                   ic.py:503-508
 //
 // A fluid grid is this domain's layers of the global grid, double[nxl][g][g] without ghosts
 // (species.Component).  y and z are periodic by index wrap.  In x a kernel reads up to H layers
@@ -244,6 +247,65 @@ __global__ __launch_bounds__(kThreads) void k_vmax(const double *__restrict__ rh
     if (threadIdx.x == 0) out[blockIdx.x] = red[0];
 }
 
+// The realisation 𝒫 = ϱ (c²w) of the P = wρ approximation (ic.py:503-508) and the pressure term of
+// maccormack_internal_sources (fluid.py:1044-1057) in one pass:
+//   J_i += minus_dt * (half_inv_dx * (𝒫[+1_i] - 𝒫[-1_i]))      diff_domaingrid, order 2 (mesh.py:4966-4970)
+// A workgroup owns a tile of kTY x kTZ cells, staged with one halo cell on every side, and walks
+// kXC layers upwards along x with the layer below, the own one and the layer above resident in
+// LDS; every ϱ value is loaded once per walk (plus the halo).  The six neighbour values of 𝒫 are
+// formed from the staged ϱ by the product that fills the 𝒫 grid, so they are the bits the
+// reference reads from that grid.  The stencil reads ϱ only: J and 𝒫 are updated in place.
+__global__ __launch_bounds__(kThreads) void k_pressure_sources(Layers rho, double *__restrict__ P,
+                                                               Out4 J, int g, int nxl, double c2w,
+                                                               double minus_dt,
+                                                               double half_inv_dx) {
+#pragma clang fp contract(off)
+    __shared__ double tile[3][kTY + 2][kTZ + 2];
+    const int tz = threadIdx.x % kTZ, ty = threadIdx.x / kTZ;
+    const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
+    const int xa = blockIdx.z * kXC, xb = xa + kXC < nxl ? xa + kXC : nxl;
+    const i64 g2 = (i64)g * g;
+    // local (ly, lz) is cell (y0 - 1 + ly, z0 - 1 + lz) of the layer, wrapped
+    auto load = [&](int buf, int l) {
+        const double *layer = layer_of<1>(rho, l, nxl, g2);
+        for (int e = threadIdx.x; e < (kTY + 2) * (kTZ + 2); e += kThreads) {
+            const int ly = e / (kTZ + 2), lz = e - ly * (kTZ + 2);
+            // (a partial tile's rows beyond the grid wrap as well: loaded, never used)
+            const int y = (y0 - 1 + ly + g) % g, z = (z0 - 1 + lz + g) % g;
+            tile[buf][ly][lz] = layer[(i64)y * g + z];
+        }
+    };
+    const bool mine = y0 + ty < g && z0 + tz < g;
+    const int cy = ty + 1, cz = tz + 1;
+    load(0, xa - 1);
+    load(1, xa);
+    for (int l = xa, n = 0; l < xb; l++, n++) {
+        const int below = n % 3, own = (n + 1) % 3, above = (n + 2) % 3;
+        load(above, l + 1);
+        __syncthreads();
+        if (mine) {
+            const i64 at = ((i64)l * g + (y0 + ty)) * g + (z0 + tz);
+            P[at] = tile[own][cy][cz] * c2w;
+            const double up[3] = {tile[above][cy][cz] * c2w, tile[own][cy + 1][cz] * c2w,
+                                  tile[own][cy][cz + 1] * c2w};
+            const double down[3] = {tile[below][cy][cz] * c2w, tile[own][cy - 1][cz] * c2w,
+                                    tile[own][cy][cz - 1] * c2w};
+#pragma unroll
+            for (int d = 0; d < 3; d++)
+                J.p[d][at] = J.p[d][at] + minus_dt * (half_inv_dx * (up[d] - down[d]));
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void k_realize_P(const double *__restrict__ rho,
+                                                        double *__restrict__ P, i64 n,
+                                                        double c2w) {
+#pragma clang fp contract(off)
+    for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads)
+        P[i] = rho[i] * c2w;
+}
+
 unsigned grid_for(i64 n, i64 cap) {
     i64 blocks = (n + kThreads - 1) / kThreads;
     if (blocks > cap) blocks = cap;
@@ -393,6 +455,44 @@ extern "C" int cg_fluid_vmax(cg_ctx *c, const double *rho, const double *P, cons
     hipLaunchKernelGGL(k_vmax, dim3(1), dim3(kThreads), 0, c->stream,
                        (const double *)c->fluid_partial, (const double *)nullptr, In4{},
                        (i64)blocks, 0.0, 1, out);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_pressure_sources(cg_ctx *c, const double *rho, const double *rho_lo,
+                                         const double *rho_hi, double *P, void *const *J,
+                                         int64_t gridsize, int64_t nxl, double c2w,
+                                         double minus_dt, double half_inv_dx) {
+    CG_CHECK(c && P, "cg_fluid_pressure_sources: null argument");
+    const void *own[1] = {rho}, *lo[1] = {rho_lo}, *hi[1] = {rho_hi};
+    Layers r;
+    if (take_layers("cg_fluid_pressure_sources", &r, 1, own, rho_lo ? lo : nullptr,
+                    rho_hi ? hi : nullptr))
+        return 1;
+    // (the realisation alone reads no neighbour: any number of own layers, no lo and hi)
+    if (check_shape("cg_fluid_pressure_sources", gridsize, nxl, J && rho_lo == nullptr, 1))
+        return 1;
+    CG_CHECK((const double *)P != rho, "cg_fluid_pressure_sources: 𝒫 and ϱ are one grid");
+    if (!J) {   // the realisation alone
+        const i64 n = nxl * gridsize * gridsize;
+        hipLaunchKernelGGL(k_realize_P, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, rho,
+                           P, n, c2w);
+        CG_LAUNCH_CHECK();
+        return 0;
+    }
+    Out4 j{};
+    for (int d = 0; d < 3; d++) {
+        // the stencil must not read what the pass writes
+        CG_CHECK(J[d] && J[d] != (const void *)rho && J[d] != (void *)P,
+                 "cg_fluid_pressure_sources: J grid %d", d);
+        for (int e = 0; e < d; e++)
+            CG_CHECK(J[d] != J[e], "cg_fluid_pressure_sources: J grids %d and %d are one", e, d);
+        j.p[d] = (double *)J[d];
+    }
+    const dim3 grid((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
+                    (unsigned)((nxl + kXC - 1) / kXC));
+    hipLaunchKernelGGL(k_pressure_sources, grid, dim3(kThreads), 0, c->stream, r, P, j, (int)gridsize,
+                       (int)nxl, c2w, minus_dt, half_inv_dx);
     CG_LAUNCH_CHECK();
     return 0;
 }

@@ -1,15 +1,21 @@
-"""concept_amd.fluid — the flux terms of the MacCormack scheme for fluid components
-(fluid.py:724-961, 1079-1363 of the reference) on the GPU (csrc/cg_fluid.hip).
+"""concept_amd.fluid — the MacCormack scheme for fluid components (fluid.py:724-1067, 1079-1363 of
+the reference) on the GPU (csrc/cg_fluid.hip).
 
-In scope: a fluid with non-linear ϱ and J (boltzmann_order = 1, closure 'truncate') and
-w_eff = 0: the two MacCormack steps with their vacuum check and correction, the eight-fold cycle
-of step directions, v_max and the Courant limit.  Out of scope (drift() raises): the internal
-sources (pressure gradient, Hubble term, ς: maccormack_internal_sources), Kurganov-Tadmor, and
-linear variables realised by CLASS.
+In scope: a fluid with non-linear ϱ and J (boltzmann_order = 1, closure 'truncate') and a
+constant equation of state P = wρ (select_eos_w; the reference's w_type 'constant'): the two
+MacCormack steps with their vacuum check and correction, the eight-fold cycle of step directions,
+v_max with the sound speed and the Courant limit, and for w ≠ 0 the realisation 𝒫 = ϱ c²w and the
+pressure term of the Euler equation (realize_𝒫, internal_sources, apply_internal_sources).  A
+w = 0 component takes the kernels and launches of the flux terms alone.  Out of scope (the
+functions raise and name the missing piece): boltzmann_order > 1 and the shear term (ς), closure
+'class' and linear variables realised by CLASS, a w that is not a constant number, decaying
+species (mom_decay_factor), Kurganov-Tadmor.  The Hubble term of the continuity equation needs
+approximations['P=wρ'] off, which the reference rules out for this scope (species.py:1678-1685).
 
 Use is explicit — nothing calls this module on its own:
 
-    stepper.Timeloop(comps, fluid_drift=fluid.drift, fluid_limiter=fluid.courant_limit)
+    stepper.Timeloop(comps, fluid_drift=fluid.drift, fluid_limiter=fluid.courant_limit,
+                     fluid_sources=fluid.apply_internal_sources)   # the last for w ≠ 0
 
 The starred grids of a component, its fac_time grid and the device flag are allocated on its
 first maccormack(), the Δ buffers on its first vacuum sweep.  On several x-slab domains
@@ -94,12 +100,79 @@ def _check_scope(component, a):
     if component.boltzmann_order > 1:
         raise ConceptGPUError(
             f'{component.name}: boltzmann_order = {component.boltzmann_order}: the non-linear '
-            'evolution of ς and 𝒫 (maccormack_internal_sources) is not implemented')
-    w_eff = component.w_eff(a=a)
-    if w_eff != 0:
+            'evolution of ς and 𝒫 (the shear term of maccormack_internal_sources) is not '
+            'implemented')
+    closure = getattr(component, 'boltzmann_closure', 'truncate')
+    if closure != 'truncate':
         raise ConceptGPUError(
-            f'{component.name}: w_eff = {w_eff}: the internal sources of a fluid with pressure '
-            '(pressure gradient, Hubble term: maccormack_internal_sources) are not implemented')
+            f'{component.name}: Boltzmann closure "{closure}": realising ς with CLASS (the shear '
+            'term of maccormack_internal_sources) is not implemented, only "truncate"')
+    # a constant w (the reference's w_type 'constant'), for which w_eff = w at all times
+    w_eff = component.w_eff(a=a)
+    w = getattr(component, 'w_constant', 0.0)
+    if getattr(component, 'w_type', 'constant') != 'constant' or w_eff != w:
+        raise ConceptGPUError(
+            f'{component.name}: w_eff = {w_eff} at a = {a} with the constant w = {w}: an equation '
+            'of state that varies in time (w from CLASS, an expression or a table; decaying '
+            'species) is not implemented')
+    if w != 0 and not component.approximations['P=wρ']:
+        # (unreachable through Component: species.py:1678-1685 forces the approximation on)
+        raise ConceptGPUError(
+            f'{component.name}: w = {w} without the P=wρ approximation: a non-linear 𝒫 and the '
+            'Hubble term of the continuity equation (fluid.py:1059-1067) are not implemented')
+
+
+def _c2w(component, a):
+    return component.params.light_speed**2*component.w(a=a)
+
+
+def realize_𝒫(component, a=1.0):
+    """realize_if_linear(2, 'trace') under the P=wρ approximation (realize_approximative,
+    ic.py:495-509): 𝒫 = ϱ*(c²w)."""
+    _check_scope(component, a)
+    check(_L.cg_fluid_pressure_sources(
+        _ctx(component), _ptr(component.ϱ), None, None, _ptr(component.𝒫), None,
+        component.gridsize, component.nxl, float(_c2w(component, a)), 0.0, 0.0))
+
+
+def internal_sources(component, ᔑdt, a_next=-1):
+    """maccormack_internal_sources (fluid.py:990-1067) within scope: the pressure term of the
+    Euler equation, ΔJⁱ = -ᔑa**(-3*w_eff)dt ∂ⁱ𝒫, with the order-2 difference of diff_domaingrid
+    (mesh.py:4966-4970).  The reference reads the 𝒫 grid that kick_long realised just before
+    (main.py:1133-1138); here the same pass realises it, 𝒫 = ϱ*(c²w), and forms the
+    neighbours' values by the same product.  The shear term belongs to boltzmann_order > 1 or
+    closure 'class' (refused), the Hubble term of the continuity equation to
+    not approximations['P=wρ'], which species.py:1678-1685 rules out for this scope."""
+    a = a_next if a_next != -1 else 1.0
+    _check_scope(component, a)
+    p = component.params
+    Δx = p.boxsize/component.gridsize
+    lo, hi = _neighbour_layers(component, [component.ϱ], 1)
+    check(_L.cg_fluid_pressure_sources(
+        _ctx(component), _ptr(component.ϱ), _ptr(lo[0]) if lo is not None else None,
+        _ptr(hi[0]) if hi is not None else None, _ptr(component.𝒫), _ptrs(list(component.J)),
+        component.gridsize, component.nxl, float(_c2w(component, a)),
+        float(-ᔑdt['a**(-3*w_eff)', component.name]), float((1/2)/Δx)))
+
+
+def apply_internal_sources(component, ᔑdt, a_next=-1):
+    """Component.apply_internal_sources (species.py:2812-2921) within scope; the `fluid_sources`
+    hook of stepper.Timeloop.  Nothing happens for w = 0, exactly as the reference's condition
+    (species.py:2886-2889) with the Hubble and shear terms out of scope.  The mom_decay_factor
+    of species.py:2840-2865 is 1 for a_next = -1; otherwise the reference scales J by it only
+    for components holding the CLASS species 'dcdm' — decaying species are out of scope, so it
+    is never applied here."""
+    if component.representation != 'fluid':
+        return   # particle components have no special internal source terms
+    scheme = is_selected(component, component.params.fluid_scheme_select)
+    if scheme != 'maccormack':
+        raise ConceptGPUError(
+            f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
+            'Kurganov-Tadmor is outside this path)')
+    _check_scope(component, a_next if a_next != -1 else 1.0)
+    if component.boltzmann_order > 0 and not (component.w_type == 'constant'
+                                              and component.w_constant == 0):
+        internal_sources(component, ᔑdt, a_next)
 
 
 def maccormack_step(component, ᔑdt, steps, mc_step, halve=False):
@@ -185,7 +258,10 @@ def maccormack(component, ᔑdt, a_next=-1, record=None):
     attempts of the two steps of the last call, component.maccormack_sweeps the vacuum sweeps."""
     if component.boltzmann_order == 0:
         return   # no J variable: nothing to do (fluid.py:727-730)
-    _check_scope(component, a_next if a_next != -1 else 1.0)
+    a = a_next if a_next != -1 else 1.0
+    _check_scope(component, a)
+    # (a w = 0 component takes the path it always took: its 𝒫 grid is left as it is)
+    pressure = getattr(component, 'w_constant', 0.0) != 0
     mc = component.params.fluid_options['maccormack']
     max_vacuum_corrections = [component.gridsize if v == 'gridsize' else v for v in
                               is_selected(component, mc['max_vacuum_corrections_select'])]
@@ -201,6 +277,10 @@ def maccormack(component, ᔑdt, a_next=-1, record=None):
             if attempt == 0 or mc_step == 0:
                 # a second step that no sweep can follow leaves the halved values at once
                 halved = mc_step == 1 and not correct
+                if mc_step == 0 and pressure:
+                    # 𝒫 is re-realised from the unstarred ϱ before every first step
+                    # (fluid.py:912-913) and used as it is in the second
+                    realize_𝒫(component, a)
                 maccormack_step(component, ᔑdt, steps, mc_step, halve=halved)
             if correct:
                 if not correct_vacuum(component, mc_step, record):
@@ -234,8 +314,9 @@ def drift(component, ᔑdt, a_end=-1):
 
 
 def v_max(component, a):
-    """measure(component, 'v_max') for a fluid with non-linear J (analysis.py:3940-3963; the
-    sound speed light_speed*sqrt(w)/a is 0 for the w = 0 this module accepts)."""
+    """measure(component, 'v_max') for a fluid with non-linear J (analysis.py:3940-3963): the
+    largest bulk velocity plus the sound speed light_speed*sqrt(w)/a.  The 𝒫 grid is read as it
+    stands (realize_𝒫 or the last source pass filled it)."""
     _check_scope(component, a)
     if component.boltzmann_order == 0:
         return 0.0
@@ -249,7 +330,12 @@ def v_max(component, a):
         J_over_ϱ_plus_𝒫_2_max = float(
             component.comm.all_gather_floats([J_over_ϱ_plus_𝒫_2_max]).max())
     w_eff = component.w_eff(a=a)
-    return a**(3*w_eff - 2)*math.sqrt(J_over_ϱ_plus_𝒫_2_max)
+    v = a**(3*w_eff - 2)*math.sqrt(J_over_ϱ_plus_𝒫_2_max)
+    # the global sound speed (analysis.py:3956-3963); a w = 0 component returns what it did
+    w = getattr(component, 'w_constant', 0.0)
+    if w != 0:
+        v += component.params.light_speed*math.sqrt(w)/a
+    return v
 
 
 def courant_limit(component, a):

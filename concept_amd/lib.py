@@ -154,6 +154,8 @@ SYMBOLS = {
     'cg_fluid_vacuum_gather': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl]),
     'cg_fluid_vacuum_apply': (_int, [_vp, _vp, _vp, _i64]),
     'cg_fluid_vmax': (_int, [_vp, _vp, _vp, _vp, _i64, _dbl, _vp]),
+    'cg_fluid_pressure_sources': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl,
+                                         _dbl]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -27,6 +27,8 @@ from .mesh import get_mesh
 PotentialGridsizes = collections.namedtuple('PotentialGridsizes', ('upstream', 'downstream'))
 
 
+APPROXIMATIONS_IMPLEMENTED = ('P=wρ',)   # species.py:4379-4381
+
 _BEGIN_WRITES = ('pos', 'Δmom', 'rung_indices_jumped')
 
 
@@ -111,6 +113,7 @@ class Component:
             self.representation = 'fluid'
             self.boltzmann_order = int(boltzmann_order)
             self._init_fluid(int(gridsize))
+        self._init_eos()
         self._init_forces()
         if self.representation == 'particles':
             # one domain: the N particles live here from the start; several: populate()
@@ -362,8 +365,61 @@ class Component:
             return mean
         raise ConceptGPUError(f'Cannot determine ϱ_bar for {self.name}')
 
+    def _init_eos(self):
+        """The equation of state (init_w, species.py:3186-3193: w_type 'constant' only), the
+        Boltzmann closure and the approximations with the reference's key folding and forcing
+        (species.py:1313-1352, 1657-1685).  Particle components keep w = 0."""
+        p = self.params
+        self.w_type = 'constant'
+        self.w_constant = 0.0
+        if self.representation == 'fluid':
+            self.w_constant = float(commons.is_selected(self, p.select_eos_w, default=0.0))
+            # (species.py:2979-3009: no phantom w with non-linear ϱ, no w < 0 with non-linear J)
+            if self.w_constant < 0 and self.boltzmann_order > 0:
+                raise ConceptGPUError(
+                    f'The equation of state parameter w for {self.name} is {self.w_constant} '
+                    '< 0. This is disallowed for components with non-linear J.')
+        self.boltzmann_closure = commons.is_selected(self, p.select_boltzmann_closure,
+                                                     default='truncate')
+        given = commons.is_selected(self, p.select_approximations, accumulate=True) or {}
+        approximations = {}
+        for approximation, value in given.items():
+            for char in ' *×^':
+                approximation = approximation.replace(char, '')
+            for s_ in ('\rho', r'\rho', 'rho'):
+                approximation = approximation.replace(s_, 'ρ')
+            if approximation in ('P=wρ', 'P=ρw', 'wρ=P', 'ρw=P'):
+                approximation = 'P=wρ'
+            if approximation not in APPROXIMATIONS_IMPLEMENTED:
+                raise ConceptGPUError(f'{self.name} was initialised with the unknown '
+                                      f'approximation "{approximation}"')
+            approximations[approximation] = bool(value)
+        for approximation in APPROXIMATIONS_IMPLEMENTED:
+            approximations.setdefault(approximation, False)
+        if self.representation == 'particles':
+            approximations['P=wρ'] = True
+        elif not approximations['P=wρ'] and self.boltzmann_closure == 'truncate':
+            if self.boltzmann_order == 1:
+                import warnings
+                warnings.warn(
+                    f'The P=wρ approximation has been switched on for {self.name} '
+                    'because the non-linear Boltzmann hierarchy is truncated after the '
+                    'non-linear fluid variable Jⁱ, while 𝒫 is part of the next fluid variable.')
+                approximations['P=wρ'] = True
+            elif self.boltzmann_order < 1:
+                approximations['P=wρ'] = True   # (no 𝒫 variable at all)
+        # (asciify('P=wρ') of the reference: both spellings are keys)
+        approximations['P=wrho'] = approximations['P=wρ']
+        self.approximations = approximations
+
+    def w(self, a=1.0):
+        """the equation of state parameter (Component.w, species.py:2940-3010), constant"""
+        return self.w_constant
+
     def w_eff(self, a=1.0):
-        return 0.0  # matter; decaying species are out of scope
+        """w_eff = w for a constant w (w_eff_type 'constant', species.py:3020-3022,
+        3440-3452); decaying species are out of scope"""
+        return self.w(a=a)
 
     def host(self, var, original_order=True):
         """Host copy of 'pos' | 'mom' | 'Δmom' | 'ids' | 'rung_indices' — of ALL N particles,

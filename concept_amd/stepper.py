@@ -395,9 +395,14 @@ class RungStepper:
             # kernels want tile order — once per base step, not once per sub-step
             if c.representation == 'particles' and not c.tiles_exact and c._store is not None:
                 c.tile_sort()
+        self._apply_internal_sources(ᔑdt, t_end)
         for force, method, receivers, suppliers in interactions.find_interactions(
                 self.components, 'long-range'):
             getattr(interactions, force)(method, receivers, suppliers, ᔑdt, 'long-range', False)
+
+    def _apply_internal_sources(self, ᔑdt, t_end):
+        """the internal source terms of main.py:1129-1138, before the interactions: none for
+        particle components (Timeloop calls its fluid_sources hook for fluids)"""
 
     # -- main.kick_short (main.py:1173-1262) ----------------------------------
     def kick_short(self, Δt, fake=False):
@@ -662,7 +667,7 @@ class Timeloop(RungStepper):
     Δt_period = 1*8
 
     def __init__(self, components, cosmology=None, on_dump=None, on_step=None, streaming=None,
-                 fluid_drift=None, fluid_limiter=None):
+                 fluid_drift=None, fluid_limiter=None, fluid_sources=None):
         """fluid_drift(component, ᔑdt, a_end): the hook for fluid components.  Their solvers
         (fluid.py: MacCormack / Kurganov-Tadmor on ϱ, J) are outside this path, but the loop
         around them is not: with the hook given, fluid components ride along — they take
@@ -672,12 +677,24 @@ class Timeloop(RungStepper):
         over the whole step, before the particles' sub-steps) with the step's integrals and the
         scale factor at its end; it advances component.ϱ / component.J in place.
         fluid_limiter(component, a) -> Δt: the fluid's own limit on the base step (the
-        reference's Courant condition, main.py:773-836), optional."""
+        reference's Courant condition, main.py:773-836), optional.
+        fluid_sources(component, ᔑdt, a_end): the internal source terms of a fluid (pressure
+        gradient; fluid.apply_internal_sources), called in every kick_long() for every fluid
+        component before the interactions, with the kick's integrals and the scale factor at
+        its end (main.py:1129-1138).  A fluid with w ≠ 0 needs it."""
         p = components[0].params
         self.cosmo = cosmology or Cosmology(p)
         self.cosmo.init_time()
         self.fluid_drift, self.fluid_limiter = fluid_drift, fluid_limiter
+        self.fluid_sources = fluid_sources
         for c in components:
+            if (c.representation != 'particles' and fluid_sources is None
+                    and getattr(c, 'w_constant', 0.0) != 0):
+                raise ConceptGPUError(
+                    f'Timeloop: {c.name} is a fluid component with w = {c.w_constant}: its '
+                    'pressure term (fluid.py) is outside this path: pass '
+                    'fluid_sources=callback(component, ᔑdt, a_end), e.g. '
+                    'fluid.apply_internal_sources, to apply the internal sources to J')
             if c.representation != 'particles' and fluid_drift is None:
                 raise ConceptGPUError(
                     f'Timeloop: {c.name} is a fluid component; fluids take part in gravity() '
@@ -982,6 +999,14 @@ class Timeloop(RungStepper):
         if cosmo.enable_Hubble and cosmo.t + Δt_new > cosmo.cosmic_time(1):
             return Δt, 'a ≈ 1'
         return Δt_new, ''
+
+    def _apply_internal_sources(self, ᔑdt, t_end):
+        if self.fluid_sources is None:
+            return
+        a_end = self.cosmo.scale_factor(t_end)
+        for c in self.components:
+            if c.representation == 'fluid':
+                self.fluid_sources(c, ᔑdt, a_end)
 
     def drift_fluids(self, Δt, sync_time):
         """main.drift_fluids (main.py:1279-1299): always over a full base step"""

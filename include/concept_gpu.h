@@ -753,7 +753,19 @@ int cg_render2d_apply(cg_ctx *ctx, double *image /*DEV n*/, int64_t n, double ex
  *   input gives the same bits on any number of domains.
  * cg_fluid_vacuum_apply: var[v] += delta[v] (fluid.py:1333-1340).
  * cg_fluid_vmax: out[0] (DEV) = max over n cells of (Jx² + Jy² + Jz²)/(ϱ + inv_c2 𝒫)²
- *   (analysis.py:3940-3955; 0 for an all-static fluid). */
+ *   (analysis.py:3940-3955; 0 for an all-static fluid).
+ * cg_fluid_pressure_sources: the realisation of 𝒫 under the P = wρ approximation
+ *   (realize_approximative, ic.py:503-508) and the pressure term of maccormack_internal_sources
+ *   (fluid.py:1044-1057) with its diff_domaingrid of order 2 (mesh.py:4966-4970), in one pass:
+ *   P[cell] = rho[cell]*c2w, J[i][cell] += minus_dt*(half_inv_dx*(𝒫[+1_i] - 𝒫[-1_i])), the
+ *   neighbours' 𝒫 formed from rho by the same product.  rho with H = 1 (rho_lo / rho_hi: one
+ *   layer each, or both NULL); c2w: light_speed**2*w; minus_dt: -ᔑdt['a**(-3*w_eff)'];
+ *   half_inv_dx: (1/2)/Δx.  J NULL: the realisation alone (fluid.py:912-913).  P and J are
+ *   written in place; none of them may be rho. */
+int cg_fluid_pressure_sources(cg_ctx *ctx, const double *rho /*DEV*/, const double *rho_lo,
+                              const double *rho_hi, double *P /*DEV*/,
+                              void *const *J /*HOST 3 or NULL*/, int64_t gridsize, int64_t nxl,
+                              double c2w, double minus_dt, double half_inv_dx);
 int cg_fluid_mc_step(cg_ctx *ctx, const void *const *src /*HOST 5*/,
                      const void *const *src_lo /*HOST 5 or NULL*/,
                      const void *const *src_hi /*HOST 5 or NULL*/, void *const *dst /*HOST 4*/,

@@ -9,7 +9,8 @@ Bytes per cell and call, FP64: a step reads five grids and writ
 the second step also reads the four it adds to: 104 B); detection reads two grids and writes
 fac_time after the first step (24 B), one grid after the second (16 B); the epilogue halves four grids in place (64 B) and clears the four
 starred ones (32 B).  A sweep adds the gather (fac_time and the four variables in, four Δ out:
-72 B, its neighbour reads served by the caches) and the apply (96 B)."""
+72 B, its neighbour reads served by the caches) and the apply (96 B).  Last, ten source passes of
+a w = 0.2 fluid (fluid.internal_sources), 64 B per cell."""
 import argparse
 import json
 import os
@@ -23,6 +24,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HBM_PEAK = 8e12   # bytes/s
 BYTES_SMOOTH = 72 + 24 + 104 + 16 + 64 + 32   # per cell and call
 BYTES_SWEEP = 72 + 96                      # per cell and sweep
+BYTES_SOURCES = 8 + 8 + 48                 # per cell and source pass: ϱ in, 𝒫 out, three J in and out
 
 
 def fields(gs, void, device):
@@ -83,6 +85,30 @@ def main():
             'min_rho': float(c.ϱ.min().item())}
         del c
         torch.cuda.empty_cache()
+    # the source pass of a w = 0.2 fluid (fluid.internal_sources: 𝒫 = ϱ c²w and the pressure term
+    # of the Euler equation in one pass): reads ϱ, writes 𝒫, reads and writes three J grids
+    commons.load_params({'boxsize': float(gs), 'select_eos_w': {'all': 0.2},
+                         'select_approximations': {'P=wρ': True}})
+    c = Component('fluid', 'matter', gridsize=gs, boltzmann_order=1)
+    ϱ, J = fields(gs, False, device)
+    c.ϱ.copy_(ϱ)
+    for d in range(3):
+        c.J[d].copy_(J[d])
+    del ϱ, J
+    ᔑdt = {'1': 1e-6, ('a**(-3*w_eff)', c.name): 1e-6}
+    fluid.internal_sources(c, ᔑdt)
+    torch.cuda.synchronize()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(args.calls):
+        fluid.internal_sources(c, ᔑdt)
+    end.record()
+    torch.cuda.synchronize()
+    ms = start.elapsed_time(end)/args.calls
+    hbm_ms = gs**3*BYTES_SOURCES/HBM_PEAK*1e3
+    result['pressure_sources'] = {
+        'ms_per_call': round(ms, 4), 'bytes_per_call': int(gs**3*BYTES_SOURCES),
+        'hbm_ms_at_8TBps': round(hbm_ms, 4), 'fraction_of_hbm_rate': round(hbm_ms/ms, 4)}
     line = json.dumps(result)
     print(line)
     if args.out:
