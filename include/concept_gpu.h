@@ -571,6 +571,12 @@ int cg_emigrant_dest(cg_ctx *ctx, const double *pos /*DEV*/, const double *mom /
                      const int64_t *idx /*DEV cap*/, const uint32_t *count /*DEV 1*/, int64_t cap,
                      double dt_over_mass, int32_t *dest /*DEV cap*/,
                      int32_t *send_counts /*DEV P*/);
+/* Owner of a particle: the x-slab that holds its lower CIC cell, by the deposit's own index map
+ * (mesh.py:1577-1606) — floor(x/cellsize - 0.5*cell_centered) except within a few ulp of boxsize
+ * around a cell face: the map's factors (1 +- machine_eps) move every face up by a relative
+ * 2^-52, so that a particle exactly ON a face belongs to the cell (and the slab) below it.  The
+ * sort, the fused pass, cg_region_insert and the deposit use the same map: an owned particle's
+ * cloud always lies in the owner's layers. */
 int cg_owner_rank(cg_ctx *ctx, const double *pos /*DEV 3n*/, int64_t n,
                   int32_t *owner_out /*DEV n*/);
 /* The fused step of the x-slab path: cg_owner_rank_drifted gives the owner of every particle
