@@ -606,7 +606,7 @@ def _load_render2D_params(p, user):
 def _load_fluid_params(p, user):
     """fluid_scheme_select and fluid_options (commons.py:3940-4030) with the reference's
     defaults and key folding.  The Kurganov-Tadmor options are loaded as the reference loads
-    them; concept_amd.fluid refuses the scheme itself."""
+    them, for fluid.kurganov_tadmor."""
     fold = lambda s: str(s).lower().replace(' ', '').replace('-', '')
     sel = {'all': 'MacCormack'}
     if user.get('fluid_scheme_select'):

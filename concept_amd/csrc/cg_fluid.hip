@@ -10,6 +10,8 @@
 //   k_pressure_sources  𝒫 = ϱ (c²w) and the pressure term of the Euler equation, one pass
 //                                                         ic.py:503-508, fluid.py:1044-1057, mesh.py:4966-4970
 //   k_realize_P       𝒫 = ϱ (c²w) alone                                   ic.py:503-508
+//   k_kt_step         one Runge-Kutta step of kurganov_tadmor, all four variables and the
+//                     realisation of 𝒫 in one pass, per flux limiter     fluid.py:103-673
 //
 // A fluid grid is this domain's layers of the global grid, double[nxl][g][g] without ghosts
 // (species.Component).  y and z are periodic by index wrap.  In x a kernel reads up to H layers
@@ -306,6 +308,238 @@ __global__ __launch_bounds__(kThreads) void k_realize_P(const double *__restrict
         P[i] = rho[i] * c2w;
 }
 
+// -- the Kurganov-Tadmor scheme (fluid.py:103-673) -------------------------------------------------
+constexpr int kKtXC = 16;   // layers a workgroup of the Kurganov-Tadmor step walks along x
+constexpr int kKtH = 2;     // cells the stencil reaches to either side
+
+enum KtLimiter {
+    kMinmod, kMonotonizedCentral, kOspre, kSuperbee, kSweby, kUmist, kVanAlbada, kVanLeer, kKoren,
+    kLimiters
+};
+
+// what a step needs besides the grids, formed by the caller as the reference's ℝ[...] expressions
+struct KtFactors {
+    double c2w;          // light_speed**2*w
+    double inv_c2;       // light_speed**(-2)
+    double a_pow;        // a**(3*w_eff - 2)
+    double soundspeed;   // light_speed*sqrt(w)/a
+    double f_J;          // ᔑdt['a**(3*w_eff-2)']/ᔑdt['1']
+    double f_P;          // ᔑdt['a**(-3*w_eff)']/ᔑdt['1']
+    double to_delta;     // (1 + rk_step)/rk_order*ᔑdt['1']/Δx
+};
+
+// slope_ratio, fluid.py:516-526
+__device__ inline double kt_slope_ratio(double numerator, double denominator) {
+    constexpr double eps = 1e+2 * 2.220446049250313e-16;
+    constexpr double inv_eps = 1 / eps;
+    if (fabs(numerator) < eps) return 0;
+    if (fabs(denominator) < eps) {
+        if (numerator > eps) return inv_eps;
+        if (numerator < -eps) return -inv_eps;
+    }
+    return numerator / denominator;
+}
+
+// the flux limiters, fluid.py:588-673, branch by branch
+template <int LIM>
+__device__ inline double kt_limiter(double r) {
+    if constexpr (LIM == kMinmod) {
+        if (r > 1) return 1;
+        if (r > 0) return r;
+        return 0;
+    } else if constexpr (LIM == kMonotonizedCentral) {
+        if (r > 3) return 2;
+        if (r > 1. / 3.) return 0.5 * (r + 1);
+        if (r > 0) return 2 * r;
+        return 0;
+    } else if constexpr (LIM == kOspre) {
+        if (r > 0) {
+            const double r2 = r * r, s = r2 + r;
+            return 1.5 * s / (s + 1);
+        }
+        return 0;
+    } else if constexpr (LIM == kSuperbee) {
+        if (r > 2) return 2;
+        if (r > 1) return r;
+        if (r > 0.5) return 1;
+        if (r > 0) return 2 * r;
+        return 0;
+    } else if constexpr (LIM == kSweby) {
+        constexpr double beta = 1.5, inv_beta = 1 / beta;
+        if (r > beta) return beta;
+        if (r > 1) return r;
+        if (r > inv_beta) return 1;
+        if (r > 0) return beta * r;
+        return 0;
+    } else if constexpr (LIM == kUmist) {
+        if (r > 5) return 2;
+        if (r > 1) return 0.75 + 0.25 * r;
+        if (r > 0.2) return 0.25 + 0.75 * r;
+        if (r > 0) return 2 * r;
+        return 0;
+    } else if constexpr (LIM == kVanAlbada) {
+        if (r > 0) {
+            const double r2 = r * r;
+            return (r2 + r) / (r2 + 1);
+        }
+        return 0;
+    } else if constexpr (LIM == kVanLeer) {
+        if (r > 0) return 2 * r / (1 + r);
+        return 0;
+    } else {
+        static_assert(LIM == kKoren, "unknown flux limiter");
+        if (r > 2.5) return 2;
+        if (r > 0.25) return 1. / 3. * (1 + 2 * r);
+        if (r > 0) return 2 * r;
+        return 0;
+    }
+}
+
+// at_interface, fluid.py:486-504: the left and right value at the interface between the cells m
+// and c, from the cells m2, m, c, p along one direction
+template <int LIM>
+__device__ inline void kt_at_interface(double m2, double m, double c, double p, double &left,
+                                       double &right) {
+    const double dcm = c - m, dpc = p - c;
+    const double r_m = kt_slope_ratio(m - m2, dcm);
+    const double r_c = kt_slope_ratio(dcm, dpc);
+    left = m + 0.5 * kt_limiter<LIM>(r_m) * dcm;
+    right = c - (0.5 * kt_limiter<LIM>(r_c)) * dpc;
+}
+
+// The numerical fluxes of ϱ, Jx, Jy, Jz through one interface across direction D
+// (fluid.py:275-297, 373-418 with kurganov_tadmor_flux, :541-554), from the four cells m2, m, c, p
+// of every variable along D; q[0] = ϱ, q[1 + i] = Jⁱ.  The interface values of ϱ, 𝒫 and J_D and the
+// propagation speed do not depend on the variable that flows: formed once.  𝒫 of a cell is the
+// product that fills the 𝒫 grid.
+template <int LIM, int D>
+__device__ inline void kt_flux(const double (&q)[4][4], const KtFactors &k, double (&flux)[4]) {
+    double face[4][2], P[2], den[2], v[2];
+#pragma unroll
+    for (int var = 0; var < 4; var++)
+        kt_at_interface<LIM>(q[var][0], q[var][1], q[var][2], q[var][3], face[var][0], face[var][1]);
+    kt_at_interface<LIM>(q[0][0] * k.c2w, q[0][1] * k.c2w, q[0][2] * k.c2w, q[0][3] * k.c2w, P[0],
+                         P[1]);
+#pragma unroll
+    for (int lr = 0; lr < 2; lr++) {
+        den[lr] = face[0][lr] + k.inv_c2 * P[lr];
+        v[lr] = fabs(k.a_pow * face[1 + D][lr] / den[lr]) + k.soundspeed;
+    }
+    // pairmax (commons.py:5091-5092)
+    const double speed = v[0] * (double)(v[1] <= v[0]) + v[1] * (double)(v[0] < v[1]);
+    const bool use_P = k.c2w != 0;
+    double f[2];
+#pragma unroll
+    for (int lr = 0; lr < 2; lr++) f[lr] = k.f_J * face[1 + D][lr];
+    flux[0] = 0.5 * ((f[1] + f[0]) - speed * (face[0][1] - face[0][0]));
+#pragma unroll
+    for (int m = 0; m < 3; m++) {
+#pragma unroll
+        for (int lr = 0; lr < 2; lr++) {
+            f[lr] = k.f_J * (face[1 + m][lr] * face[1 + D][lr] / den[lr]);
+            if (m == D && use_P) f[lr] = f[lr] + k.f_P * P[lr];
+        }
+        flux[1 + m] = 0.5 * ((f[1] + f[0]) - speed * (face[1 + m][1] - face[1 + m][0]));
+    }
+}
+
+// One Runge-Kutta step of kurganov_tadmor (fluid.py:103-464) with its finalize_rk_step
+// (:565-586), as a gather.  The reference scatters Δ = flux*to_delta of every interface to the two
+// cells beside it, in loops over the variable, the direction and the interfaces in ascending
+// (i, j, k); a cell therefore receives, per variable, +Δ(x-½), -Δ(x+½), +Δ(y-½), -Δ(y+½),
+// +Δ(z-½), -Δ(z+½) in this order, onto 0 in step 0 (the unstarred value is added last) and onto
+// the unstarred value in step 1.  src: the grids the stencil reads (the unstarred in step 0, the
+// starred in step 1), with kKtH layers beyond the own ones; dst: the grids written (the starred in
+// step 0, the unstarred in step 1).  P receives the realisation ϱ (c²w) of the grid that is read
+// (realize_if_linear(2, 'trace', use_gridˣ), fluid.py:240).
+// A workgroup owns a tile of kTY x kTZ cells and walks kKtXC layers upwards.  A thread keeps the
+// four x-neighbours of the next x-interface of its column in registers and hands the flux through
+// x+½ to the next layer as its flux through x-½; the own layer is staged in LDS with a halo of two
+// cells in y and z.
+template <int LIM>
+__global__ __launch_bounds__(kThreads) void k_kt_step(LayersN<4> src, Out4 dst,
+                                                      double *__restrict__ P, int g, int nxl,
+                                                      int rk_step, KtFactors k) {
+#pragma clang fp contract(off)
+    __shared__ double tile[4][kTY + 2 * kKtH][kTZ + 2 * kKtH];
+    const int tz = threadIdx.x % kTZ, ty = threadIdx.x / kTZ;
+    const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
+    const int xa = blockIdx.z * kKtXC, xb = xa + kKtXC < nxl ? xa + kKtXC : nxl;
+    const i64 g2 = (i64)g * g;
+    const bool mine = y0 + ty < g && z0 + tz < g;
+    const int cy = ty + kKtH, cz = tz + kKtH;
+    const i64 col = mine ? (i64)(y0 + ty) * g + (z0 + tz) : 0;
+    // the cells xa-2 .. xa+1 of the column, and the flux through xa-½
+    double w[4][4], lower[4] = {0, 0, 0, 0};
+    if (mine) {
+#pragma unroll
+        for (int var = 0; var < 4; var++)
+#pragma unroll
+            for (int o = 0; o < 4; o++)
+                w[var][o] = layer_of<kKtH>(src.v[var], xa - 2 + o, nxl, g2)[col];
+        kt_flux<LIM, 0>(w, k, lower);
+    }
+    for (int l = xa; l < xb; l++) {
+        // local (ly, lz) is cell (y0 - 2 + ly, z0 - 2 + lz) of the layer, wrapped
+        for (int e = threadIdx.x; e < (kTY + 2 * kKtH) * (kTZ + 2 * kKtH); e += kThreads) {
+            const int ly = e / (kTZ + 2 * kKtH), lz = e - ly * (kTZ + 2 * kKtH);
+            // (a partial tile's rows beyond the grid wrap as well: loaded, never used)
+            const int y = (y0 - kKtH + ly + g) % g, z = (z0 - kKtH + lz + g) % g;
+            const i64 at = (i64)y * g + z;
+#pragma unroll
+            for (int var = 0; var < 4; var++)
+                tile[var][ly][lz] = layer_of<kKtH>(src.v[var], l, nxl, g2)[at];
+        }
+        __syncthreads();
+        if (mine) {
+            const i64 at = (i64)l * g2 + col;
+            double out[4], flux[4], q[4][4];
+#pragma unroll
+            for (int var = 0; var < 4; var++) {
+                out[var] = rk_step == 0 ? 0.0 : dst.p[var][at];
+                out[var] = out[var] + lower[var] * k.to_delta;
+                // the cells l-1 .. l+2 of the column: the interface l+½
+                w[var][0] = w[var][1];
+                w[var][1] = w[var][2];
+                w[var][2] = w[var][3];
+                w[var][3] = layer_of<kKtH>(src.v[var], l + 2, nxl, g2)[col];
+            }
+            kt_flux<LIM, 0>(w, k, lower);
+#pragma unroll
+            for (int var = 0; var < 4; var++) out[var] = out[var] - lower[var] * k.to_delta;
+#pragma unroll
+            for (int side = 0; side < 2; side++) {
+#pragma unroll
+                for (int var = 0; var < 4; var++)
+#pragma unroll
+                    for (int o = 0; o < 4; o++) q[var][o] = tile[var][cy - 2 + side + o][cz];
+                kt_flux<LIM, 1>(q, k, flux);
+#pragma unroll
+                for (int var = 0; var < 4; var++)
+                    out[var] = side ? out[var] - flux[var] * k.to_delta
+                                    : out[var] + flux[var] * k.to_delta;
+            }
+#pragma unroll
+            for (int side = 0; side < 2; side++) {
+#pragma unroll
+                for (int var = 0; var < 4; var++)
+#pragma unroll
+                    for (int o = 0; o < 4; o++) q[var][o] = tile[var][cy][cz - 2 + side + o];
+                kt_flux<LIM, 2>(q, k, flux);
+#pragma unroll
+                for (int var = 0; var < 4; var++)
+                    out[var] = side ? out[var] - flux[var] * k.to_delta
+                                    : out[var] + flux[var] * k.to_delta;
+            }
+            if (P) P[at] = w[0][1] * k.c2w;
+#pragma unroll
+            for (int var = 0; var < 4; var++)
+                dst.p[var][at] = rk_step == 0 ? out[var] + w[var][1] : out[var];
+        }
+        __syncthreads();
+    }
+}
+
 unsigned grid_for(i64 n, i64 cap) {
     i64 blocks = (n + kThreads - 1) / kThreads;
     if (blocks > cap) blocks = cap;
@@ -359,6 +593,52 @@ extern "C" int cg_fluid_mc_step(cg_ctx *c, const void *const *src, const void *c
                     (unsigned)((nxl + kXC - 1) / kXC));
     hipLaunchKernelGGL(k_mc_step, grid, dim3(kThreads), 0, c->stream, s, d, (int)gridsize, (int)nxl,
                        steps[0], steps[1], steps[2], factor, inv_c2, mc_step, halve);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+namespace {
+
+template <int LIM>
+void launch_kt_step(cg_ctx *c, dim3 grid, const LayersN<4> &s, const Out4 &d, double *P, int g,
+                    int nxl, int rk_step, int limiter, const KtFactors &k) {
+    if constexpr (LIM < kLimiters) {
+        if (limiter == LIM)
+            hipLaunchKernelGGL(k_kt_step<LIM>, grid, dim3(kThreads), 0, c->stream, s, d, P, g, nxl,
+                               rk_step, k);
+        else
+            launch_kt_step<LIM + 1>(c, grid, s, d, P, g, nxl, rk_step, limiter, k);
+    }
+}
+
+}  // namespace
+
+extern "C" int cg_fluid_kt_step(cg_ctx *c, const void *const *src, const void *const *src_lo,
+                                const void *const *src_hi, void *const *dst, double *P,
+                                int64_t gridsize, int64_t nxl, int limiter, int rk_step, double c2w,
+                                double inv_c2, double a_pow, double soundspeed, double f_J,
+                                double f_P, double to_delta) {
+    CG_CHECK(c && dst, "cg_fluid_kt_step: null argument");
+    LayersN<4> s;
+    if (take_layers("cg_fluid_kt_step", s.v, 4, src, src_lo, src_hi)) return 1;
+    if (check_shape("cg_fluid_kt_step", gridsize, nxl, src_lo == nullptr, kKtH)) return 1;
+    CG_CHECK(rk_step == 0 || rk_step == 1, "cg_fluid_kt_step: rk_step %d", rk_step);
+    CG_CHECK(limiter >= 0 && limiter < kLimiters, "cg_fluid_kt_step: flux limiter %d", limiter);
+    Out4 d;
+    for (int v = 0; v < 4; v++) {
+        CG_CHECK(dst[v] && dst[v] != (void *)P, "cg_fluid_kt_step: null grid %d", v);
+        d.p[v] = (double *)dst[v];
+        // the stencil must not read what the pass writes
+        for (int u = 0; u < 4; u++) {
+            CG_CHECK(dst[v] != src[u], "cg_fluid_kt_step: grid %d is read and written", v);
+            CG_CHECK(u == v || dst[v] != dst[u], "cg_fluid_kt_step: grids %d and %d are one", u, v);
+        }
+        CG_CHECK(src[v] != (const void *)P, "cg_fluid_kt_step: 𝒫 and grid %d are one", v);
+    }
+    const dim3 grid((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
+                    (unsigned)((nxl + kKtXC - 1) / kKtXC));
+    const KtFactors k{c2w, inv_c2, a_pow, soundspeed, f_J, f_P, to_delta};
+    launch_kt_step<0>(c, grid, s, d, P, (int)gridsize, (int)nxl, rk_step, limiter, k);
     CG_LAUNCH_CHECK();
     return 0;
 }

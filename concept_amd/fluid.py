@@ -1,5 +1,5 @@
-"""concept_amd.fluid — the MacCormack scheme for fluid components (fluid.py:724-1067, 1079-1363 of
-the reference) on the GPU (csrc/cg_fluid.hip).
+"""concept_amd.fluid — the MacCormack scheme (fluid.py:724-1067, 1079-1363 of the reference) and
+the Kurganov-Tadmor scheme (fluid.py:103-673) for fluid components on the GPU (csrc/cg_fluid.hip).
 
 In scope: a fluid with non-linear ϱ and J (boltzmann_order = 1, closure 'truncate') and a
 constant equation of state P = wρ (select_eos_w; the reference's w_type 'constant'): the two
@@ -9,13 +9,20 @@ pressure term of the Euler equation (realize_𝒫, internal_sources, apply_inter
 w = 0 component takes the kernels and launches of the flux terms alone.  Out of scope (the
 functions raise and name the missing piece): boltzmann_order > 1 and the shear term (ς), closure
 'class' and linear variables realised by CLASS, a w that is not a constant number, decaying
-species (mom_decay_factor), Kurganov-Tadmor.  The Hubble term of the continuity equation needs
+species (mom_decay_factor).  The Hubble term of the continuity equation needs
 approximations['P=wρ'] off, which the reference rules out for this scope (species.py:1678-1685).
+Kurganov-Tadmor, in the same scope: Runge-Kutta orders 1 and 2 and the nine flux limiters, one
+launch per Runge-Kutta step with the pressure term in the flux (kurganov_tadmor); no vacuum
+correction exists in that scheme.
 
 Use is explicit — nothing calls this module on its own:
 
     stepper.Timeloop(comps, fluid_drift=fluid.drift, fluid_limiter=fluid.courant_limit,
                      fluid_sources=fluid.apply_internal_sources)   # the last for w ≠ 0
+
+drift() and apply_internal_sources() are the MacCormack scheme and refuse any other;
+drift_selected() and sources_selected() take their place in the call above to send every
+component to the scheme fluid_scheme_select names for it.
 
 The starred grids of a component, its fac_time grid and the device flag are allocated on its
 first maccormack(), the Δ buffers on its first vacuum sweep.  On several x-slab domains
@@ -311,6 +318,137 @@ def drift(component, ᔑdt, a_end=-1):
             f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
             'Kurganov-Tadmor is outside this path)')
     maccormack(component, ᔑdt, a_end)
+
+
+# -- the Kurganov-Tadmor scheme --------------------------------------------------------------------
+# flux_limiter_select -> the limiter id of cg_fluid_kt_step, with the reference's aliases
+# (fluid.py:208-227)
+FLUX_LIMITERS = {'minmod': 0, 'monotonizedcentral': 1, 'mc': 1, 'ospre': 2, 'superbee': 3,
+                 'sweby': 4, 'umist': 5, 'vanalbada': 6, 'vanleer': 7, 'muscl': 7, 'harmonic': 7,
+                 'koren': 8}
+
+
+def _kt_options(component):
+    return component.params.fluid_options['kurganovtadmor']
+
+
+def kt_step_scale_factors(cosmo, a, Δt):
+    """The scale factors of the two Runge-Kutta steps of order 2 under enable_Hubble
+    (fluid.py:160-173): `a` belongs to the middle of the drift of duration Δt = ᔑdt['1'], the
+    steps to the middles of its two halves.  cosmo: an integration.Cosmology with its clock
+    initialised."""
+    t_flux = cosmo.cosmic_time(a) - 0.5*Δt
+    return cosmo.scale_factor(t_flux + 0.25*Δt), cosmo.scale_factor(t_flux + 0.75*Δt)
+
+
+def kurganov_tadmor_step(component, ᔑdt, a, rk_order, rk_step, limiter):
+    """One Runge-Kutta step of kurganov_tadmor (fluid.py:174-464) and its finalize_rk_step
+    (:565-586): the starred grids from the unstarred ones (rk_step 0) or the update of the
+    unstarred ones from the starred (rk_step 1).  The 𝒫 grid receives ϱ*(c²w) of the grids the
+    step reads (realize_if_linear(2, 'trace', a, use_gridˣ), fluid.py:240; a linear 𝒫 has one
+    buffer for both views, species.py:259-275).  `a` is the scale factor of this step, limiter
+    an id of FLUX_LIMITERS."""
+    st = _state(component)
+    p = component.params
+    name = component.name
+    src, dst = (_grids(component), st.starred) if rk_step == 0 else (st.starred, _grids(component))
+    Δx = p.boxsize/component.gridsize
+    w = component.w(a=a)
+    w_eff = component.w_eff(a=a)
+    soundspeed = p.light_speed*math.sqrt(w)/a
+    # (the pressure joins the flux only for w ≠ 0, use_𝒫 of fluid.py:316)
+    f_𝒫 = ᔑdt['a**(-3*w_eff)', name]/ᔑdt['1'] if w != 0 else 0.0
+    lo, hi = _neighbour_layers(component, src, 2)
+    check(_L.cg_fluid_kt_step(
+        _ctx(component), _ptrs(src), _ptrs(lo), _ptrs(hi), _ptrs(dst), _ptr(component.𝒫),
+        component.gridsize, component.nxl, int(limiter), int(rk_step),
+        float(p.light_speed**2*w), float(p.light_speed**(-2)), float(a**(3*w_eff - 2)),
+        float(soundspeed), float(ᔑdt['a**(3*w_eff-2)', name]/ᔑdt['1']), float(f_𝒫),
+        float((1 + rk_step)/rk_order*ᔑdt['1']/Δx)))
+
+
+def kurganov_tadmor(component, ᔑdt, a, rk_order=2, cosmo=None):
+    """kurganov_tadmor (fluid.py:103-464) with finalize_rk_step (:565-586): the flux terms of
+    the continuity and Euler equations, the pressure term among them, by one (rk_order 1) or two
+    Runge-Kutta steps.  a: the scale factor the reference takes from universals.a
+    (species.py:2230).  cosmo: the integration.Cosmology that maps it onto the scale factors of
+    the two steps (kt_step_scale_factors); needed for rk_order 2 under enable_Hubble.  There is no
+    vacuum correction in this scheme."""
+    if component.boltzmann_order < 1:
+        return   # no J variable: nothing to do (fluid.py:139-142)
+    if rk_order not in (1, 2):
+        raise ConceptGPUError('Only Runge-Kutta orders 1 and 2 are implemented for the '
+                              f'Kurganov-Tadmor method ({component.name}: {rk_order})')
+    name = is_selected(component, _kt_options(component)['flux_limiter_select'])
+    if name not in FLUX_LIMITERS:
+        raise ConceptGPUError(f'Flux limiter "{name}" not implemented')
+    _check_scope(component, a)
+    a_steps = [a]*rk_order
+    if component.params.enable_Hubble and rk_order == 2:
+        if cosmo is None:
+            raise ConceptGPUError(
+                f'{component.name}: Kurganov-Tadmor of Runge-Kutta order 2 with enable_Hubble '
+                'needs cosmo, the integration.Cosmology that gives the scale factors of its two '
+                'steps')
+        a_steps = kt_step_scale_factors(cosmo, a, ᔑdt['1'])
+    for rk_step in range(rk_order):
+        _check_scope(component, a_steps[rk_step])
+        kurganov_tadmor_step(component, ᔑdt, a_steps[rk_step], rk_order, rk_step,
+                             FLUX_LIMITERS[name])
+    if rk_order == 1:
+        # Euler integration: the updated grids are the starred ones (fluid.py:573-577)
+        for grid, starred in zip(_grids(component), _state(component).starred):
+            grid.copy_(starred)
+
+
+def kurganov_tadmor_internal_sources(component, ᔑdt, a=-1):
+    """The Kurganov-Tadmor branch of Component.apply_internal_sources (species.py:2902-2916):
+    the flux step holds every term but the Hubble term of the continuity equation, which needs
+    approximations['P=wρ'] off and is not implemented.  Within scope nothing happens."""
+    _check_scope(component, a if a != -1 else 1.0)
+    if (component.boltzmann_order > -1 and not component.approximations['P=wρ']
+            and component.params.enable_Hubble):
+        raise ConceptGPUError(
+            f'{component.name}: the Hubble term of kurganov_tadmor_internal_sources '
+            '(fluid.py:689-709, a non-linear 𝒫 without the P=wρ approximation) is not '
+            'implemented')
+
+
+def _clock(component):
+    clock = component.__dict__.get('clock')
+    if clock is None:
+        raise ConceptGPUError(
+            f'{component.name}: the Kurganov-Tadmor hook needs the clock of the time loop '
+            '(component.clock, set by stepper.Timeloop) for the current scale factor')
+    return clock
+
+
+def drift_selected(component, ᔑdt, a_end=-1):
+    """Component.drift for fluids (species.py:2200-2236) with both schemes; a `fluid_drift` hook
+    of stepper.Timeloop.  'maccormack' goes to drift(); 'kurganovtadmor' to kurganov_tadmor()
+    with the selected rungekuttaorder and, as the reference passes no scale factor
+    (species.py:2230), the current one of the loop's clock: the start of the drift
+    (main.py:335-361)."""
+    if component.representation != 'fluid':
+        raise ConceptGPUError(f'{component.name}: fluid.drift_selected() is for fluid components')
+    if is_selected(component, component.params.fluid_scheme_select) != 'kurganovtadmor':
+        return drift(component, ᔑdt, a_end)
+    if component.boltzmann_order < 1:
+        return
+    clock = _clock(component)
+    kurganov_tadmor(component, ᔑdt, clock.a,
+                    rk_order=is_selected(component, _kt_options(component)['rungekuttaorder']),
+                    cosmo=clock)
+
+
+def sources_selected(component, ᔑdt, a_next=-1):
+    """Component.apply_internal_sources (species.py:2812-2921) with both schemes; a
+    `fluid_sources` hook of stepper.Timeloop."""
+    if component.representation != 'fluid':
+        return
+    if is_selected(component, component.params.fluid_scheme_select) != 'kurganovtadmor':
+        return apply_internal_sources(component, ᔑdt, a_next)
+    kurganov_tadmor_internal_sources(component, ᔑdt, a_next)
 
 
 def v_max(component, a):

@@ -156,6 +156,8 @@ SYMBOLS = {
     'cg_fluid_vmax': (_int, [_vp, _vp, _vp, _vp, _i64, _dbl, _vp]),
     'cg_fluid_pressure_sources': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl,
                                          _dbl]),
+    'cg_fluid_kt_step': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _dbl, _dbl,
+                                _dbl, _dbl, _dbl, _dbl, _dbl]),
 }
 
 if not os.path.exists(LIB_PATH):

@@ -688,6 +688,10 @@ class Timeloop(RungStepper):
         self.fluid_drift, self.fluid_limiter = fluid_drift, fluid_limiter
         self.fluid_sources = fluid_sources
         for c in components:
+            if c.representation != 'particles':
+                # the loop's clock (universals.t and universals.a of the reference), for hooks
+                # that need the current scale factor (fluid.drift_selected)
+                c.clock = self.cosmo
             if (c.representation != 'particles' and fluid_sources is None
                     and getattr(c, 'w_constant', 0.0) != 0):
                 raise ConceptGPUError(

@@ -767,7 +767,25 @@ int cg_render2d_apply(cg_ctx *ctx, double *image /*DEV n*/, int64_t n, double ex
  *   neighbours' 𝒫 formed from rho by the same product.  rho with H = 1 (rho_lo / rho_hi: one
  *   layer each, or both NULL); c2w: light_speed**2*w; minus_dt: -ᔑdt['a**(-3*w_eff)'];
  *   half_inv_dx: (1/2)/Δx.  J NULL: the realisation alone (fluid.py:912-913).  P and J are
- *   written in place; none of them may be rho. */
+ *   written in place; none of them may be rho.
+ * cg_fluid_kt_step: one Runge-Kutta step of kurganov_tadmor (fluid.py:103-464) with at_interface,
+ *   slope_ratio, kurganov_tadmor_flux (:486-554), the flux limiters (:588-673) and
+ *   finalize_rk_step (:565-586) for ϱ, Jx, Jy, Jz in one pass.  src[0..3]: the grids the stencil
+ *   reads (the unstarred in rk_step 0, the starred in rk_step 1) with H = 2; dst[0..3]: the grids
+ *   written (rk_step 0: dst = flux terms + src; 1: dst += flux terms).  P (or NULL): receives
+ *   src[0]*c2w, the realisation of 𝒫 the step uses (ic.py:503-508); the pressure joins the flux
+ *   of Jᵐ across m when c2w != 0.  limiter: 0 minmod, 1 monotonizedcentral (mc), 2 ospre,
+ *   3 superbee, 4 sweby, 5 umist, 6 vanalbada, 7 vanleer (muscl, harmonic), 8 koren.
+ *   c2w: light_speed**2*w; inv_c2: light_speed**-2; a_pow: a**(3*w_eff-2); soundspeed:
+ *   light_speed*sqrt(w)/a; f_J: ᔑdt['a**(3*w_eff-2)']/ᔑdt['1']; f_P: ᔑdt['a**(-3*w_eff)']/ᔑdt['1'];
+ *   to_delta: (1 + rk_step)/rk_order*ᔑdt['1']/Δx.  A gather without atomics: the same input gives
+ *   the same bits on any number of domains. */
+int cg_fluid_kt_step(cg_ctx *ctx, const void *const *src /*HOST 4*/,
+                     const void *const *src_lo /*HOST 4 or NULL*/,
+                     const void *const *src_hi /*HOST 4 or NULL*/, void *const *dst /*HOST 4*/,
+                     double *P /*DEV or NULL*/, int64_t gridsize, int64_t nxl, int limiter,
+                     int rk_step, double c2w, double inv_c2, double a_pow, double soundspeed,
+                     double f_J, double f_P, double to_delta);
 int cg_fluid_pressure_sources(cg_ctx *ctx, const double *rho /*DEV*/, const double *rho_lo,
                               const double *rho_hi, double *P /*DEV*/,
                               void *const *J /*HOST 3 or NULL*/, int64_t gridsize, int64_t nxl,

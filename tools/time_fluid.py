@@ -25,6 +25,9 @@ HBM_PEAK = 8e12   # bytes/s
 BYTES_SMOOTH = 72 + 24 + 104 + 16 + 64 + 32   # per cell and call
 BYTES_SWEEP = 72 + 96                      # per cell and sweep
 BYTES_SOURCES = 8 + 8 + 48                 # per cell and source pass: ϱ in, 𝒫 out, three J in and out
+# per cell and Kurganov-Tadmor call of order 2: either step reads four grids and writes four and
+# 𝒫 (72 B); the second also reads the four it adds to (32 B)
+BYTES_KT = 72 + 72 + 32
 
 
 def fields(gs, void, device):
@@ -42,12 +45,65 @@ def fields(gs, void, device):
     return ϱ.contiguous(), [j.contiguous() for j in J]
 
 
+def time_kt(args):
+    """--kt: ten kurganov_tadmor calls of order 2 (w = 0.2, 'mc') beside the MacCormack line of
+    profiles/fluid_drift_512.json and the HBM time of the bytes of a call"""
+    from concept_amd import commons, fluid
+    from concept_amd.species import Component
+    gs = args.gridsize
+    commons.load_params({'boxsize': float(gs), 'select_eos_w': {'all': 0.2},
+                         'select_approximations': {'P=wρ': True}, 'enable_Hubble': False,
+                         'fluid_scheme_select': 'Kurganov-Tadmor',
+                         'fluid_options': {'kurganovtadmor': {'flux_limiter_select': 'mc'}}})
+    device = torch.device('cuda', torch.cuda.current_device())
+    c = Component('fluid', 'matter', gridsize=gs, boltzmann_order=1)
+    ϱ, J = fields(gs, False, device)
+    c.ϱ.copy_(ϱ)
+    for d in range(3):
+        c.J[d].copy_(J[d])
+    del ϱ, J
+    # a Courant number of about 0.07 on a grid spacing of 1 (the sound speed is c sqrt(0.2))
+    ᔑdt = {'1': 5e-4, ('a**(3*w_eff-2)', c.name): 5e-4, ('a**(-3*w_eff)', c.name): 5e-4}
+    fluid.kurganov_tadmor(c, ᔑdt, 1.0, rk_order=2)   # warm-up: buffers, first launches
+    torch.cuda.synchronize()
+    start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(args.calls):
+        fluid.kurganov_tadmor(c, ᔑdt, 1.0, rk_order=2)
+    end.record()
+    torch.cuda.synchronize()
+    ms = start.elapsed_time(end)/args.calls
+    hbm_ms = gs**3*BYTES_KT/HBM_PEAK*1e3
+    result = {'gridsize': gs, 'calls': args.calls, 'device': torch.cuda.get_device_name(device),
+              'hbm_peak_TBps': HBM_PEAK/1e12,
+              'kurganov_tadmor': {
+                  'rk_order': 2, 'limiter': 'mc', 'w': 0.2, 'ms_per_call': round(ms, 4),
+                  'bytes_per_call': int(gs**3*BYTES_KT), 'hbm_ms_at_8TBps': round(hbm_ms, 4),
+                  'fraction_of_hbm_rate': round(hbm_ms/ms, 4),
+                  'min_rho': float(c.ϱ.min().item())}}
+    recorded = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                            'profiles', 'fluid_drift_512.json')
+    if gs == 512 and os.path.exists(recorded):
+        with open(recorded) as f:
+            result['maccormack_smooth_recorded'] = json.load(f)['smooth']
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gridsize', type=int, default=512)
     ap.add_argument('--calls', type=int, default=10)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--kt', action='store_true',
+                    help='time the Kurganov-Tadmor scheme instead (profiles/fluid_kt_512.json)')
     args = ap.parse_args()
+    if args.kt:
+        line = json.dumps(time_kt(args))
+        print(line)
+        if args.out:
+            with open(args.out, 'w') as f:
+                f.write(line + '\n')
+        return
     from concept_amd import commons, fluid
     from concept_amd.species import Component
     gs = args.gridsize
