@@ -14,7 +14,16 @@
   save_powerspec()               analysis.py:796-833 with save_polyspec / get_txt_info
                                  (analysis.py:3283-3484, 3495-3751)
 The linear and corrected spectra need CLASS, and plots need matplotlib: a selection that asks
-for them is warned about once and left out; 'data' is what gets computed."""
+for them is warned about once and left out; 'data' is what gets computed.
+
+The bispectrum's computational core:
+  compute_bispec_value()         analysis.py:2576-2707 with get_bispec_grid (2739-2789): shell
+                                 fields and triple sums in HIP (cg_bispec_shell,
+                                 cg_bispec_sums, csrc/cg_bispec.hip)
+  bispec_measure()               compute_bispec (analysis.py:3031-3166) and the mode counting
+                                 of get_bispec_bins (analysis.py:1293-1316) for explicit bins
+The configuration grammar, the shell boundaries, the tree-level bispectrum, the file, the
+dump of the time loop, plots and the on-disk mode cache are not built."""
 import collections
 import hashlib
 import itertools
@@ -101,7 +110,8 @@ def upstream_gridsize(component, output_type='powerspec'):
     'powerspec' and 'render2D': the selected 'upstream gridsize', else 2*cbrt(Ñ) for particles
     and the fluid's own grid size for fluids."""
     p = commons.params
-    options = getattr(p, f'{output_type}_options')
+    # (bispec_options is not read: the bispectrum takes the reference's default here)
+    options = getattr(p, f'{output_type}_options', None) or {'upstream gridsize': {}}
     g = is_selected(component, options['upstream gridsize'], default=-1)
     if g == -1:
         g = 'gridsize' if component.representation == 'fluid' else '2*cbrt(Ñ)'
@@ -112,7 +122,7 @@ def upstream_gridsize(component, output_type='powerspec'):
     if component.representation == 'fluid' and g != component.gridsize:
         raise ConceptGPUError(
             f'{component.name}: '
-            f'{"power spectrum" if output_type == "powerspec" else output_type} '
+            f'{ {"powerspec": "power spectrum", "bispec": "bispectrum"}.get(output_type, output_type)} '
             f'upstream grid size {g} differs from the fluid '
             f'grid size {component.gridsize}')
     return g
@@ -492,3 +502,167 @@ def load_powerspec_σ(filename, tophat_Mpc):
             if m:
                 return float(m.group(1))
     return None
+
+
+# -- the bispectrum: the computational core (analysis.py:929-3280) ------------------------------
+BispecResult = collections.namedtuple(
+    'BispecResult', ('n_modes', 'bpower', 'power', 'bpower_reduced', 'n_modes_power'))
+
+# compute_bispec_value's three grids of the previous call: (shell, gridsize, is_indicator) ->
+# (buffer number, mesh)  (analysis.py:2708-2710)
+bispec_grid_cache = {}
+_bispec_cache_antialiasing = [None]
+
+
+def _bispec_antialiasing(antialiasing):
+    if antialiasing is not None:
+        return bool(antialiasing)
+    return bool(getattr(commons.params, 'bispec_antialiasing', True))
+
+
+def get_bispec_grid(gridsize, shell, buffer_number, slab_data, antialiasing):
+    """get_bispec_grid (analysis.py:2739-2789): the shell-filtered copy of slab_data's Fourier
+    view (the indicator field of the shell without slab_data) on the mesh of role
+    'bispec <buffer_number>', transformed back to real space."""
+    grid = _mesh(gridsize, f'bispec {buffer_number}')
+    grid.bispec_shell(shell, slab_data, antialiasing)
+    grid.poisson_backward()
+    return grid
+
+
+def _bispec_sums(grids, power_mask):
+    """(value, Σg₀², Σg₁², Σg₂²) of this rank's layers as floats"""
+    return grids[0].bispec_sums(grids[1:], power_mask).cpu().tolist()
+
+
+def compute_bispec_value(gridsize, shells, power_dict, slab_data=None, *, antialiasing=None):
+    """compute_bispec_value (analysis.py:2576-2707), the Scoccimarro estimator: the sum over
+    the cells of the product of the three shell-filtered grids.  shells: three (k_inner,
+    k_outer) in grid units.  Without slab_data (the mesh whose Fourier view holds the data)
+    the grids are indicator fields and (value, shells_new) is returned, else the value.
+    power_dict (or None) receives Σ grid² under every shell it does not hold yet.  The value
+    is unnormalised and of this rank's layers only: under comm.init() the caller combines the
+    ranks with sum_in_rank_order.  A grid is reused when the previous call built it for the
+    same (shell, gridsize, is_indicator)."""
+    antialiasing = _bispec_antialiasing(antialiasing)
+    if _bispec_cache_antialiasing[0] != antialiasing:
+        bispec_grid_cache.clear()
+        _bispec_cache_antialiasing[0] = antialiasing
+    shells = [tuple(float(k) for k in shell) for shell in shells]
+    if len(shells) != 3:
+        raise ConceptGPUError(f'compute_bispec_value(): {len(shells)} shells given, not 3')
+    is_indicator = slab_data is None
+    shellinfos_counter = collections.Counter((shell, int(gridsize), is_indicator)
+                                             for shell in shells)
+    # grids of the previous call first, then the ones to build (analysis.py:2599-2617)
+    shellinfos, gridinfos = [], []
+    buffer_numbers = {0, 1, 2}
+    for shellinfo, multiplicity in shellinfos_counter.items():
+        loot = bispec_grid_cache.get(shellinfo)
+        if loot is not None:
+            shellinfos.append(shellinfo)
+            n, grid = loot
+            gridinfos.append((multiplicity, n, grid))
+            buffer_numbers -= {n}
+    for shellinfo, multiplicity in shellinfos_counter.items():
+        if shellinfo not in bispec_grid_cache:
+            shellinfos.append(shellinfo)
+            n = min(buffer_numbers)
+            buffer_numbers -= {n}
+            grid = get_bispec_grid(int(gridsize), shellinfo[0], n, slab_data, antialiasing)
+            gridinfos.append((multiplicity, n, grid))
+    if len(gridinfos) == 2 and gridinfos[0][0] > gridinfos[1][0]:
+        # Σ g₀g₁²: the grid that counts twice is grid 1 (analysis.py:2656-2658)
+        gridinfos.reverse()
+        shellinfos.reverse()
+    unique_shells = [shellinfo[0] for shellinfo in shellinfos]
+    compute_power = [power_dict is not None and shell not in power_dict
+                     for shell in unique_shells]
+    power_mask = sum(1 << q for q, want in enumerate(compute_power) if want)
+    sums = _bispec_sums([grid for _, _, grid in gridinfos], power_mask)
+    value = sums[0]
+    shells_new = []
+    for q, (shell, want) in enumerate(zip(unique_shells, compute_power)):
+        if want:
+            power_dict[shell] = sums[1 + q]
+            shells_new.append(shell)
+    bispec_grid_cache.clear()
+    for shellinfo, (_, n, grid) in zip(shellinfos, gridinfos):
+        bispec_grid_cache[shellinfo] = (n, grid)
+    return (value, shells_new) if is_indicator else value
+
+
+def _sum_ranks(values):
+    values = np.asarray(values, dtype=np.float64)
+    c = _comm.active()
+    if c is not None and c.world > 1 and values.size:
+        values = c.sum_in_rank_order(values)
+    return values
+
+
+def bispec_measure(components, shells_per_bin, gridsize, *, interpolation='PCS', deconvolve=True,
+                   interlace=True, do_reduced=True, a=1.0, antialiasing=None):
+    """compute_bispec (analysis.py:3031-3166) with the mode-counting half of get_bispec_bins
+    (analysis.py:1293-1316) for an explicit list of bins, each a triple of (k_inner, k_outer)
+    shells in grid units, processed in the given order.  Returns a BispecResult of arrays:
+    n_modes and bpower [boxsize⁶] per bin, power [boxsize³] (3 x nbins, the bin's shells in
+    the given order), bpower_reduced = B/(P₁P₂ + P₂P₃ + P₃P₁), and n_modes_power
+    (3 x nbins).  Empty bins and shells give NaN.  power and bpower_reduced are NaN without
+    do_reduced.  Collective under comm.init(); every rank returns the full result."""
+    antialiasing = _bispec_antialiasing(antialiasing)
+    gridsize = int(gridsize)
+    bins = [tuple(tuple(float(k) for k in shell) for shell in shells)
+            for shells in shells_per_bin]
+    nbins = len(bins)
+    order = int(commons.interpolation_orders.get(str(interpolation).upper(), interpolation))
+    lattice = commons._interlace2latticekind(interlace)
+    # the mode counts (analysis.py:1293-1316): indicator fields, normalised by 0.5/N³
+    bispec_grid_cache.clear()
+    normalization = 0.5/gridsize**3
+    n_modes = np.zeros(nbins)
+    n_modes_power = {}
+    for b, shells in enumerate(bins):
+        n_modes[b], _ = compute_bispec_value(gridsize, shells, n_modes_power,
+                                             antialiasing=antialiasing)
+    n_modes = _sum_ranks(n_modes)*normalization
+    n_modes_power = dict(zip(n_modes_power,
+                             _sum_ranks(list(n_modes_power.values()))*normalization))
+    # the data (analysis.py:3056-3093)
+    gridsizes_upstream = [upstream_gridsize(c, 'bispec') for c in components]
+    slab = interpolate_upstream(components, gridsizes_upstream, gridsize,
+                                lambda c: a**(-3*(1 + c.w_eff(a=a))), order, deconvolve,
+                                lattice, roles=('bispec', 'bispec upstream'))
+    bispec_grid_cache.clear()
+    power_dict = {} if do_reduced else None
+    bpower = np.zeros(nbins)
+    for b, shells in enumerate(bins):
+        bpower[b] = compute_bispec_value(gridsize, shells, power_dict, slab,
+                                         antialiasing=antialiasing)
+    bispec_grid_cache.clear()
+    bpower = _sum_ranks(bpower)
+    if do_reduced:
+        power_dict = dict(zip(power_dict, _sum_ranks(list(power_dict.values()))))
+    # normalisation (analysis.py:3097-3141)
+    ρ_bar = 0
+    for component in components:
+        ρ_bar += a**(-3*(1 + component.w_eff(a=a)))*component.ϱ_bar
+    boxsize = commons.params.boxsize
+    normalization = ρ_bar**-3*(0.5*boxsize**6)/gridsize**3
+    with np.errstate(divide='ignore', invalid='ignore'):
+        bpower = np.where(n_modes != 0, bpower*(normalization/n_modes), np.nan)
+    power = np.full((3, nbins), np.nan)
+    modes_power = np.array([[n_modes_power[shell] for shell in shells] for shells in bins]
+                           ).reshape(nbins, 3).T
+    bpower_reduced = np.full(nbins, np.nan)
+    if do_reduced:
+        normalization = ρ_bar**-2*(0.5*boxsize**3)/gridsize**3
+        for shell in power_dict:
+            n_mode_power = n_modes_power[shell]
+            power_dict[shell] = (power_dict[shell]*(normalization/n_mode_power)
+                                 if n_mode_power != 0 else float('nan'))
+        # the reduced bispectrum (analysis.py:3143-3164)
+        for b, shells in enumerate(bins):
+            power[:, b] = [power_dict[shell] for shell in shells]
+        bpower_reduced = bpower/(power[0]*power[1] + power[1]*power[2] + power[2]*power[0])
+    return BispecResult(n_modes=n_modes, bpower=bpower, power=power,
+                        bpower_reduced=bpower_reduced, n_modes_power=modes_power)

@@ -290,6 +290,9 @@ def load_params(source=None, **overrides):
     _load_powerspec_params(p, user, units)
     _load_render2D_params(p, user)
     _load_fluid_params(p, user)
+    # commons.py: bispec_antialiasing (cells are weighted by their overlap with the shell);
+    # bispec_options and bispec_select are not read
+    p.bispec_antialiasing = bool(user.get('bispec_antialiasing', True))
     # nghosts (commons.py:4411-4432): default 2 comes from the PCS default of the
     # power-spectrum and 2D render options; force interpolation and differentiation orders
     # raise it (powerspec_options default: PCS, interlaced -> 4//2 = 2, + 1 with cell-vertex

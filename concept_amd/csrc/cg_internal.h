@@ -245,6 +245,9 @@ struct cg_ctx {
     // ---- fluid solver ----
     cg_buf<double> fluid_partial;        // cg_fluid_vmax: per-workgroup partial maxima
 
+    // ---- bispectrum ----
+    cg_buf<double> bispec_partial;       // cg_bispec_sums: per-workgroup partial sums
+
     // ---- errors ----
     // device word of sticky error bits set by kernels (CG_ERR_*), read by cg_error_flags
     cg_buf<unsigned> err_flags;

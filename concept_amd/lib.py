@@ -143,6 +143,8 @@ SYMBOLS = {
     'cg_fluid_kick': (_int, [_vp, _vp, _vp, _vp, _int, _int, _dbl, _dbl]),
     'cg_powerspec_workspace': (_i64, [_vp, ctypes.c_int32]),
     'cg_powerspec_bin': (_int, [_vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _i64]),
+    'cg_bispec_shell': (_int, [_vp, _vp, _dbl, _dbl, _int]),
+    'cg_bispec_sums': (_int, [_vp, _vp, _vp, _int, _int, _vp]),
     'cg_render2d_project': (_int, [_vp, _int, _i64, _i64, _dbl, _dbl, _dbl, _vp]),
     'cg_render2d_workspace': (_i64, []),
     'cg_render2d_minmax': (_int, [_vp, _vp, _i64, _dbl, _vp, _vp]),

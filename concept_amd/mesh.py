@@ -480,6 +480,29 @@ class PotentialMesh:
                                   _ptr(out), _ptr(ws), ws.numel()))
         return out
 
+    # -- bispectrum (analysis.py:2576-2982; csrc/cg_bispec.hip) ------------------------
+    def bispec_shell(self, shell, source=None, antialiasing=True):
+        """The loop of get_bispec_grid (analysis.py:2739-2778) as an assignment of this mesh's
+        whole Fourier view: frac x the modes of `source` (a mesh of the same size and domain)
+        inside the shell (k_inner, k_outer) in grid units, or frac itself without a source
+        (the indicator field); zero everywhere else."""
+        k_inner, k_outer = shell
+        check(_L.cg_bispec_shell(self._ctx, None if source is None else source._ctx,
+                                 float(k_inner), float(k_outer), int(bool(antialiasing))))
+        return self
+
+    def bispec_sums(self, others=(), power_mask=0, out=None):
+        """The sums of compute_bispec_value (analysis.py:2621-2689) over this domain's real
+        cells, this mesh being grid 0 and `others` the further unique grids: a float64 tensor
+        (Σ g₀g₁g₂ | Σ g₀g₁² | Σ g₀³, Σ g₀², Σ g₁², Σ g₂²), the Σ gᵢ² of the bits set in
+        power_mask."""
+        if out is None:
+            out = torch.empty(4, dtype=torch.float64, device=self.device)
+        ctxs = [self._ctx] + [m._ctx for m in others] + [None]*(2 - len(others))
+        check(_L.cg_bispec_sums(ctxs[0], ctxs[1], ctxs[2], 1 + len(others), int(power_mask),
+                                _ptr(out)))
+        return out
+
     # -- 2D render (graphics.py:1374-1755; csrc/cg_render.hip) -------------------------
     def render2D_project(self, axis, plane_bgn, plane_end, frac_bgn, frac_end, factor, out=None):
         """project_render2D (graphics.py:1374-1532) of this mesh's real-space values: the N x N

@@ -702,6 +702,29 @@ int cg_powerspec_bin(cg_ctx *ctx, const int32_t *k_bin_indices /*DEV k2_max+1*/,
                      int32_t nbins, double *power_out /*DEV nbins*/, double *workspace /*DEV*/,
                      int64_t workspace_doubles);
 
+/* --- bispectrum (analysis.py:929-3280; built: the computational core, 2576-2982) ---
+ * cg_bispec_shell: the loop of get_bispec_grid (analysis.py:2739-2778) over
+ *   fourier_shell_loop(gridsize, k_inner, k_outer, skip_origin=True, skip_negative_ki=True)
+ *   (mesh.py:3186-3296) with its mirror to -ki, as an ASSIGNMENT of the whole current Fourier
+ *   view of dst (the in-place slab of one domain, or the buffer bound by
+ *   cg_dist_bind_fourier): a visited mode gets frac * src's mode (src NULL: frac + 0i, the
+ *   indicator field), every other element of the view 0 — padding, the origin and both
+ *   Nyquist planes included, which is the nullified slab of get_fftw_slab(nullify=True)
+ *   (analysis.py:2745).  frac = get_bispec_overlap_cellshell(|ki|, kj, kk, k_inner, k_outer)
+ *   (analysis.py:2803-2982) when antialias, else (k_inner^2 < k^2 <= k_outer^2)
+ *   (analysis.py:2764).  Shells in grid units.  src: a context of the same grid size and
+ *   domain, not dst.
+ * cg_bispec_sums: the three cases of compute_bispec_value (analysis.py:2621-2689) over the
+ *   real cells of this domain (domain_loop(skip_ghosts=True); owned layers, no padding) of
+ *   n_unique contexts' real-space meshes: out[0] = sum g0 g1 g2 (3), sum g0 g1^2 (2) or
+ *   sum g0^3 (1); out[1 + q] = sum gq^2 where bit q of want_power_mask is set, else 0.
+ *   Deterministic: the same grids give bit-identical sums (no floating-point atomics; fixed
+ *   summation order).  Unused contexts may be NULL. */
+int cg_bispec_shell(cg_ctx *dst, cg_ctx *src /*or NULL*/, double k_inner, double k_outer,
+                    int antialias);
+int cg_bispec_sums(cg_ctx *ctx0, cg_ctx *ctx1, cg_ctx *ctx2, int n_unique, int want_power_mask,
+                   double *out /*DEV 4*/);
+
 /* --- 2D render (graphics.py:1027-1955) --------------------------------------------
  * cg_render2d_project: project_render2D (graphics.py:1374-1532) of the context's real-space
  *   mesh (after the inverse transform) along axis (0 x, 1 y, 2 z): the planes
