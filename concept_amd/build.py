@@ -12,7 +12,9 @@ CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libconcept_gpu.so')
 SOURCES = ['cg_context.hip', 'cg_mesh_kernels.hip', 'cg_tiled_kernels.hip', 'cg_fft.hip', 'cg_shortrange.hip', 'cg_shortrange_dense.hip', 'cg_rungs.hip',
            'cg_particles.hip', 'cg_general.hip', 'cg_pp.hip', 'cg_analysis.hip', 'cg_render.hip', 'cg_fluid.hip', 'cg_bispec.hip']
-HEADERS = [os.path.join(CSRC, 'cg_internal.h'), os.path.join(CSRC, 'cg_kspace.h'), os.path.join(CSRC, 'cg_tiles.h'), os.path.join(CSRC, 'cg_substep.h'), os.path.join(CSRC, 'cg_fft_plan.h'), os.path.join(CSRC, 'cg_bispec.h'), os.path.join(REPO, 'include', 'concept_gpu.h')]
+# every header of csrc (a new one is in the staleness check without being listed), the C ABI last
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + [
+    os.path.join(REPO, 'include', 'concept_gpu.h')]
 
 FLAGS = [
     '--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC',

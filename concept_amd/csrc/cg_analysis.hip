@@ -2,8 +2,8 @@
 //   k_powerspec_bin      the binning loop of compute_powerspec   analysis.py:544-560
 //                        over fourier_loop(sparse=True, skip_origin=True, k2_max)
 //                                                                 mesh.py:2748-2838
-//   k_powerspec_reduce   the Reduce(op=MPI.SUM) of the partial bins, in a fixed order
-//                                                                 analysis.py:562-566
+//   k_reduce_columns     the Reduce(op=MPI.SUM) of the partial bins, in a fixed order
+//   (cg_wave.h)                                                   analysis.py:562-566
 // The walk is over the context's current Fourier view (cg_ctx::four, the view
 // k_fourier_operate walks): mode (ki, kj, kk) with array indices (a, b, kk) at
 // four[a*f_si + (b - f_j0)*cp + kk].  Visited are the modes of the reference's sparse loop:
@@ -13,13 +13,14 @@
 // Deterministic: no floating-point atomics.  A wave owns a row (a, b) at a time and walks it in
 // chunks of 64 modes, one per lane.  Along kk the bin index never decreases, so a chunk whose
 // modes all fall into the bin of the wave's pending run is added lane-wise into per-lane
-// accumulators; a change of bin closes the run: a fixed butterfly over the lanes sums it, and
+// accumulators; a change of bin closes the run: wave_sum_xor sums it over the lanes, and
 // lane 0 adds the sum into the wave's private histogram.  The waves of a workgroup are
 // combined in wave order into one partial histogram per workgroup (LDS histograms), or every
 // wave keeps its partial histogram in global memory (bins beyond the LDS budget);
-// k_powerspec_reduce then sums the partials of every bin in a fixed tree order.
+// k_reduce_columns then sums the partials of every bin in a fixed tree order (cg_wave.h).
 // Compiled with -ffp-contract=off; FP64 throughout, k² as an integer.
 #include "cg_internal.h"
+#include "cg_wave.h"
 
 namespace {
 
@@ -34,13 +35,6 @@ __device__ __host__ inline i64 isqrt64(i64 n) {
     while (r * r > n) r--;
     while ((r + 1) * (r + 1) <= n) r++;
     return r;
-}
-
-// Sum over the 64 lanes in a fixed butterfly order; lane 0's value is the one used.
-__device__ inline double wave_sum(double v) {
-#pragma clang fp contract(off)
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
-    return v;
 }
 
 template <bool kLds>
@@ -93,7 +87,7 @@ __global__ __launch_bounds__(kThreads) void k_powerspec_bin(
                 // the whole chunk falls into one bin
                 if (b0 != pending) {
                     if (pending >= 0) {
-                        const double s = wave_sum(acc);
+                        const double s = wave_sum_xor(acc);
                         if (lane == 0) hist[pending] += s;
                     }
                     pending = b0;
@@ -104,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void k_powerspec_bin(
             }
             // the chunk spans several bins: close the run, then one butterfly per bin
             if (pending >= 0) {
-                const double s = wave_sum(acc);
+                const double s = wave_sum_xor(acc);
                 if (lane == 0) hist[pending] += s;
             }
             pending = -1;
@@ -113,13 +107,13 @@ __global__ __launch_bounds__(kThreads) void k_powerspec_bin(
                 const int l = __ffsll((long long)vmask) - 1;
                 const int bsel = __shfl(bin, l);
                 const bool sel = valid && bin == bsel;
-                const double s = wave_sum(sel ? pw : 0.0);
+                const double s = wave_sum_xor(sel ? pw : 0.0);
                 if (lane == 0) hist[bsel] += s;
                 vmask &= ~__ballot(sel);
             }
         }
         if (pending >= 0) {
-            const double s = wave_sum(acc);
+            const double s = wave_sum_xor(acc);
             if (lane == 0) hist[pending] += s;
         }
     }
@@ -132,25 +126,6 @@ __global__ __launch_bounds__(kThreads) void k_powerspec_bin(
             out[bb] = s;
         }
     }
-}
-
-// power[bin] = sum over the partial histograms, in a fixed order: thread t sums partials
-// t, t + 256, ... in turn, then a tree over the threads.
-__global__ __launch_bounds__(256) void k_powerspec_reduce(const double *__restrict__ partial,
-                                                          i64 npartials, int nbins,
-                                                          double *__restrict__ power) {
-#pragma clang fp contract(off)
-    __shared__ double red[256];
-    const int bin = blockIdx.x;
-    double s = 0;
-    for (i64 p = threadIdx.x; p < npartials; p += 256) s = s + partial[p * nbins + bin];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int m = 128; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) power[bin] = red[0];
 }
 
 struct BinLaunch {
@@ -212,8 +187,9 @@ extern "C" int cg_powerspec_bin(cg_ctx *c, const int32_t *k_bin_indices, int64_t
                            c->f_j0, c->f_nj, k_bin_indices, (i64)k2_max, (int)nbins, workspace);
     }
     CG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_powerspec_reduce, dim3((unsigned)nbins), dim3(256), 0, c->stream,
-                       (const double *)workspace, L.npartials, (int)nbins, power_out);
+    // power[bin] = the sum of the partial histograms' column `bin`
+    hipLaunchKernelGGL(k_reduce_columns<OpPlus>, dim3((unsigned)nbins), dim3(256), 0, c->stream,
+                       (const double *)workspace, L.npartials, (i64)nbins, power_out);
     CG_LAUNCH_CHECK();
     return 0;
 }

@@ -3,17 +3,18 @@
 //                    over fourier_shell_loop(skip_origin)     mesh.py:3186-3296
 //                    with get_bispec_overlap_cellshell        analysis.py:2803-2982 (cg_bispec.h)
 //   k_bispec_sums    the three cases of compute_bispec_value  analysis.py:2621-2689
-//   k_bispec_final   the sum of the workgroups' partial sums, in a fixed tree
+//   k_reduce_columns the sum of the workgroups' partial sums, in a fixed tree (cg_wave.h)
 // k_bispec_shell ASSIGNS the whole Fourier view of the destination (cg_ctx::four, the view
 // k_powerspec_bin walks): one thread per complex element, frac x source (or frac + 0i) inside
 // the reference's visited set and 0 everywhere else, so the nullified slab the reference
 // starts from (get_fftw_slab(nullify=True)) needs no pass of its own.
 // k_bispec_sums walks the real cells of the domain (owned layers, no padding): a workgroup
 // takes rows in turn, a thread two neighbouring cells of a row at a time.  Deterministic: no
-// floating-point atomics; lanes by a fixed butterfly, waves in wave order, workgroups by
-// k_bispec_final in a fixed tree.  Compiled with -ffp-contract=off; FP64 throughout.
+// floating-point atomics; lanes by a fixed butterfly (wave_sum_xor), waves in wave order,
+// workgroups by k_reduce_columns in a fixed tree.  Compiled with -ffp-contract=off; FP64 throughout.
 #include "cg_bispec.h"
 #include "cg_internal.h"
+#include "cg_wave.h"
 
 namespace {
 
@@ -53,13 +54,6 @@ __global__ __launch_bounds__(kThreads) void k_bispec_shell(
         }
     }
     dst[(i64)a * dst_si + (i64)bl * cp + kk] = out;
-}
-
-// Sum over the 64 lanes in a fixed butterfly order; every lane ends with the sum.
-__device__ inline double wave_sum(double v) {
-#pragma clang fp contract(off)
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
-    return v;
 }
 
 // kUnique grids: 3 sums g0 g1 g2, 2 sums g0 g1^2, 1 sums g0^3; bit q of power_mask adds the
@@ -104,10 +98,10 @@ __global__ __launch_bounds__(kThreads) void k_bispec_sums(
             }
         }
     }
-    v = wave_sum(v);
-    p0 = wave_sum(p0);
-    p1 = wave_sum(p1);
-    p2 = wave_sum(p2);
+    v = wave_sum_xor(v);
+    p0 = wave_sum_xor(p0);
+    p1 = wave_sum_xor(p1);
+    p2 = wave_sum_xor(p2);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
         red[wave][0] = v;
@@ -121,25 +115,6 @@ __global__ __launch_bounds__(kThreads) void k_bispec_sums(
         for (int w = 1; w < kWaves; w++) s = s + red[w][threadIdx.x];
         partial[(i64)blockIdx.x * 4 + threadIdx.x] = s;
     }
-}
-
-// out[q] = sum over the workgroups' partials, in a fixed order: thread t sums partials t,
-// t + 256, ... in turn, then a tree over the threads.  One workgroup per q.
-__global__ __launch_bounds__(kThreads) void k_bispec_final(const double *__restrict__ partial,
-                                                           int npartials,
-                                                           double *__restrict__ out) {
-#pragma clang fp contract(off)
-    __shared__ double red[kThreads];
-    const int q = blockIdx.x;
-    double s = 0;
-    for (int p = threadIdx.x; p < npartials; p += kThreads) s = s + partial[(i64)p * 4 + q];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int m = kThreads / 2; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[q] = red[0];
 }
 
 bool same_geometry(const cg_ctx *a, const cg_ctx *b) {
@@ -211,8 +186,9 @@ extern "C" int cg_bispec_sums(cg_ctx *c0, cg_ctx *c1, cg_ctx *c2, int n_unique,
     else CG_BISPEC_SUMS(1);
 #undef CG_BISPEC_SUMS
     CG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_bispec_final, dim3(4), dim3(kThreads), 0, c0->stream,
-                       (const double *)partial, blocks, out);
+    // out[q] = the sum of the workgroups' partial q
+    hipLaunchKernelGGL(k_reduce_columns<OpPlus>, dim3(4), dim3(256), 0, c0->stream,
+                       (const double *)partial, (i64)blocks, (i64)4, out);
     CG_LAUNCH_CHECK();
     return 0;
 }

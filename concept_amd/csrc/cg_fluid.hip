@@ -7,6 +7,7 @@
 //   k_vacuum_gather   the pair terms of the 3x3x3 blocks, as a gather     fluid.py:1289-1319
 //   k_vacuum_apply    variable += Δ                                       fluid.py:1333-1340
 //   k_vmax            max (Jx² + Jy² + Jz²)/(ϱ + c⁻²𝒫)²                   analysis.py:3940-3955
+//                     (the workgroups' maxima, then k_reduce_columns of cg_wave.h)
 //   k_pressure_sources  𝒫 = ϱ (c²w) and the pressure term of the Euler equation, one pass
 //                                                         ic.py:503-508, fluid.py:1044-1057, mesh.py:4966-4970
 //   k_realize_P       𝒫 = ϱ (c²w) alone                                   ic.py:503-508
@@ -22,6 +23,7 @@
 // FP64, compiled with -ffp-contract=off: every sum, product and quotient is evaluated as the
 // reference writes it.  No floating-point atomics: the results do not depend on the launch.
 #include "cg_internal.h"
+#include "cg_wave.h"
 
 namespace {
 
@@ -219,34 +221,22 @@ __global__ __launch_bounds__(kThreads) void k_vacuum_apply(Out4 var, In4 delta, 
     }
 }
 
-// partial maxima per workgroup (final = 0), then one workgroup over the partials (final = 1);
-// the reference's compare (value > maximum, from 0) lets no NaN in
+// partial maxima per workgroup, then k_reduce_columns over the partials (cg_wave.h); the
+// reference's compare (value > maximum, from 0: OpGreaterFrom0) lets no NaN in
 __global__ __launch_bounds__(kThreads) void k_vmax(const double *__restrict__ rho,
                                                   const double *__restrict__ P, In4 J, i64 n,
-                                                  double inv_c2, int final,
-                                                  double *__restrict__ out) {
+                                                  double inv_c2, double *__restrict__ out) {
 #pragma clang fp contract(off)
     __shared__ double red[kThreads];
-    double best = 0;
-    if (!final) {
-        for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads) {
-            const double jx = J.p[0][i], jy = J.p[1][i], jz = J.p[2][i];
-            const double den = rho[i] + inv_c2 * P[i];
-            const double v = (jx * jx + jy * jy + jz * jz) / (den * den);
-            if (v > best) best = v;
-        }
-    } else {
-        for (i64 i = threadIdx.x; i < n; i += kThreads)
-            if (rho[i] > best) best = rho[i];
+    double best = OpGreaterFrom0::identity();
+    for (i64 i = (i64)blockIdx.x * kThreads + threadIdx.x; i < n; i += (i64)gridDim.x * kThreads) {
+        const double jx = J.p[0][i], jy = J.p[1][i], jz = J.p[2][i];
+        const double den = rho[i] + inv_c2 * P[i];
+        const double v = (jx * jx + jy * jy + jz * jz) / (den * den);
+        best = OpGreaterFrom0()(best, v);
     }
-    red[threadIdx.x] = best;
-    __syncthreads();
-    for (int m = kThreads / 2; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m && red[threadIdx.x + m] > red[threadIdx.x])
-            red[threadIdx.x] = red[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    best = block_tree<OpGreaterFrom0>(red, best);
+    if (threadIdx.x == 0) out[blockIdx.x] = best;
 }
 
 // The realisation 𝒫 = ϱ (c²w) of the P = wρ approximation (ic.py:503-508) and the pressure term of
@@ -730,11 +720,10 @@ extern "C" int cg_fluid_vmax(cg_ctx *c, const double *rho, const double *P, cons
     if (c->fluid_partial.reserve(c, sizeof(double) * kPartials)) return 1;
     const unsigned blocks = grid_for(n, kPartials);
     hipLaunchKernelGGL(k_vmax, dim3(blocks), dim3(kThreads), 0, c->stream, rho, P, j, (i64)n, inv_c2,
-                       0, (double *)c->fluid_partial);
+                       (double *)c->fluid_partial);
     CG_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_vmax, dim3(1), dim3(kThreads), 0, c->stream,
-                       (const double *)c->fluid_partial, (const double *)nullptr, In4{},
-                       (i64)blocks, 0.0, 1, out);
+    hipLaunchKernelGGL(k_reduce_columns<OpGreaterFrom0>, dim3(1), dim3(256), 0, c->stream,
+                       (const double *)c->fluid_partial, (i64)blocks, (i64)1, out);
     CG_LAUNCH_CHECK();
     return 0;
 }

@@ -46,20 +46,12 @@ int cgk_drift(cg_ctx *c, double *pos, const double *mom, i64 n, double dt_over_m
 // 3965-3972): sum of mom[r]^2 over all 3N reals and the largest |mom_i|^2 of a particle — the
 // inputs of the time loop's PM / P3M step-size limiters (main.py:842-912).  Two stages so that
 // the sum has a fixed order (bit-reproducible): kMeasureBlocks workgroups each reduce a
-// contiguous share to one partial, one workgroup adds the partials in index order.
+// contiguous share to one partial (block_sum_max_store, cg_wave.h), one wave adds the partials
+// in index order.
 // ---------------------------------------------------------------------------
 constexpr int kMeasureBlocks = 1024;
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off));
-    return v;
-}
 __global__ __launch_bounds__(256) void k_measure_mom(const double *__restrict__ mom, i64 n,
                                                      double *__restrict__ partial) {
-    __shared__ double s_sum[4], s_max[4];
     const i64 per = (n + gridDim.x - 1) / gridDim.x;
     const i64 p0 = (i64)blockIdx.x * per, p1 = p0 + per < n ? p0 + per : n;
     double sum = 0, mx = 0;
@@ -69,29 +61,18 @@ __global__ __launch_bounds__(256) void k_measure_mom(const double *__restrict__ 
         sum += m2;
         mx = fmax(mx, m2);
     }
-    sum = wave_sum(sum);
-    mx = wave_max(mx);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[w] = sum;
-        s_max[w] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        partial[2 * blockIdx.x + 1] = fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3]));
-    }
+    block_sum_max_store(sum, mx, partial + 2 * blockIdx.x);
 }
 __global__ __launch_bounds__(64) void k_measure_final(const double *__restrict__ partial, int nb,
                                                       double *__restrict__ out) {
-    // lane l adds partials l, l + 64, ... in order; then the fixed shuffle tree
+    // lane l adds partials l, l + 64, ... in order; then the fixed shuffle trees (lane 0's value)
     double sum = 0, mx = 0;
     for (int b = threadIdx.x; b < nb; b += 64) {
         sum += partial[2 * b];
         mx = fmax(mx, partial[2 * b + 1]);
     }
-    sum = wave_sum(sum);
-    mx = wave_max(mx);
+    sum = wave_sum_xor(sum);
+    mx = wave_max_down(mx);
     if (threadIdx.x == 0) {
         out[0] = sum;
         out[1] = mx;
@@ -105,7 +86,6 @@ __global__ __launch_bounds__(256) void k_measure_mom_regions(const double *__res
                                                              const unsigned *__restrict__ count,
                                                              i64 nregions,
                                                              double *__restrict__ partial) {
-    __shared__ double s_sum[4], s_max[4];
     const i64 per = (nregions + gridDim.x - 1) / gridDim.x;
     const i64 r0 = (i64)blockIdx.x * per, r1 = r0 + per < nregions ? r0 + per : nregions;
     double sum = 0, mx = 0;
@@ -119,18 +99,7 @@ __global__ __launch_bounds__(256) void k_measure_mom_regions(const double *__res
             mx = fmax(mx, m2);
         }
     }
-    sum = wave_sum(sum);
-    mx = wave_max(mx);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        s_sum[w] = sum;
-        s_max[w] = mx;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]);
-        partial[2 * blockIdx.x + 1] = fmax(fmax(s_max[0], s_max[1]), fmax(s_max[2], s_max[3]));
-    }
+    block_sum_max_store(sum, mx, partial + 2 * blockIdx.x);
 }
 
 int cgk_measure_mom_regions(cg_ctx *c, const double *mom, const unsigned *start,

@@ -15,10 +15,11 @@
 // (x, z), (x, y) for the axes x, y, z.
 //
 // Deterministic: no floating-point atomics.  A pixel is summed by one wave (axis z: the lanes
-// walk the contiguous row, then a fixed butterfly) or by one thread (axes x and y: the lanes run
+// walk the contiguous row, then a fixed butterfly: wave_sum_xor) or by one thread (axes x and y: the lanes run
 // along z, every thread adds its planes in ascending order).  The histogram counts are integers
 // (LDS and global integer atomics).  Compiled with -ffp-contract=off; FP64 throughout.
 #include "cg_internal.h"
+#include "cg_wave.h"
 
 namespace {
 
@@ -36,13 +37,6 @@ struct Planes {
 
 __device__ inline double plane_weight(const Planes &pl, int s) {
     return s == pl.s0 ? pl.w_first : (s == pl.s1 - 1 ? pl.w_last : 1.0);
-}
-
-// Sum over the 64 lanes in a fixed butterfly order
-__device__ inline double wave_sum(double v) {
-#pragma clang fp contract(off)
-    for (int m = 32; m >= 1; m >>= 1) v = v + __shfl_xor(v, m);
-    return v;
 }
 
 // Axis z: the row (layer, j) is contiguous.  A wave takes 64 consecutive rows j of one layer in
@@ -64,7 +58,7 @@ __global__ __launch_bounds__(kThreads) void k_project_along_z(
         const double *row = mesh0 + ((i64)l * ny + (jb + t)) * pad;
         double acc = 0;
         for (int k = pl.s0 + lane; k < pl.s1; k += 64) acc = acc + plane_weight(pl, k) * row[k];
-        const double s = wave_sum(acc);
+        const double s = wave_sum_xor(acc);
         if (lane == t) mine = s;
     }
     const int j = jb + lane;
@@ -134,19 +128,11 @@ __global__ __launch_bounds__(kThreads) void k_image_minmax(const double *__restr
             hi = fmax(hi, image[2 * i + 1]);
         }
     }
-    lo_s[threadIdx.x] = lo;
-    hi_s[threadIdx.x] = hi;
-    __syncthreads();
-    for (int m = kThreads / 2; m >= 1; m >>= 1) {
-        if ((int)threadIdx.x < m) {
-            lo_s[threadIdx.x] = fmin(lo_s[threadIdx.x], lo_s[threadIdx.x + m]);
-            hi_s[threadIdx.x] = fmax(hi_s[threadIdx.x], hi_s[threadIdx.x + m]);
-        }
-        __syncthreads();
-    }
+    lo = block_tree<OpFmin>(lo_s, lo);
+    hi = block_tree<OpFmax>(hi_s, hi);
     if (threadIdx.x == 0) {
-        pairs[2 * blockIdx.x] = lo_s[0];
-        pairs[2 * blockIdx.x + 1] = hi_s[0];
+        pairs[2 * blockIdx.x] = lo;
+        pairs[2 * blockIdx.x + 1] = hi;
     }
 }
 

@@ -23,6 +23,7 @@
 
 #include "cg_internal.h"
 #include "cg_substep.h"
+#include "cg_wave.h"
 
 struct SrParams {
     double boxsize, r2_index_scaling, r2_max, factor;
@@ -496,18 +497,6 @@ __device__ __forceinline__ void sr_cell_ranges(const int (&sa)[NSEG], const int 
     }
 }
 
-// inclusive scan over the 64 lanes of a wave in DPP adds (no LDS round trips): row_shr 1, 2, 4,
-// 8 inside the rows of 16 lanes, then the row totals are broadcast forward (row_bcast 15, 31)
-__device__ __forceinline__ unsigned sr_wave_scan(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-
 // One receiver chunk's lanes: R receivers x S supplier groups
 struct SrChunk {
     int R, S, sub, rl;
@@ -910,8 +899,8 @@ k_sr_sweep_blocks(const double *__restrict__ pos_r, const unsigned *__restrict__
     p_cnt[lane] = ca_;
     if (WRAP) p_cnt[kSbCols + lane] = cb_;
     else if (lane < kSbCols - 64) p_cnt[64 + lane] = cb_;
-    const unsigned i0 = sr_wave_scan(c0);                                   // inclusive
-    const unsigned i1 = WRAP ? i0 : sr_wave_scan(c1) + __builtin_amdgcn_readlane(i0, 63);
+    const unsigned i0 = wave_scan_dpp(c0);                                   // inclusive
+    const unsigned i1 = WRAP ? i0 : wave_scan_dpp(c1) + __builtin_amdgcn_readlane(i0, 63);
     const unsigned e0 = i0 - c0, e1 = i1 - c1;                              // exclusive
     p_off[lane] = e0;  // (identical values from every wave: a wave reads what it wrote itself)
     if (WRAP) p_off[kSbCols + lane] = e0 + ca_;
@@ -1231,7 +1220,7 @@ __global__ __launch_bounds__(256) void k_sr_active_cells(const unsigned *__restr
 #pragma unroll
     for (int i = 0; i < kSaPerThread; i++) {
         const unsigned n = mine[i];
-        const unsigned incl = sr_wave_scan(n);
+        const unsigned incl = wave_scan_dpp(n);
         if (n) {
             const unsigned c = first + 64u * i + lane, r0 = off_r[c];
             unsigned slot = off + incl - n;
@@ -1322,7 +1311,7 @@ __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
     // 4 runs x 16 lanes, most of them half empty (0.48 of the lane slots used).
     {
         const unsigned mine = lane < kSaRuns ? r_cnt[wave][lane] : 0u;
-        const unsigned incl = sr_wave_scan(mine);
+        const unsigned incl = wave_scan_dpp(mine);
         r_pre[wave][lane] = incl - mine;   // (lanes >= 52: the total)
     }
     sr_wave_lds_sync();
@@ -1407,24 +1396,8 @@ __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
                 c0 = n0, c1 = n1;
             }
         }
-        // the wave's lanes added in a fixed order (DPP: rows of 16, then the row totals)
-        auto wave_sum = [](double v) {
-#define SA_DPP_ADD(ctrl, rows)                                                                    \
-    do {                                                                                          \
-        const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rows, 0xf, false); \
-        const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, rows, 0xf, false); \
-        v += __hiloint2double(hi_, lo_);                                                          \
-    } while (0)
-            SA_DPP_ADD(0x111, 0xf);
-            SA_DPP_ADD(0x112, 0xf);
-            SA_DPP_ADD(0x114, 0xf);
-            SA_DPP_ADD(0x118, 0xf);
-            SA_DPP_ADD(0x142, 0xa);
-            SA_DPP_ADD(0x143, 0xc);
-#undef SA_DPP_ADD
-            return v;  // (the total in lane 63)
-        };
-        ax = wave_sum(ax), ay = wave_sum(ay), az = wave_sum(az);
+        // the wave's lanes added in a fixed order (the totals in lane 63)
+        ax = wave_sum_dpp(ax), ay = wave_sum_dpp(ay), az = wave_sum_dpp(az);
         if (lane == 63) {
             dmom_r[o] += ax * f;
             dmom_r[o + 1] += ay * f;

@@ -66,17 +66,6 @@ struct SrdShared {
     unsigned char pimg[kdPieces];
 };
 
-// inclusive scan over the 64 lanes of a wave in DPP adds
-__device__ __forceinline__ unsigned srd_wave_scan(unsigned v) {
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);
-    v += (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-
 // ---------------------------------------------------------------------------
 // Lists by tile (Tiling.sort, species.py:775-780; z fastest): a counting sort — histogram,
 // scan, scatter — with the positions copied in list order.
@@ -85,20 +74,6 @@ __device__ __forceinline__ unsigned srd_wave_scan(unsigned v) {
 __device__ __forceinline__ unsigned srd_tile1(double x, double inv, unsigned nt) {
     unsigned t = (unsigned)(i64)((x - 0.0) * inv);
     return t >= nt ? nt - 1 : t;
-}
-
-// runs of equal keys inside a wavefront -> one atomic per run (device-scope atomics execute
-// memory-side on MI355X; particle memory is in mesh-tile order, so runs are long)
-__device__ __forceinline__ void srd_wave_runs(unsigned key, int lane, int &run_start,
-                                              int &run_len) {
-    unsigned prev = __shfl_up(key, 1);
-    bool head = (lane == 0) || (key != prev);
-    unsigned long long mask = __ballot(head);
-    unsigned long long below = mask & (~0ull >> (63 - lane));
-    run_start = 63 - __clzll(below);
-    unsigned long long above = (lane == 63) ? 0ull : (mask >> (lane + 1));
-    int next = above ? (lane + 1 + (__ffsll((long long)above) - 1)) : 64;
-    run_len = next - run_start;
 }
 
 constexpr unsigned kdNoKey = 0xffffffffu;
@@ -131,7 +106,7 @@ __global__ __launch_bounds__(256) void k_srd_histogram(const double *__restrict_
     const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const SrdKey k = srd_key(pos, p, n, inv, nt, rung, lowest_active);
     int rs, rl;
-    srd_wave_runs(k.key, lane, rs, rl);
+    wave_runs(k.key, lane, rs, rl);
     if (lane == rs && k.key != kdNoKey) atomicAdd(&count[k.key], (unsigned)rl);
 }
 __global__ __launch_bounds__(256) void k_srd_scatter(const double *__restrict__ pos, i64 n,
@@ -146,7 +121,7 @@ __global__ __launch_bounds__(256) void k_srd_scatter(const double *__restrict__ 
     const i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     const SrdKey k = srd_key(pos, p, n, inv, nt, rung, lowest_active);
     int rs, rl;
-    srd_wave_runs(k.key, lane, rs, rl);
+    wave_runs(k.key, lane, rs, rl);
     unsigned first = 0;
     if (lane == rs && k.key != kdNoKey)
         first = offset[k.key] + atomicAdd(&cursor[k.key], (unsigned)rl);
@@ -236,7 +211,7 @@ __global__ __launch_bounds__(256) void k_srd_subsort(const unsigned *__restrict_
             v[i] = hist[8 * threadIdx.x + i];
             sum += v[i];
         }
-        unsigned run = srd_wave_scan(sum) - sum;
+        unsigned run = wave_scan_dpp(sum) - sum;
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             base[8 * threadIdx.x + i] = run;
@@ -554,7 +529,7 @@ __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sr_sweep_dense(
     __syncthreads();
     if (wave == 0) {  // counts -> exclusive prefix
         const unsigned cnt = lane < kdPieces ? S.ppre[lane] : 0u;
-        const unsigned incl = srd_wave_scan(cnt);
+        const unsigned incl = wave_scan_dpp(cnt);
         if (lane < kdPieces) S.ppre[lane] = incl - cnt;
         if (lane == kdPieces) S.ppre[kdPieces] = incl;
     }

@@ -491,25 +491,6 @@ struct PrepArgs {
     double *mom2_out;
 };
 
-// sum over the 64 lanes of a wave, in DPP moves (the lanes' order is fixed: reproducible);
-// returned in lane 63
-__device__ __forceinline__ double gk_wave_sum(double v) {
-#define GK_DPP_ADD(ctrl, rows)                                                                    \
-    do {                                                                                          \
-        const int lo_ = __builtin_amdgcn_update_dpp(0, __double2loint(v), ctrl, rows, 0xf, false); \
-        const int hi_ = __builtin_amdgcn_update_dpp(0, __double2hiint(v), ctrl, rows, 0xf, false); \
-        v += __hiloint2double(hi_, lo_);                                                          \
-    } while (0)
-    GK_DPP_ADD(0x111, 0xf);  // row_shr 1, 2, 4, 8: inclusive scan inside the rows of 16 lanes
-    GK_DPP_ADD(0x112, 0xf);
-    GK_DPP_ADD(0x114, 0xf);
-    GK_DPP_ADD(0x118, 0xf);
-    GK_DPP_ADD(0x142, 0xa);  // row_bcast 15, 31: the row totals forward
-    GK_DPP_ADD(0x143, 0xc);
-#undef GK_DPP_ADD
-    return v;
-}
-
 // LDS of the staged block.  A workgroup's allocation is rounded up to 1280 B and three workgroups
 // per CU need <= 53,760 B each (measured with a probe allocation: 53,760 B runs three, 54,016 B
 // two).  T = 16, order 2: the full 19^3 block is 54,872 B.  The 6-point stencil never reads an
@@ -912,7 +893,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(
                 // pass's 80 is held for it — a per-lane accumulator cost the third workgroup
                 // per CU its place)
                 const double e = pvalid ? (n0 * n0 + n1 * n1) + n2 * n2 : 0.0;
-                const double t = gk_wave_sum(e);
+                const double t = wave_sum_dpp(e);  // (fixed order; the total in lane 63)
                 const double acc = __hiloint2double(m2_hi, m2_lo) +
                                    __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(t), 63),
                                                     __builtin_amdgcn_readlane(__double2loint(t), 63));
@@ -929,7 +910,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(
 }
 
 // the wavefronts' partial sums added in a fixed order: 256 workgroups each sum a slice (256 strided
-// sums, then a tree), one workgroup sums the 256 results the same way
+// sums, then block_tree), one workgroup sums the 256 results the same way
 __global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__ part, i64 n,
                                                       double *__restrict__ out) {
     __shared__ double red[256];
@@ -937,13 +918,8 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__
     const i64 lo = (i64)blockIdx.x * per, hi = lo + per < n ? lo + per : n;
     double s = 0;
     for (i64 i = lo + threadIdx.x; i < hi; i += 256) s += part[i];
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int h = 128; h > 0; h >>= 1) {
-        if ((int)threadIdx.x < h) red[threadIdx.x] += red[threadIdx.x + h];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = red[0];
+    s = block_tree<OpPlus>(red, s);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 template <int ORDER, int T>

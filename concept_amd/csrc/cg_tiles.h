@@ -1,7 +1,9 @@
 // cg_tiles.h — device helpers shared by the particle kernels: the reference's mod(),
-// the tile / bucket key of a particle and per-wavefront run detection.
+// the tile / bucket key of a particle; with it come the wave primitives of cg_wave.h (wave_runs
+// turns runs of equal keys into one atomic each).
 #pragma once
 #include "cg_internal.h"
+#include "cg_wave.h"
 
 // Component.drift's mod (species.py:2194-2196, commons.py:5103-5110): numpy floored
 // modulo, then a result that rounded to exactly boxsize becomes 0.
@@ -54,17 +56,3 @@ __device__ __forceinline__ unsigned tile_of(double x, double y, double z, const 
                  (((cc & last) == last) ? 1u : 0u);
     return ((a * t.nty + b) * t.ntz + c) * 8u + f;
 }
-
-// For the calling wave (all 64 lanes active): runs of consecutive lanes with
-// equal key.  Returns the first lane of this lane's run and the run length.
-__device__ __forceinline__ void wave_runs(unsigned key, int lane, int &run_start, int &run_len) {
-    unsigned prev = __shfl_up(key, 1);
-    bool head = (lane == 0) || (key != prev);
-    unsigned long long mask = __ballot(head);
-    unsigned long long below = mask & (~0ull >> (63 - lane));  // heads at lanes <= lane
-    run_start = 63 - __clzll(below);
-    unsigned long long above = (lane == 63) ? 0ull : (mask >> (lane + 1));
-    int next = above ? (lane + 1 + (__ffsll((long long)above) - 1)) : 64;
-    run_len = next - run_start;
-}
-

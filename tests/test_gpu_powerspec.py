@@ -163,6 +163,45 @@ def test_binning_is_deterministic_and_matches_numpy():
     assert nbins > 1024, 'the second binning must exceed the LDS histograms'
 
 
+def test_the_final_reduction_adds_in_the_documented_order():
+    """k_reduce_columns (csrc/cg_wave.h), bit for bit.  cg_powerspec_bin leaves the partial
+    histograms in the caller's workspace, so its second stage can be recomputed from them:
+    workgroup `bin`, thread t folds the partials t, t + 256, ... of the bin in turn from 0.0, then
+    for m = 128, 64, ..., 1 the threads t < m add red[t + m] to red[t].  Grid size 48 on one
+    domain gives min(ceil(48·48/4), 2048) = 576 = 2·256 + 64 partials: threads 0-63 fold three,
+    the others two — the smallest launch with both the strided fold and a ragged last trip."""
+    import torch
+    from concept_amd import commons, lib
+    from concept_amd.mesh import PotentialMesh
+    N, L, nbins = 48, 100.0, 7
+    npartials, k2_max = 576, 3*(N//2)**2
+    commons.load_params({'boxsize': L})
+    mesh = PotentialMesh(N, L)
+    _write_real_mesh(mesh, np.random.default_rng(48).standard_normal((N, N, N)))
+    mesh.fft_forward()
+    table = torch.tensor(np.arange(k2_max + 1)*nbins//(k2_max + 1), dtype=torch.int32,
+                         device='cuda')
+    assert int(table.min()) == 0 and int(table.max()) == nbins - 1
+    assert lib.raw().cg_powerspec_workspace(mesh._ctx, nbins) == npartials*nbins
+    workspace = torch.full((npartials*nbins,), np.nan, dtype=torch.float64, device='cuda')
+    power = torch.empty(nbins, dtype=torch.float64, device='cuda')
+    lib.check(lib.raw().cg_powerspec_bin(mesh._ctx, lib._ptr(table), k2_max, nbins,
+                                         lib._ptr(power), lib._ptr(workspace),
+                                         workspace.numel()))
+    partial = workspace.cpu().numpy().reshape(npartials, nbins)
+    assert np.isfinite(partial).all() and (partial > 0).any(axis=0).all()
+    red = np.zeros((256, nbins))
+    for p0 in range(0, npartials, 256):   # thread t takes partial p0 + t in trip p0/256
+        trip = partial[p0:p0 + 256]
+        red[:len(trip)] = red[:len(trip)] + trip
+    m = 128
+    while m >= 1:
+        red[:m] = red[:m] + red[m:2*m]
+        m >>= 1
+    got = power.cpu().numpy()
+    assert np.array_equal(got.view(np.int64), red[0].view(np.int64)), (got, red[0])
+
+
 # -- the binning beyond the first chunk of 64 kk ------------------------------------------------
 # A wave of k_powerspec_bin walks a row in chunks of 64 kk and carries a pending run from chunk to
 # chunk.  N = 144 (nyq = 72: a second chunk of 8 live lanes, the library FFT's view) and N = 256
