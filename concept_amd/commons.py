@@ -293,6 +293,7 @@ def load_params(source=None, **overrides):
     # commons.py: bispec_antialiasing (cells are weighted by their overlap with the shell);
     # bispec_options and bispec_select are not read
     p.bispec_antialiasing = bool(user.get('bispec_antialiasing', True))
+    _load_ic_params(p, user)
     # nghosts (commons.py:4411-4432): default 2 comes from the PCS default of the
     # power-spectrum and 2D render options; force interpolation and differentiation orders
     # raise it (powerspec_options default: PCS, interlaced -> 4//2 = 2, + 1 with cell-vertex
@@ -417,6 +418,43 @@ def load_params(source=None, **overrides):
     p.user = user
     params = p
     return p
+
+
+def _load_ic_params(p, user):
+    """What the particle realisation reads (commons.py:3742-3832, 3899-3925): the pseudo-random
+    number generator and its seeds, the noise imprinting scheme, fixed amplitudes and the phase
+    shift, and realization_options as {option: {selector: value}} (looked up per component
+    with is_selected).  'structure' defaults to 'primordial' here: the other value, the
+    reference's default for late-time fluid realisations, is not built."""
+    p.random_generator = str(user.get('random_generator', 'PCG64DXSM'))
+    seeds_default = {'general': 0, 'primordial amplitudes': 1_000, 'primordial phases': 2_000}
+    p.random_seeds = dict(user.get('random_seeds') or {})
+    for key, val in seeds_default.items():
+        p.random_seeds[key] = int(p.random_seeds.get(key, val))
+    for key in p.random_seeds:
+        if key not in seeds_default:
+            raise ValueError(f'Key {key} in random_seeds not understood')
+    p.primordial_noise_imprinting = str(
+        user.get('primordial_noise_imprinting', 'distributed')).lower()
+    if p.primordial_noise_imprinting not in {'simple', 'distributed'}:
+        raise ValueError(f'primordial_noise_imprinting = "{p.primordial_noise_imprinting}" '
+                         '∉ {"simple", "distributed"}')
+    p.primordial_amplitude_fixed = bool(user.get('primordial_amplitude_fixed', False))
+    p.primordial_phase_shift = float(user.get('primordial_phase_shift', 0))
+    defaults = {'backscale': False, 'lpt': 1, 'dealias': False, 'nongaussianity': 0.0,
+                'structure': 'primordial'}
+    simplify = lambda s: (s.lower().replace('-', '').replace('_', '').replace(' ', '')
+                          if isinstance(s, str) else s)
+    options = {}
+    for key, d in dict(user.get('realization_options') or {}).items():
+        key = simplify(key)
+        key = {'nongauss': 'nongaussianity', 'nongaussian': 'nongaussianity'}.get(key, key)
+        if not isinstance(d, dict):
+            d = {'default': d}
+        options[key] = {sel: simplify(val) for sel, val in d.items()}
+    for key, val in defaults.items():
+        options.setdefault(key, {}).setdefault('default', val)
+    p.realization_options = options
 
 
 def _interlace2latticekind(interlace):

@@ -1,0 +1,260 @@
+// cg_lpt.hip — the mesh and particle passes of the 1LPT / 2LPT particle realisation.
+//   k_lpt_potential  realize_grid (scalar case)         ic.py:711-764
+//                    fused with laplacian_inverse       mesh.py:3422-3437
+//   k_lpt_diff       fourier_diff                       mesh.py:3466-3510
+//   k_lpt_product    the grid product and the move to the output grid of handle_lpt_term
+//                                                       ic.py:2020-2057
+//   k_lpt_displace   displace_particles                 ic.py:2249-2280
+// All four are streaming maps: one grid-stride loop, a thread per complex mode or per pair of
+// neighbouring real cells (16-byte loads and stores), no LDS, no atomics, nothing wave-level.
+// The k-space kernels walk the Fourier view of the contexts (cg_ctx::four, the view
+// k_fourier_operate walks) over the N/2 + 1 modes of every row, the real-space kernels the N
+// cells of the N rows of the owned layers: the row padding and the unused row of a layer are
+// neither read nor written.  Compiled with -ffp-contract=off: every product and sum is rounded
+// on its own, in the reference's order.  FP64 throughout.
+#include "cg_internal.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kMaxBlocks = 256 * 8;  // 8 workgroups per CU, the rest by grid stride
+const double kPi = 3.141592653589793;  // float(np.pi), commons.py:1816
+
+unsigned grid_for(i64 work) {
+    i64 b = (work + kThreads - 1) / kThreads;
+    return (unsigned)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
+}
+
+bool same_geometry(const cg_ctx *a, const cg_ctx *b) {
+    return a->N == b->N && a->pad == b->pad && a->ny == b->ny && a->xmap.nxl == b->xmap.nxl &&
+           a->xmap.x0 == b->xmap.x0 && a->f_si == b->f_si && a->f_j0 == b->f_j0 &&
+           a->f_nj == b->f_nj;
+}
+
+struct LptPotential {
+    const double *amp;  // amplitudes by k2 (null: the modes are taken as they are)
+    int shifted;
+    double A, B, Cc;    // ℝ[-2*π/gridsize*shift[d]] of fourier_loop, for the negated lattice shift
+    double lap;         // ℝ[-factor/k_fundamental**2]
+};
+
+// dst = (amp[k2] * rotated src) * (lap / k2) off the origin and the Nyquist planes, 0 on them
+__global__ __launch_bounds__(kThreads) void k_lpt_potential(double2 *dst, const double2 *src,
+                                                            int N, i64 dst_si, i64 src_si, i64 cp,
+                                                            int j0, int nj, LptPotential P) {
+#pragma clang fp contract(off)
+    const int nyq = N / 2, nk = nyq + 1;
+    const i64 total = (i64)N * nj * nk;
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const int row = (int)(e / nk), kk = (int)(e - (i64)row * nk);
+        const int a = row / nj, bl = row - a * nj, b = j0 + bl;
+        const i64 ki = a - (a >= nyq ? N : 0), kj = b - (b >= nyq ? N : 0);
+        const i64 k2 = (kj * kj + ki * ki) + (i64)kk * kk;  // ic.py:714
+        double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
+        if (a != nyq && b != nyq && kk != nyq && k2 != 0) {
+            const double2 z = src[(i64)a * src_si + (i64)bl * cp + kk];
+            double re = z.x, im = z.y;
+            if (P.shifted) {  // mesh.py:2873-2888, ic.py:719-726
+                const double theta = ((double)ki * P.A + (double)kj * P.B) + (double)kk * P.Cc;
+                const double c = cos(theta), s = sin(theta);
+                const double re2 = re * c - im * s, im2 = re * s + im * c;
+                re = re2;
+                im = im2;
+            }
+            if (P.amp) {  // ic.py:715, 761-762
+                const double amplitude = P.amp[k2];
+                re = amplitude * re;
+                im = amplitude * im;
+            }
+            const double inv = P.lap / (double)k2;  // mesh.py:3434-3436
+            out = make_double2(re * inv, im * inv);
+        }
+        dst[(i64)a * dst_si + (i64)bl * cp + kk] = out;
+    }
+}
+
+// dst = i k_dim0 src (dim1 < 0) or -k_dim0 k_dim1 src, times factor; 0 on the origin and the
+// Nyquist planes (the nullified output slab of mesh.py:3477)
+__global__ __launch_bounds__(kThreads) void k_lpt_diff(double2 *dst, const double2 *src, int N,
+                                                       i64 dst_si, i64 src_si, i64 cp, int j0,
+                                                       int nj, int dim0, int dim1, double scale) {
+#pragma clang fp contract(off)
+    const int nyq = N / 2, nk = nyq + 1;
+    const i64 total = (i64)N * nj * nk;
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const int row = (int)(e / nk), kk = (int)(e - (i64)row * nk);
+        const int a = row / nj, bl = row - a * nj, b = j0 + bl;
+        const int ki = a - (a >= nyq ? N : 0), kj = b - (b >= nyq ? N : 0);
+        double2 out = make_double2(0.0, 0.0);
+        if (a != nyq && b != nyq && kk != nyq && (ki | kj | kk) != 0) {
+            const double2 z = src[(i64)a * src_si + (i64)bl * cp + kk];
+            const int kl0 = dim0 == 0 ? ki : (dim0 == 1 ? kj : kk);
+            if (dim1 < 0) {
+                const double amplitude = scale * (double)kl0;  // mesh.py:3496
+                out = make_double2(amplitude * -z.y, amplitude * z.x);
+            } else {
+                const int kl1 = dim1 == 0 ? ki : (dim1 == 1 ? kj : kk);
+                const double amplitude = scale * (double)kl0 * (double)kl1;  // mesh.py:3506
+                out = make_double2(amplitude * -z.x, amplitude * -z.y);
+            }
+        }
+        dst[(i64)a * dst_si + (i64)bl * cp + kk] = out;
+    }
+}
+
+// out (= | += | -=) factor * a * b over the real cells; the three grids may be one another
+template <int kOp>
+__global__ __launch_bounds__(kThreads) void k_lpt_product(double *out, const double *a,
+                                                          const double *b, int N, i64 nrows, i64 ny,
+                                                          i64 pad, double factor) {
+#pragma clang fp contract(off)
+    const int half = N / 2;  // pairs of cells per row (N is even)
+    const i64 total = nrows * half;
+    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
+         t += (i64)gridDim.x * kThreads) {
+        const i64 row = t / half;
+        const int p = (int)(t - row * half);
+        const i64 layer = row / N;
+        const i64 off = (layer * ny + (row - layer * N)) * pad + 2 * p;
+        const double2 x = *(const double2 *)(a + off), y = *(const double2 *)(b + off);
+        double2 v = make_double2(x.x * y.x, x.y * y.y);  // ic.py:2020-2021
+        if (factor != 1) v = make_double2(factor * v.x, factor * v.y);  // ic.py:2042-2057
+        double2 *o = (double2 *)(out + off);
+        if (kOp == 0) {
+            *o = v;
+        } else {
+            const double2 w = *o;
+            *o = kOp == 1 ? make_double2(w.x + v.x, w.y + v.y) : make_double2(w.x - v.x, w.y - v.y);
+        }
+    }
+}
+
+// particle p = (i*N + j)*N + k of the rows from index_bgn on takes cell (i, j, k) of psi
+__global__ __launch_bounds__(kThreads) void k_lpt_displace(const double *psi, int N, i64 ny,
+                                                           i64 pad, double *pos, double *mom,
+                                                           int dim, double pos_factor,
+                                                           double mom_factor) {
+#pragma clang fp contract(off)
+    const int half = N / 2;
+    const i64 total = (i64)N * N * half;
+    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
+         t += (i64)gridDim.x * kThreads) {
+        const i64 row = t / half;  // i*N + j
+        const int kp = (int)(t - row * half);
+        const i64 i = row / N;
+        const double2 v = *(const double2 *)(psi + (i * ny + (row - i * N)) * pad + 2 * kp);
+        const i64 r = 3 * (row * N + 2 * kp) + dim;
+        if (pos_factor != 0) {  // ic.py:2277-2279 (1*psi is psi: no branch for a factor of 1)
+            pos[r] = pos[r] + pos_factor * v.x;
+            pos[r + 3] = pos[r + 3] + pos_factor * v.y;
+        }
+        if (mom_factor != 0) {
+            mom[r] = mom[r] + mom_factor * v.x;
+            mom[r + 3] = mom[r + 3] + mom_factor * v.y;
+        }
+    }
+}
+
+int fourier_pair_checks(const char *name, cg_ctx *dst, cg_ctx *src) {
+    CG_CHECK(dst && src, "%s: null context", name);
+    CG_CHECK(dst->four != nullptr && src->four != nullptr,
+             "%s: no Fourier buffer bound (cg_dist_bind_fourier)", name);
+    CG_CHECK(dst->N >= 2 && dst->N % 2 == 0, "%s: grid size %lld is not even", name,
+             (long long)dst->N);
+    CG_CHECK(same_geometry(dst, src), "%s: the two meshes differ in grid size or domain", name);
+    CG_CHECK(dst->N * (i64)dst->f_nj < ((i64)1 << 31), "%s: %lld rows", name,
+             (long long)(dst->N * (i64)dst->f_nj));
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cg_lpt_potential(cg_ctx *dst, cg_ctx *noise_src, const double *amplitudes,
+                                int64_t k2_max, const double *shift, double factor) {
+    if (fourier_pair_checks("cg_lpt_potential", dst, noise_src)) return 1;
+    const i64 nyq = dst->N / 2;
+    CG_CHECK(!amplitudes || k2_max == 3 * (nyq - 1) * (nyq - 1),
+             "cg_lpt_potential: %lld amplitudes for grid size %lld, which needs "
+             "3*(nyquist - 1)**2 + 1 = %lld", (long long)(k2_max + 1), (long long)dst->N,
+             (long long)(3 * (nyq - 1) * (nyq - 1) + 1));
+    LptPotential P{};
+    P.amp = amplitudes;
+    P.shifted = shift && (shift[0] != 0 || shift[1] != 0 || shift[2] != 0);
+    if (P.shifted) {
+        // the positions have been shifted by +shift, fourier_loop assumes -shift (ic.py:692-695)
+        P.A = -2 * kPi / (double)dst->N * -shift[0];
+        P.B = -2 * kPi / (double)dst->N * -shift[1];
+        P.Cc = -2 * kPi / (double)dst->N * -shift[2];
+    }
+    const double k_fundamental = 2 * kPi / dst->p.boxsize;
+    P.lap = -factor / (k_fundamental * k_fundamental);
+    const i64 total = dst->N * (i64)dst->f_nj * (nyq + 1);
+    hipLaunchKernelGGL(k_lpt_potential, dim3(grid_for(total)), dim3(kThreads), 0, dst->stream,
+                       dst->four, (const double2 *)noise_src->four, (int)dst->N, dst->f_si,
+                       noise_src->f_si, dst->pad / 2, dst->f_j0, dst->f_nj, P);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_lpt_diff(cg_ctx *dst, cg_ctx *src, int dim0, int dim1, double factor) {
+    if (fourier_pair_checks("cg_lpt_diff", dst, src)) return 1;
+    CG_CHECK(dim0 >= 0 && dim0 < 3 && dim1 >= -1 && dim1 < 3,
+             "cg_lpt_diff: dimensions (%d, %d) outside 0..2 (the second may be -1)", dim0, dim1);
+    // the first derivative with factor 1 into another mesh is fourier_operate(diff_dim) to the bit
+    if (dim1 < 0 && factor == 1 && dst != src)
+        return cgk_fourier_operate(dst, src, 0, 1, nullptr, dim0, 0);
+    const double k_fundamental = 2 * kPi / dst->p.boxsize;
+    const double scale = dim1 < 0 ? factor * k_fundamental
+                                  : factor * (k_fundamental * k_fundamental);
+    const i64 total = dst->N * (i64)dst->f_nj * (dst->N / 2 + 1);
+    hipLaunchKernelGGL(k_lpt_diff, dim3(grid_for(total)), dim3(kThreads), 0, dst->stream,
+                       dst->four, (const double2 *)src->four, (int)dst->N, dst->f_si, src->f_si,
+                       dst->pad / 2, dst->f_j0, dst->f_nj, dim0, dim1, scale);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double factor) {
+    CG_CHECK(out && a && b, "cg_lpt_product: null context");
+    CG_CHECK(op >= 0 && op <= 2, "cg_lpt_product: operation %d not in {0 '=', 1 '+=', 2 '-='}", op);
+    CG_CHECK(out->N >= 2 && out->N % 2 == 0, "cg_lpt_product: grid size %lld is not even",
+             (long long)out->N);
+    CG_CHECK(same_geometry(out, a) && same_geometry(out, b),
+             "cg_lpt_product: the meshes differ in grid size or domain");
+    const i64 nrows = out->xmap.nxl * out->N;
+    const i64 total = nrows * (out->N / 2);
+#define CG_LPT_PRODUCT(OP)                                                                      \
+    hipLaunchKernelGGL(k_lpt_product<OP>, dim3(grid_for(total)), dim3(kThreads), 0, out->stream, \
+                       out->mesh0, (const double *)a->mesh0, (const double *)b->mesh0,          \
+                       (int)out->N, nrows, out->ny, out->pad, factor)
+    if (op == 0) CG_LPT_PRODUCT(0);
+    else if (op == 1) CG_LPT_PRODUCT(1);
+    else CG_LPT_PRODUCT(2);
+#undef CG_LPT_PRODUCT
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
+                               int64_t index_bgn, int dim, double pos_factor, double mom_factor) {
+    CG_CHECK(psi, "cg_lpt_displace: null context");
+    CG_CHECK(dim >= 0 && dim < 3, "cg_lpt_displace: dim = %d not in {0, 1, 2}", dim);
+    if (n == 0) return 0;
+    CG_CHECK(psi->p.nprocs == 1, "cg_lpt_displace: single-domain entry point");
+    CG_CHECK(psi->N % 2 == 0 && n == psi->N * psi->N * psi->N,
+             "cg_lpt_displace: %lld particles for a lattice of %lld**3 cells", (long long)n,
+             (long long)psi->N);
+    CG_CHECK(index_bgn >= 0, "cg_lpt_displace: index_bgn = %lld < 0", (long long)index_bgn);
+    CG_CHECK((pos || pos_factor == 0) && (mom || mom_factor == 0),
+             "cg_lpt_displace: null particle array with a non-zero factor");
+    if (pos_factor == 0 && mom_factor == 0) return 0;
+    psi->prep_valid = false;  // (momenta written)
+    hipLaunchKernelGGL(k_lpt_displace, dim3(grid_for(n / 2)), dim3(kThreads), 0, psi->stream,
+                       (const double *)psi->mesh0, (int)psi->N, psi->ny, psi->pad,
+                       pos ? pos + 3 * index_bgn : nullptr, mom ? mom + 3 * index_bgn : nullptr,
+                       dim, pos_factor, mom_factor);
+    CG_LAUNCH_CHECK();
+    return 0;
+}

@@ -1,0 +1,531 @@
+"""Initial conditions: 1LPT / 2LPT particle realisation (ic.py:67-232, 599-627, 928-1589,
+1895-2280 of the reference).
+
+The reference gets two things from CLASS — a table of amplitudes T(k)·ζ(k) indexed by k² and a
+handful of growth factors — and does everything after that on meshes.  Here both are inputs
+(`amplitudes_from_power` makes the table from a tabulated P(k)) and the mesh work runs on the
+GPU (csrc/cg_lpt.hip through PotentialMesh.lpt_*):
+
+    noise (host, numpy's own generators: the reference's random streams, number for number)
+      -> Φ⁽¹⁾ = ∇⁻²(amplitude·noise)            lpt_potential
+      -> Ψ⁽¹⁾ᵢ = ∂ᵢΦ⁽¹⁾, back to real space      lpt_diff + the mesh's inverse transform
+      -> positions += Ψ, momenta += factor·Ψ    lpt_displace
+    2LPT: the six products of second derivatives of Φ⁽¹⁾ (lpt_diff, lpt_product) summed into
+    the source of Φ⁽²⁾, transformed, ∇⁻², and displaced the same way.
+
+Out of scope, refused by name: 3LPT, Orszag dealiasing, non-Gaussianity, non-primordial
+structure, fluid components, N without a cubic lattice, several domains."""
+import contextlib
+import math
+
+import numpy as np
+import torch
+
+from . import comm as _comm
+from . import commons
+from .commons import is_selected, π
+from .lib import ConceptGPUError
+
+
+# ---- pseudo-random numbers (ic.py:67-232) ------------------------------------------------
+class PseudoRandomNumberGenerator:
+    """The reference's generator: a numpy bit generator seeded with the salted seed, children
+    by spawn key, every distribution drawn through a cache of `cache_size` numbers.  draws()
+    hands out the next n numbers of a distribution at once — the same numbers, in the same
+    order, as n single draws."""
+    streams = {name: attr for name, attr in vars(np.random).items()
+               if isinstance(attr, type) and issubclass(attr, np.random.BitGenerator)
+               and attr is not np.random.BitGenerator}
+
+    def __init__(self, seed=None, stream=None, cache_size=2**12, salt=True):
+        if stream is None:
+            stream = commons.params.random_generator if commons.params else 'PCG64DXSM'
+        if salt and isinstance(seed, int):
+            seed += int(π*1e+8)  # no seeds of many zero bits
+            seed += 137          # the reference's hand-picked offset
+        if not isinstance(seed, np.random.SeedSequence):
+            seed = np.random.SeedSequence(seed)
+        self.seed = seed
+        self.stream = stream
+        self.cache_size = cache_size
+        bit_generator = self.streams.get(stream)
+        if bit_generator is None:
+            names = ', '.join(f'"{s}"' for s in self.streams)
+            raise ConceptGPUError(f'Pseudo-random bit generator "{stream}" not available in '
+                                  f'NumPy. The available ones are {names}.')
+        self.generator = np.random.Generator(bit_generator(self.seed))
+        self._cache = {}  # distribution -> (numbers, how many of them are used)
+
+    def spawn(self, spawn_key=0):
+        spawn_key = tuple(spawn_key) if isinstance(spawn_key, (tuple, list)) else (spawn_key,)
+        seed = np.random.SeedSequence(self.seed.entropy,
+                                      spawn_key=(self.seed.spawn_key + spawn_key))
+        return type(self)(seed, self.stream, self.cache_size)
+
+    def draws(self, distribution, n):
+        """the next n unit-scale numbers of 'uniform' [0, 1), 'gaussian' or 'rayleigh'"""
+        out = np.empty(n, dtype=np.float64)
+        cache, used = self._cache.get(distribution, (None, self.cache_size))
+        filled = 0
+        while filled < n:
+            if used == self.cache_size:
+                cache = {'uniform': lambda: self.generator.uniform(0, 1, size=self.cache_size),
+                         'gaussian': lambda: self.generator.normal(0, 1, size=self.cache_size),
+                         'rayleigh': lambda: self.generator.rayleigh(1, size=self.cache_size),
+                         }[distribution]()
+                used = 0
+            take = min(n - filled, self.cache_size - used)
+            out[filled:filled + take] = cache[used:used + take]
+            filled += take
+            used += take
+        self._cache[distribution] = (cache, used)
+        return out
+
+    def uniform(self, low=0, high=1, n=1):
+        return low + self.draws('uniform', n)*(high - low)
+
+    def gaussian(self, scale=1, n=1):
+        return self.draws('gaussian', n)*scale
+
+    def rayleigh(self, scale=1, n=1):
+        return self.draws('rayleigh', n)*scale
+
+
+# ---- the Fourier space-filling curve (mesh.py:3053-3096) -----------------------------------
+def fourier_curve_key(ki, kj, kk):
+    """The place of mode (ki, kj, kk) on the curve that fills Fourier space outwards from the
+    origin, shell by shell of max(|ki|, |kj|, kk) (get_fourier_curve_key); int64 arrays."""
+    ki, kj, kk = (np.asarray(v, dtype=np.int64) for v in (ki, kj, kk))
+    ki_abs, kj_abs = np.abs(ki), np.abs(kj)
+    kl = np.where(ki_abs > kj_abs, ki, np.where(ki_abs < kj_abs, kj, np.maximum(ki, kj)))
+    kl_abs = np.abs(kl)
+    s = np.where(kl_abs < kk, kk, kl_abs + (kl > 0))
+    return np.select(
+        [kk == s, kj == -s, ki == -s, ki != s - 1],
+        [kj + s*(2*ki + s*(4*s + 2) + 1),
+         kk + s*(ki + s*(4*s - 1)),
+         kk + s*(kj + s*(4*s - 3)),
+         kk + s*(ki + s*(4*s - 5) + 2)],
+        kk + s*(kj + s*(4*s - 7) + 3))
+
+
+def _curve_order_slice(gridsize):
+    """(ki, kk) of one j-slice off the Nyquist planes in visiting order: the curve's order for
+    the slice kj = 0, whatever the slice (fourier_curve_slice_loop, mesh.py:2984-3044)"""
+    nyquist = gridsize//2
+    ki, kk = np.meshgrid(np.arange(-nyquist + 1, nyquist), np.arange(nyquist), indexing='ij')
+    ki, kk = ki.ravel(), kk.ravel()
+    order = np.argsort(fourier_curve_key(ki, np.zeros_like(ki), kk), kind='stable')
+    return ki[order], kk[order]
+
+
+def _curve_order(gridsize):
+    """(ki, kj, kk) of the whole grid off the Nyquist planes in the curve's order
+    (fourier_curve_loop, mesh.py:2909-2962)"""
+    nyquist = gridsize//2
+    full = np.arange(-nyquist + 1, nyquist)
+    ki, kj, kk = (v.ravel() for v in np.meshgrid(full, full, np.arange(nyquist), indexing='ij'))
+    order = np.argsort(fourier_curve_key(ki, kj, kk), kind='stable')
+    return ki[order], kj[order], kk[order]
+
+
+# ---- primordial noise (ic.py:928-1163) ---------------------------------------------------------
+def generate_primordial_noise(gridsize, fixed_amplitude=False, phase_shift=0, params=None):
+    """The Fourier slab of primordial white noise of one domain, double[j][i][gridsize + 2] in
+    the reference's transposed layout: r·exp(iθ) with r Rayleigh(1/√2) (1 when fixed_amplitude)
+    and θ uniform in [-π, π) (+ phase_shift), imprinted by params.primordial_noise_imprinting
+    ('distributed': streams per j-slice spawned by kj; 'simple': one stream pair along the
+    whole curve), the kk = 0 plane Hermitian, the origin zero; the Nyquist planes stay zero."""
+    p = params or commons.params
+    if p is None:
+        raise ConceptGPUError('no parameters loaded: call concept_amd.commons.load_params()')
+    g = int(gridsize)
+    if g < 2 or g % 2:
+        raise ConceptGPUError(f'generate_primordial_noise(): grid size {g} must be even and ≥ 2')
+    nyquist = g//2
+    slab = np.zeros((g, g, g + 2), dtype=np.float64)
+    prng_amplitudes_common = PseudoRandomNumberGenerator(
+        p.random_seeds['primordial amplitudes'], p.random_generator)
+    prng_phases_common = PseudoRandomNumberGenerator(
+        p.random_seeds['primordial phases'], p.random_generator)
+    scale = 1/math.sqrt(2)
+
+    def polar(prng_r, prng_θ, n):
+        r = 1.0 if fixed_amplitude else prng_r.rayleigh(scale, n)
+        return r, prng_θ.uniform(-π, π, n)
+
+    def finalize(r, θ, mask):
+        θ = θ[mask]
+        if phase_shift:
+            θ = θ + phase_shift
+        r = r if fixed_amplitude else r[mask]
+        return r*np.cos(θ), r*np.sin(θ)
+
+    scheme = p.primordial_noise_imprinting
+    if scheme == 'simple':
+        ki, kj, kk = _curve_order(g)
+        r, θ = polar(prng_amplitudes_common, prng_phases_common, ki.size)
+        lower_x_zdc = (ki < 0) | ((ki == 0) & (kj < 0))
+        imprint = (kk != 0) | lower_x_zdc
+        imprint_conj = (kk == 0) & lower_x_zdc
+        re, im = finalize(r, θ, imprint)
+        slab[kj[imprint] % g, ki[imprint] % g, 2*kk[imprint]] = re
+        slab[kj[imprint] % g, ki[imprint] % g, 2*kk[imprint] + 1] = im
+        re, im = finalize(r, θ, imprint_conj)
+        slab[-kj[imprint_conj] % g, -ki[imprint_conj] % g, 0] = +re
+        slab[-kj[imprint_conj] % g, -ki[imprint_conj] % g, 1] = -im
+    elif scheme == 'distributed':
+        spawn_key_offset = 2**32  # negative seeds not allowed
+        ki, kk = _curve_order_slice(g)
+        i = ki % g
+        i_conj = -ki % g
+        for j in range(g):
+            kj = j - (g if j >= nyquist else 0)
+            if kj == -nyquist:
+                continue
+            r, θ = polar(prng_amplitudes_common.spawn(spawn_key_offset + kj),
+                         prng_phases_common.spawn(spawn_key_offset + kj), ki.size)
+            r_conj, θ_conj = polar(prng_amplitudes_common.spawn(spawn_key_offset - kj),
+                                   prng_phases_common.spawn(spawn_key_offset - kj), ki.size)
+            # off the kk = 0 plane every point takes its own numbers; on it the lower x half
+            # (ki < 0, or ki = 0 and kj < 0) does, and the other half takes the conjugate of
+            # what the slice at -kj drew for the reflected point
+            on_zdc = (kk == 0)
+            imprint = ~on_zdc | (ki < 0) | ((ki == 0) & (kj < 0))
+            imprint_conj = on_zdc & ~((ki > 0) | ((ki == 0) & (-kj > 0)))
+            re, im = finalize(r, θ, imprint)
+            slab[j, i[imprint], 2*kk[imprint]] = re
+            slab[j, i[imprint], 2*kk[imprint] + 1] = im
+            re, im = finalize(r_conj, θ_conj, imprint_conj)
+            slab[j, i_conj[imprint_conj], 0] = +re
+            slab[j, i_conj[imprint_conj], 1] = -im
+    else:
+        raise ConceptGPUError(f'primordial_noise_imprinting = "{scheme}" not implemented')
+    slab[0, 0, 0] = slab[0, 0, 1] = 0  # nullify_modes(slab, 'origin')
+    return slab
+
+
+# ---- amplitudes (ic.py:599-627) ------------------------------------------------------------------
+def amplitudes_from_power(k, P, gridsize, boxsize):
+    """The k²-indexed table get_amplitudes hands to realize_grid, from a tabulated power
+    spectrum: amplitudes[k2] = sqrt(P(k_f·√k2))·boxsize**(-1.5) for k2 = 1 .. 3(nyquist-1)²,
+    P interpolated linearly in (log k, log P); amplitudes[0] = 0."""
+    k, P = np.asarray(k, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    if k.ndim != 1 or k.shape != P.shape or k.size < 2 or np.any(np.diff(k) <= 0):
+        raise ConceptGPUError('amplitudes_from_power(): k must be increasing, P of its length')
+    nyquist = int(gridsize)//2
+    k2_max = 3*(nyquist - 1)**2
+    k_fundamental = 2*π/boxsize
+    amplitudes = np.zeros(k2_max + 1, dtype=np.float64)
+    k_magnitude = k_fundamental*np.sqrt(np.arange(1, k2_max + 1, dtype=np.float64))
+    if k2_max and (k_magnitude[0] < k[0] or k_magnitude[-1] > k[-1]):
+        raise ConceptGPUError(
+            f'amplitudes_from_power(): the table covers k in [{k[0]}, {k[-1]}], the grid needs '
+            f'[{k_magnitude[0]}, {k_magnitude[-1]}]')
+    amplitudes[1:] = np.sqrt(np.exp(np.interp(np.log(k_magnitude), np.log(k), np.log(P)))
+                             )*boxsize**(-1.5)
+    return amplitudes
+
+
+# ---- lattices (mesh.py:78-182) ----------------------------------------------------------------
+def lattice_shifts(kind, cell_centered=True):
+    """The shifts, in grid units and as applied to particles, of the primitive simple cubic
+    lattices of a 'sc', 'bcc' or 'fcc' lattice: -½ on cell-centred grids, +½ on cell-vertex."""
+    s = (1 - 2*bool(cell_centered))*0.5
+    return {'sc': [(0, 0, 0)],
+            'bcc': [(0, 0, 0), (s, s, s)],
+            'fcc': [(0, 0, 0), (0, s, s), (s, 0, s), (s, s, 0)]}[kind]
+
+
+def preic_lattice(N):
+    """'sc', 'bcc', 'fcc' for N, N/2, N/4 cubic, else '' (species.py:1107-1117)"""
+    def iscubic(n):
+        return round(n**(1/3))**3 == n
+    if iscubic(N):
+        return 'sc'
+    if N % 2 == 0 and iscubic(N//2):
+        return 'bcc'
+    if N % 4 == 0 and iscubic(N//4):
+        return 'fcc'
+    return ''
+
+
+# Record updated by realize_particles(), as in the reference (ic.py:1406-1411)
+n_particles_realized = {'components_tally': 0, 'components_total': 0, 'particles_tally': 0}
+
+
+def reset_tally():
+    n_particles_realized.update(components_tally=0, components_total=0, particles_tally=0)
+
+
+# ---- pre-initialisation (ic.py:2138-2223) ---------------------------------------------------------
+def preinitialize_particles(component, n_particles=-1, index_bgn=0, id_bgn=0,
+                            shift=(0, 0, 0)):
+    """Rows [index_bgn, index_bgn + n_particles) of the component at the points of a simple
+    cubic lattice (cell centres on cell-centred grids) moved by `shift` grid units, row
+    (i·g + j)·g + k at point (i, j, k) with identifier id_bgn + that number, momenta zero.
+    Torch expressions: (c + i)·(boxsize/g) in FP64 is the reference's value to the bit."""
+    if component.representation != 'particles':
+        return 0
+    p = component.params
+    if n_particles == -1:
+        n_particles = component.N
+    g = round(n_particles**(1/3))
+    if g**3 != n_particles:
+        raise ConceptGPUError(f'preinitialize_particles() called with non-cubic number of '
+                              f'particles {n_particles}')
+    if component.N_local < index_bgn + n_particles:
+        raise ConceptGPUError('Component passed to preinitialize_particles() is too small')
+    rows = slice(index_bgn, index_bgn + n_particles)
+    pos = component.pos[rows].view(g, g, g, 3)
+    index = torch.arange(g, dtype=torch.float64, device=pos.device)
+    spacing = p.boxsize/g
+    for dim, view in enumerate(((g, 1, 1), (1, g, 1), (1, 1, g))):
+        c = (0 + 0.5*bool(p.cell_centered)) + shift[dim]
+        pos[..., dim] = ((c + index)*spacing).view(view)
+    component.ids[rows] = id_bgn + torch.arange(n_particles, dtype=torch.int64,
+                                                 device=pos.device)
+    component.mom[rows] = 0
+    return n_particles
+
+
+def wrap_positions(pos, boxsize):
+    """pos = mod(pos, boxsize) with the reference's mod (commons.py:5108-5113): the remainder
+    with the sign of boxsize, and 0 where that rounds to boxsize.  A torch expression."""
+    pos.remainder_(boxsize)
+    pos.masked_fill_(pos == boxsize, 0.0)
+    return pos
+
+
+# ---- the driver (ic.py:1199-1589) ---------------------------------------------------------------
+GROWTH_FACTOR_KEYS = ('D1', 'f1', 'D2', 'f2', 'D3a', 'f3a', 'D3b', 'f3b', 'D3c', 'f3c')
+
+
+def realization_options(component):
+    p = component.params
+    return {key: is_selected(component, d) for key, d in p.realization_options.items()}
+
+
+def _check_scope(component, options):
+    name = component.name
+    lpt = options['lpt']
+    if lpt == 3:
+        raise ConceptGPUError(f'{name}: realization_options["lpt"] = 3: 3LPT is not '
+                              'implemented (1LPT and 2LPT are)')
+    if lpt not in {1, 2}:
+        raise ConceptGPUError(f'{name}: realize_particles() called with attempted {lpt}LPT, '
+                              'though only 1LPT and 2LPT are implemented')
+    if options['dealias']:
+        raise ConceptGPUError(f'{name}: realization_options["dealias"]: Orszag dealiasing of '
+                              'the LPT products is not implemented')
+    if options['nongaussianity'] != 0:
+        raise ConceptGPUError(f'{name}: realization_options["nongaussianity"] = '
+                              f'{options["nongaussianity"]}: non-Gaussian initial conditions are '
+                              'not implemented')
+    if options['structure'] != 'primordial':
+        raise ConceptGPUError(f'{name}: Can only realize particles using the primordial '
+                              f'structure, not "{options["structure"]}"')
+    if component.representation != 'particles':
+        raise ConceptGPUError(f'{name}: realize_particles() called with a non-particle '
+                              'component (fluid realisation is not implemented)')
+    if not preic_lattice(component.N):
+        raise ConceptGPUError(
+            f'Cannot initialize particle component {name} with N = {component.N} on a lattice, '
+            'as neither of {N, N/2, N/4} is a cubic number')
+    if _comm.active() is not None or getattr(component, 'nprocs', 1) > 1:
+        raise ConceptGPUError(f'{name}: realize_particles() with an active comm process group: '
+                              'multi-GPU realisation is not implemented')
+
+
+class _Stopwatch:
+    """event pairs around the passes of one realisation, summed by kind (tools/ic_time.py)"""
+    def __init__(self, timings):
+        self.timings, self.pairs = timings, []
+
+    @contextlib.contextmanager
+    def __call__(self, kind):
+        if self.timings is None:
+            yield
+            return
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        yield
+        e1.record()
+        self.pairs.append((kind, e0, e1))
+
+    def finish(self):
+        if self.timings is None:
+            return
+        torch.cuda.synchronize()
+        for kind, e0, e1 in self.pairs:
+            self.timings[kind] = self.timings.get(kind, 0.0) + e0.elapsed_time(e1)
+            self.timings[kind + ' passes'] = self.timings.get(kind + ' passes', 0) + 1
+
+
+def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_factors=None,
+                      cosmology=None, components_all=None, timings=None):
+    """Realise a particle component at scale factor a (realize_particles, ic.py:1199-1400):
+    particles on their lattice, displaced and boosted by 1LPT and, with
+    realization_options['lpt'] = 2, 2LPT; positions wrapped into [0, boxsize).
+
+    amplitudes: the k²-indexed table of δ (amplitudes_from_power, or the caller's own transfer
+      functions, signed as they wish); amplitudes_θ: that of θ, needed without back-scaling.
+    growth_factors: dict with the reference's keys ('D1', 'f1', 'D2', 'f2', ...) at a; needed
+      with back-scaling or 2LPT.
+    cosmology: an integration.Cosmology (H(a)); default: one of the component's parameters.
+    components_all: every component of the run; those that are particles with mass -1 are the
+      ones to be realised and decide the lattice of each (1: sc, 2: bcc, 4: fcc by tally).
+    timings: a dict that receives milliseconds by kind of pass (synchronises)."""
+    options = realization_options(component)
+    _check_scope(component, options)
+    p = component.params
+    backscale, lpt = bool(options['backscale']), int(options['lpt'])
+    if not backscale and amplitudes_θ is None:
+        raise ConceptGPUError(f'{component.name}: without back-scaling the momenta come from '
+                              'the amplitudes of θ: pass amplitudes_θ')
+    growth_factors = dict(growth_factors or {})
+    if backscale or lpt > 1:
+        need = ('D1', 'f1') + (('D2', 'f2') if lpt > 1 else ())
+        missing = [key for key in need if key not in growth_factors]
+        if missing:
+            raise ConceptGPUError(f'{component.name}: growth factors {missing} are needed')
+    for key in GROWTH_FACTOR_KEYS:
+        growth_factors.setdefault(key, math.nan)
+    if cosmology is None:
+        from .integration import Cosmology
+        cosmology = Cosmology(p)
+    # the lattice (ic.py:1231-1281)
+    tally = n_particles_realized
+    if tally['components_tally'] == 0:
+        others = [c for c in (components_all or [component])
+                  if c.representation == 'particles' and c.mass == -1]
+        tally['components_total'] = len(others)
+    kind = preic_lattice(component.N)
+    shifts = lattice_shifts(kind, p.cell_centered)
+    if kind == 'sc':
+        kind_all = {2: 'bcc', 4: 'fcc'}.get(tally['components_total'])
+        if kind_all is not None:
+            shifts = lattice_shifts(kind_all, p.cell_centered)
+            shifts = [shifts[tally['components_tally'] % len(shifts)]]
+    n_particles = component.N//len(lattice_shifts(kind))
+    gridsize = round(n_particles**(1/3))
+    if gridsize % 2:
+        raise ConceptGPUError(f'{component.name}: a lattice of {gridsize}³ particles: the '
+                              'realisation grid must be even')
+    if component.mass == -1:
+        component.mass = component.ϱ_bar*p.boxsize**3/component.N
+    amplitudes_dev = {0: _amplitudes_dev(component, amplitudes, gridsize)}
+    if not backscale:
+        amplitudes_dev[1] = _amplitudes_dev(component, amplitudes_θ, gridsize)
+    watch = _Stopwatch(timings)
+    # Φ⁽¹⁾ and one temporary grid; 2LPT: Φ⁽²⁾ and a second temporary grid (ic.py:1304-1312)
+    from .mesh import get_mesh
+    def grid(role):
+        return get_mesh(gridsize, p.boxsize, p.nghosts, p.cell_centered, role=role,
+                        device=component.device)
+    Φ1, tmp0 = grid('lpt Φ1'), grid('lpt tmp0')
+    Φ2, tmp1 = (grid('lpt Φ2'), grid('lpt tmp1')) if lpt >= 2 else (None, tmp0)
+    with _host_timer(timings, 'noise (host)'):
+        noise = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
+                                          p.primordial_phase_shift, p)
+    mass = a**(-3*component.w_eff(a=a))*component.mass  # ic.py:2267
+    H = cosmology.hubble(a)
+    pos, mom = component.pos, component.mom
+    index_bgn, id_bgn = 0, tally['particles_tally']
+
+    def displace(Φ, tmp, pos_factor, mom_factor):
+        """Ψᵢ = ∂ᵢΦ to real space (diff_ifft, ic.py:2093-2103), then displace_particles twice"""
+        for dim in range(3):
+            with watch('k-space'):
+                tmp.lpt_diff(Φ, dim)
+            with watch('transforms'):
+                tmp.poisson_backward()
+            with watch('particles'):
+                tmp.lpt_displace(pos if pos_factor else None, mom if mom_factor else None, dim,
+                                 pos_factor, mom_factor, index_bgn)
+
+    for shift in shifts:
+        with watch('particles'):
+            preinitialize_particles(component, n_particles, index_bgn, id_bgn, shift)
+        # 1LPT (carryout_1lpt, ic.py:1447-1509): ∇²Φ⁽¹⁾ = -δ; first θ, then δ
+        velocity_factor = a*H*growth_factors['f1']
+        uploaded = False
+        for variable in range(1 - backscale, -1, -1):
+            if not uploaded or tmp1 is tmp0:
+                with watch('upload'):
+                    tmp0.upload_fourier(noise)
+                uploaded = True
+            with watch('k-space'):
+                Φ1.lpt_potential(tmp0, amplitudes_dev[variable], shift, factor=2*variable - 1)
+            if backscale:
+                displace(Φ1, tmp1, 1.0, velocity_factor*(a*mass))
+            elif variable == 0:
+                displace(Φ1, tmp1, 1.0, 0.0)
+            else:
+                displace(Φ1, tmp1, 0.0, 1*(a*mass))
+        if lpt >= 2:
+            # 2LPT (carryout_2lpt, ic.py:1539-1589):
+            #   ∇²Φ⁽²⁾ = D⁽²⁾/(D⁽¹⁾)² (-Φ,₀₀Φ,₁₁ - Φ,₁₁Φ,₂₂ - Φ,₂₂Φ,₀₀ + Φ,₀₁² + Φ,₁₂² + Φ,₂₀²)
+            # with a derivative grid kept where the next term needs it, as the reference's
+            # notes do: seven inverse transforms for the six terms
+            potential_factor = (float(gridsize)**(-3)*growth_factors['D2']
+                                / growth_factors['D1']**2)
+            velocity_factor = a*H*growth_factors['f2']
+
+            def derivative(tmp, i, j):
+                with watch('k-space'):
+                    tmp.lpt_diff(Φ1, i, j)
+                with watch('transforms'):
+                    tmp.poisson_backward()
+
+            def term(operation, x, y, factor=1.0):
+                with watch('products'):
+                    Φ2.lpt_product(x, y, operation, factor)
+            derivative(tmp0, 0, 0)
+            derivative(tmp1, 1, 1)
+            term('=', tmp0, tmp1, -1.0)
+            derivative(tmp0, 2, 2)
+            term('-=', tmp1, tmp0)
+            derivative(tmp1, 0, 0)
+            term('-=', tmp0, tmp1)
+            for i, j in ((0, 1), (1, 2), (0, 2)):
+                derivative(tmp0, i, j)
+                term('+=', tmp0, tmp0)
+            with watch('transforms'):
+                Φ2.fft_forward()
+            with watch('k-space'):
+                Φ2.lpt_potential(Φ2, None, factor=potential_factor)
+            displace(Φ2, tmp0, 1.0, velocity_factor*(a*mass))
+        id_bgn += n_particles
+        index_bgn += n_particles
+    tally['particles_tally'] = id_bgn
+    tally['components_tally'] += 1
+    if id_bgn != component.N:
+        component.use_ids = True  # not the running row numbers of this component
+    with watch('particles'):
+        wrap_positions(pos, p.boxsize)  # ic.py:1396-1398
+    # the rows are new particles to everything that keeps state about them
+    component.tile_mesh = None
+    component.tiles_exact = False
+    component._store.touch_mom()
+    watch.finish()
+    return {'Φ1': Φ1, 'Φ2': Φ2, 'gridsize': gridsize}
+
+
+def _amplitudes_dev(component, amplitudes, gridsize):
+    amplitudes = np.ascontiguousarray(np.asarray(amplitudes, dtype=np.float64))
+    k2_max = 3*(gridsize//2 - 1)**2
+    if amplitudes.shape != (k2_max + 1,):
+        raise ConceptGPUError(
+            f'{component.name}: {amplitudes.shape} amplitudes for a lattice of {gridsize}³ '
+            f'particles, which needs 3*(nyquist - 1)**2 + 1 = {k2_max + 1}')
+    return torch.from_numpy(amplitudes).to(component.device)
+
+
+@contextlib.contextmanager
+def _host_timer(timings, kind):
+    import time
+    t0 = time.perf_counter()
+    yield
+    if timings is not None:
+        timings[kind] = timings.get(kind, 0.0) + (time.perf_counter() - t0)*1e3

@@ -158,6 +158,10 @@ SYMBOLS = {
     'cg_fluid_vmax': (_int, [_vp, _vp, _vp, _vp, _i64, _dbl, _vp]),
     'cg_fluid_pressure_sources': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl,
                                          _dbl]),
+    'cg_lpt_potential': (_int, [_vp, _vp, _vp, _i64, _vp, _dbl]),
+    'cg_lpt_diff': (_int, [_vp, _vp, _int, _int, _dbl]),
+    'cg_lpt_product': (_int, [_vp, _vp, _vp, _int, _dbl]),
+    'cg_lpt_displace': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _dbl, _dbl]),
     'cg_fluid_kt_step': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _dbl, _dbl,
                                 _dbl, _dbl, _dbl, _dbl, _dbl]),
 }

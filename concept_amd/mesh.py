@@ -504,6 +504,66 @@ class PotentialMesh:
         return out
 
     # -- 2D render (graphics.py:1374-1755; csrc/cg_render.hip) -------------------------
+    # -- initial conditions (ic.py:1199-1589, 2038-2280; csrc/cg_lpt.hip) ------------------
+    def upload_fourier(self, slab):
+        """A host Fourier slab in the reference's transposed layout double[j][i][N+2] (what
+        fetch_fourier returns) becomes this mesh's Fourier content (one domain)."""
+        N = self.gridsize
+        if self.dist:
+            raise lib.ConceptGPUError('upload_fourier(): single-domain upload')
+        slab = np.asarray(slab, dtype=np.float64)
+        if slab.shape != (N, N, N + 2):
+            raise lib.ConceptGPUError(
+                f'upload_fourier(): slab of shape {slab.shape} for grid size {N}')
+        rows = self.layer_doubles//self.pad
+        native = np.zeros((N, rows, self.pad), dtype=np.float64)
+        native[:, :N, :N + 2] = slab.transpose(1, 0, 2)
+        self.layers_write(0, N, torch.from_numpy(native).to(self.device))
+        return self
+
+    def lpt_potential(self, noise, amplitudes=None, shift=(0.0, 0.0, 0.0), factor=1.0):
+        """realize_grid (scalar case, ic.py:711-764) + laplacian_inverse (mesh.py:3422-3437) of
+        the Fourier content of `noise` into this mesh; amplitudes: float64 tensor of
+        3*(nyquist - 1)**2 + 1 entries on the device, or None for laplacian_inverse alone."""
+        k2_max = 0
+        if amplitudes is not None:
+            if (amplitudes.dtype != torch.float64 or amplitudes.device != self.device
+                    or not amplitudes.is_contiguous() or amplitudes.dim() != 1):
+                raise lib.ConceptGPUError(
+                    f'lpt_potential(): amplitudes must be a contiguous 1D float64 tensor on '
+                    f'{self.device}')
+            k2_max = amplitudes.numel() - 1
+        sh = (ctypes.c_double*3)(*[float(x) for x in shift])
+        check(_L.cg_lpt_potential(self._ctx, noise._ctx, _ptr(amplitudes), k2_max, sh,
+                                  float(factor)))
+        return self
+
+    def lpt_diff(self, source, dim0, dim1=-1, factor=1.0):
+        """fourier_diff (mesh.py:3466-3510) of `source` into this mesh"""
+        check(_L.cg_lpt_diff(self._ctx, source._ctx, int(dim0), int(dim1), float(factor)))
+        return self
+
+    def lpt_product(self, a, b, operation='=', factor=1.0):
+        """this mesh (= | += | -=) factor*a*b in real space (handle_lpt_term, ic.py:2020-2057)"""
+        check(_L.cg_lpt_product(self._ctx, a._ctx, b._ctx, ('=', '+=', '-=').index(operation),
+                                float(factor)))
+        return self
+
+    def lpt_displace(self, pos, mom, dim, pos_factor, mom_factor, index_bgn=0):
+        """displace_particles (ic.py:2249-2280) from this mesh's real-space content: the
+        gridsize**3 rows of pos / mom from index_bgn on, row (i*g + j)*g + k from cell (i, j, k).
+        pos or mom may be None where its factor is 0."""
+        n = self.gridsize**3
+        for t in (pos, mom):
+            if t is None:
+                continue
+            self._check_particles(t)
+            if t.shape[0] < index_bgn + n:
+                raise lib.ConceptGPUError(
+                    f'lpt_displace(): {t.shape[0]} rows, {index_bgn} + {n} needed')
+        check(_L.cg_lpt_displace(self._ctx, _ptr(pos), _ptr(mom), n, int(index_bgn), int(dim),
+                                 float(pos_factor), float(mom_factor)))
+
     def render2D_project(self, axis, plane_bgn, plane_end, frac_bgn, frac_end, factor, out=None):
         """project_render2D (graphics.py:1374-1532) of this mesh's real-space values: the N x N
         image, in its final orientation, of this domain's part of the planes

@@ -834,6 +834,35 @@ int cg_fluid_vacuum_apply(cg_ctx *ctx, void *const *var /*HOST 4*/,
 int cg_fluid_vmax(cg_ctx *ctx, const double *rho /*DEV n*/, const double *P /*DEV n*/,
                   const void *const *J /*HOST 3*/, int64_t n, double inv_c2, double *out /*DEV 1*/);
 
+/* --- initial conditions: 1LPT / 2LPT particle realisation (ic.py:1199-1589, 2038-2280) ----
+ * The k-space entries work on the contexts' current Fourier views, the real-space ones on the
+ * owned layers of their meshes; meshes named together have one grid size and one domain.
+ * cg_lpt_potential: realize_grid (scalar case, ic.py:711-764) fused with laplacian_inverse
+ *   (mesh.py:3422-3437) in one pass: every mode of fourier_loop(skip_origin=True) becomes
+ *   dst = (amplitudes[k2] * noise_src rotated by theta) * ((-factor/k_fundamental**2)/k2),
+ *   k2 = ki^2 + kj^2 + kk^2; theta is fourier_loop's (mesh.py:2873-2888) for the NEGATED shift
+ *   (the lattice shift is the particles', ic.py:692-695); the origin and the three Nyquist planes
+ *   are written as 0.  amplitudes: DEV double[k2_max + 1], k2_max = 3*(N/2 - 1)^2 (get_amplitudes,
+ *   ic.py:599-627); NULL: the modes are taken as they are, which is laplacian_inverse alone (dst
+ *   may then be noise_src: in place).  shift: HOST double[3] in grid units, or NULL.
+ * cg_lpt_diff: fourier_diff (mesh.py:3466-3510) of src into dst: i*k_dim0 (dim1 = -1) or
+ *   -k_dim0*k_dim1 times factor times the mode; origin and Nyquist planes 0.
+ * cg_lpt_product: the product of two real-space grids and its move to the output grid in
+ *   handle_lpt_term (ic.py:2020-2057): out (op 0 '=', 1 '+=', 2 '-=') factor*(a*b) cell by cell,
+ *   the multiplication by factor left out when it is 1.  Row padding is neither read nor
+ *   written.  a, b and out may be one another.
+ * cg_lpt_displace: displace_particles (ic.py:2249-2280) on one domain: particle
+ *   p = (i*N + j)*N + k of the n = N^3 rows from index_bgn on reads cell (i, j, k) of psi's
+ *   real-space mesh once; pos[3p+dim] += pos_factor*psi and mom[3p+dim] += mom_factor*psi, product
+ *   and sum rounded separately.  A factor of 0 skips that array (which may then be NULL).
+ *   n = 0: nothing is done. */
+int cg_lpt_potential(cg_ctx *dst, cg_ctx *noise_src, const double *amplitudes /*DEV or NULL*/,
+                     int64_t k2_max, const double *shift /*HOST 3 or NULL*/, double factor);
+int cg_lpt_diff(cg_ctx *dst, cg_ctx *src, int dim0, int dim1, double factor);
+int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double factor);
+int cg_lpt_displace(cg_ctx *psi, double *pos /*DEV or NULL*/, double *mom /*DEV or NULL*/,
+                    int64_t n, int64_t index_bgn, int dim, double pos_factor, double mom_factor);
+
 /* --- debug fetch (parity tests) -------------------------------------------- */
 int cg_fetch(cg_ctx *ctx, int which, double *out /*HOST*/, int64_t n_doubles);
 /* CIC cell indices exactly as set_weights_CIC returns them for the deposit
