@@ -157,6 +157,18 @@ CASES = {
                         diff=2, pp=True, ewald_gridsize=6),
     'ppnonperiodic_n4': dict(method='ppnonperiodic', n=4, gridsize=8, boxsize=20.0, seed=32,
                              dist='clustered', diff=2, pp=True, ewald_gridsize=6),
+    # ... with the other softening kernels (get_softened_r3inv, interactions.py:1847-1914) on a
+    # table of size 4, and with the particles spread by hand over rungs 0..3 of N_rungs = 4,
+    # some flagged to jump (rung + N_rungs, rung + 2 N_rungs), rung 0 inactive
+    'pp_none_n4': dict(method='pp', n=4, gridsize=8, boxsize=20.0, seed=61, dist='uniform',
+                       diff=2, pp=True, ewald_gridsize=4, softening_kernel='none'),
+    'pp_plummer_n4': dict(method='pp', n=4, gridsize=8, boxsize=20.0, seed=62, dist='clustered',
+                          diff=2, pp=True, ewald_gridsize=4, softening_kernel='plummer'),
+    'ppnonperiodic_plummer_n4': dict(method='ppnonperiodic', n=4, gridsize=8, boxsize=20.0,
+                                     seed=63, dist='clustered', diff=2, pp=True,
+                                     ewald_gridsize=4, softening_kernel='plummer'),
+    'pp_rungs_n4': dict(method='pp', n=4, gridsize=8, boxsize=20.0, seed=64, dist='clustered',
+                        diff=2, pp=True, ewald_gridsize=4, pp_rungs=4),
     # GADGET-2 snapshots (snapshot.py:640-2640) written by the
     # reference (the binary file is the fixture) and read back by it (expected arrays)
     'gadget_sf2_32': dict(method='pm', n=4, gridsize=8, boxsize=64.0, seed=41, dist='uniform',
@@ -689,6 +701,10 @@ select_forces = {{'matter': {{'gravity': '{method}'}}}}
 select_softening_length = {{'matter': '0.03*boxsize/cbrt(N)'}}
 ewald_gridsize = {cfg['ewald_gridsize']}
 """
+    if 'softening_kernel' in cfg:
+        text += f"softening_kernel = {cfg['softening_kernel']!r}\n"
+    if 'pp_rungs' in cfg:
+        text += f"N_rungs = {cfg['pp_rungs']}\n"
     ref = load_reference(text, f'/tmp/concept_golden_work/{name}')
     commons, interactions, species = ref.commons, ref.interactions, ref.species
     import importlib
@@ -712,10 +728,26 @@ ewald_gridsize = {cfg['ewald_gridsize']}
         # ewald.tabulate() with filename '' (h5py is absent: the grid is not cached on disk)
         ewald.grid = ref.mesh.tabulate_vectorgrid(
             commons.ewald_gridsize, ewald.summation, 0.5/(commons.ewald_gridsize - 1), '')
+    out['softening_kernel'] = str(commons.softening_kernel)
     comp.nullify_Δ('mom')
     comp.lowest_active_rung = 0
     comp.lowest_populated_rung = 0
     comp.highest_populated_rung = 0
+    if 'pp_rungs' in cfg:
+        # rungs 0..3 by hand; of the active ones (rung >= 1) a third each keeps its rung, is
+        # flagged upwards (rung + N_rungs) and downwards (rung + 2 N_rungs, below 3 N_rungs - 1)
+        assert comp.use_rungs and nr == cfg['pp_rungs']
+        rung = (np.arange(N)*7 % nr).astype(np.int8)
+        jump = np.arange(N)//nr % 3
+        jump[(rung + nr*jump >= 3*nr - 1) | (rung == 0)] = 0
+        jumped = (rung + nr*jump).astype(np.int8)
+        comp.rung_indices_mv[:N] = rung
+        comp.rung_indices_jumped_mv[:N] = jumped
+        comp.set_rungs_N()                       # and the populated bounds with it
+        comp.lowest_active_rung = 1
+        assert (comp.lowest_populated_rung, comp.highest_populated_rung) == (0, nr - 1)
+        assert len(set(sdt_rungs[key2])) == 3*nr - 1
+        out.update(rung_indices=rung, rung_indices_jumped=jumped, lowest_active_rung=1)
     interactions.gravity(method, [comp], [comp], sdt_rungs, 'any', False)
     out['dmom'] = np.array(comp.Δmom_mv3[:N]).copy()
     out['pos_after'] = np.array(comp.pos_mv3[:N]).copy()
