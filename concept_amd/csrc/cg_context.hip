@@ -495,7 +495,7 @@ extern "C" int cg_deposit_cic(cg_ctx *c, const double *pos, int64_t n, double co
     CG_CHECK(c && (pos || n == 0), "cg_deposit_cic: null argument");
     CG_CHECK(n >= 0, "cg_deposit_cic: negative particle count");
     if (n == 0) return 0;
-    return cgk_deposit_cic(c, pos, n, contribution);
+    return cgk_deposit_general(c, pos, n, contribution, 2, c->geom_deposit);
 }
 
 // ---- general particle_mesh() pieces (cg_general.hip) ----

@@ -12,6 +12,7 @@
 // mesh is double[N][N][pad] / complex[N][N][pad/2], un-transposed: the first
 // index is x (the reference's ki), the second y (kj).
 // Compiled with -ffp-contract=off; every expression keeps the reference's order.
+#include "cg_chunk_box.h"
 #include "cg_internal.h"
 
 // Fluid grids of an x-slab domain are its own layers double[nxl][N][N]; `mesh` is then the
@@ -224,39 +225,6 @@ __global__ __launch_bounds__(64) void k_cm_unpack(const double2 *__restrict__ in
     }
 }
 
-// diff_domaingrid (mesh.py:4874-5030): the value of one force cell from the potential along
-// one dimension, P(s) = the potential s cells away.  Coefficients and the order of the terms
-// are the reference's; order 1 is its one-sided 'forward' difference.
-struct FdCoef {
-    double c1, c2, c3, c4;
-};
-template <int ORDER, class P>
-__device__ __forceinline__ double fd_value(const P &phi, const FdCoef &c) {
-#pragma clang fp contract(off)
-    if (ORDER == 0) return phi(0);  // the mesh already holds the force (Fourier-space gradient)
-    if (ORDER == 1) return c.c1 * (phi(1) - phi(0));                                // mesh.py:4962
-    if (ORDER == 2) return c.c1 * (phi(1) - phi(-1));                               // mesh.py:4967
-    if (ORDER == 4) return c.c1 * (phi(1) - phi(-1)) - c.c2 * (phi(2) - phi(-2));   // mesh.py:4973
-    if (ORDER == 6)                                                                  // mesh.py:4984
-        return (c.c1 * (phi(1) - phi(-1)) - c.c2 * (phi(2) - phi(-2))) + c.c3 * (phi(3) - phi(-3));
-    return ((c.c1 * (phi(1) - phi(-1)) - c.c2 * (phi(2) - phi(-2))) +                // mesh.py:4999
-            c.c3 * (phi(3) - phi(-3))) - c.c4 * (phi(4) - phi(-4));
-}
-static bool fd_coefficients(int order, double dx, FdCoef &c) {
-    c = FdCoef{0, 0, 0, 0};
-    switch (order) {
-        case 0: return true;
-        case 1: c.c1 = 1 / dx; return true;
-        case 2: c.c1 = (1.0 / 2) / dx; return true;
-        case 4: c.c1 = (2.0 / 3) / dx; c.c2 = (1.0 / 12) / dx; return true;
-        case 6: c.c1 = (3.0 / 4) / dx; c.c2 = (3.0 / 20) / dx; c.c3 = (1.0 / 60) / dx; return true;
-        case 8:
-            c.c1 = (4.0 / 5) / dx; c.c2 = (1.0 / 5) / dx; c.c3 = (4.0 / 105) / dx;
-            c.c4 = (1.0 / 280) / dx;
-            return true;
-    }
-    return false;
-}
 #define CG_FD_SWITCH(order, KERNEL, ...)                                          \
     switch (order) {                                                              \
         case 0: hipLaunchKernelGGL(KERNEL<0>, __VA_ARGS__); break;                \
@@ -285,8 +253,8 @@ __global__ __launch_bounds__(256) void k_fluid_kick(double *__restrict__ J,
         auto phi = [&](int s) {
             i64 ii = cg_xlayer(xm, xm.x0 + i + (dim == 0 ? s : 0), N);
             int jj = j, kk = k;
-            if (dim == 1) jj = (j + s + N) % N;
-            else if (dim == 2) kk = (k + s + N) % N;
+            if (dim == 1) jj = wrap(j + s, N);
+            else if (dim == 2) kk = wrap(k + s, N);
             return mesh[(ii * ny + jj) * pad + kk];
         };
         const double g = fd_value<ORDER>(phi, fc);
@@ -296,253 +264,92 @@ __global__ __launch_bounds__(256) void k_fluid_kick(double *__restrict__ J,
 }
 
 // ---------------------------------------------------------------------------
-// Particle interpolation of every order: set_weights_NGP / CIC /
-// TSC / PCS (mesh.py:5305-5394) and the loops over ORDER^3 grid points
-// (mesh.py:5052-5283), with the coordinate map of interpolate_particles
-// (mesh.py:1577-1606, lattice shift subtracted) or interpolate_domaingrid_to_particles
-// (mesh.py:409-432, lattice shift added) in `geo`.  Direct form: one lane per particle,
-// device-scope FP64 atomics for the deposit (these orders are accuracy options, not the
-// benchmarked path; the tiled CIC kernels keep the default configuration).
+// Particle interpolation of every order: deposit and scalar gather with
+// the weights of set_weights_NGP / CIC / TSC / PCS and the loops over ORDER^3 grid points
+// (mesh.py:5052-5283), with the coordinate map of interpolate_particles (mesh.py:1512-1636,
+// lattice shift subtracted) or interpolate_domaingrid_to_particles (mesh.py:376-459, lattice
+// shift added) in `geo`.  Particles in any memory order, through the chunk boxes of
+// cg_chunk_box.h (the scheme and its measurements are described there); cg_deposit_cic is the
+// order-2 deposit.  The tiled CIC kernels keep the default configuration's tile-sorted path.
 // ---------------------------------------------------------------------------
 template <int ORDER>
-__device__ __forceinline__ int set_weights(double x, double (&w)[4]) {
+__global__ __launch_bounds__(kChunkLanes) void k_deposit_general(const double *__restrict__ pos,
+                                                                 i64 n, double *__restrict__ mesh,
+                                                                 int N, i64 ny, i64 pad, int g,
+                                                                 XMap xm, CicGeom geo,
+                                                                 double contribution) {
 #pragma clang fp contract(off)
-    if (ORDER == 1) {
-        int index = (int)(x + 0.5);
-        w[0] = 1;
-        return index;
-    }
-    if (ORDER == 2) {
-        int index = (int)x;
-        double dist = x - (double)index;
-        w[0] = 1 - dist;
-        w[1] = dist;
-        return index;
-    }
-    if (ORDER == 3) {
-        int index = (int)(x + 0.5);
-        double dist = x - (double)index;
-        index -= 1;
-        double dist2 = dist * dist;
-        double weight0 = 0.125 + 0.5 * (dist2 - dist);
-        double weight1 = 0.75 - dist2;
-        w[0] = weight0;
-        w[1] = weight1;
-        w[2] = 1 - weight0 - weight1;
-        return index;
-    }
-    int index = (int)x;
-    index -= 1;
-    double dist = x - (double)index;
-    double tmp = 2 - dist;
-    double tmp2 = tmp * tmp;
-    double tmp3 = tmp * tmp2;
-    double weight0 = 1. / 6. * tmp3;
-    double weight2 = 2. / 3. - tmp2 + 0.5 * tmp3;
-    double d1 = dist - 1;
-    double weight3 = 1. / 6. * (d1 * d1 * d1);
-    w[0] = weight0;
-    w[1] = 1 - weight0 - weight2 - weight3;
-    w[2] = weight2;
-    w[3] = weight3;
-    return index;
-}
-__device__ __forceinline__ int wrap32(int a, int n) {
-    a = a < 0 ? a + n : a;
-    return a >= n ? a - n : a;
-}
-
-// ---------------------------------------------------------------------------
-// Deposit and scalar gather of order 1-4 with lattice shifts (mesh.py:1512-1636, :376-459),
-// round 5: through LDS boxes, like cg_deposit_cic / cg_gather_kick (cg_mesh_kernels.hip).  A
-// workgroup takes 2048 consecutive particles, finds the box of their stencils' first cells
-// relative to the first particle's (the periodic seam is no seam) and, when the box with the
-// stencil's width fits 4096 cells of LDS, accumulates there and adds the box to the mesh once — one
-// device-scope FP64 atomic (memory-side on MI355X) per touched cell instead of ORDER^3 per
-// particle — or copies the box of the field in before the gather.  Particles in tile order of
-// ANY mesh are compact enough; a chunk that is spread out takes the direct accesses.  Index and
-// weight arithmetic unchanged (the reference's expressions, set_weights above).
-// ---------------------------------------------------------------------------
-constexpr int kGcPer = 4, kGcLanes = 512, kGcCells = 4096;
-
-// the box of a chunk: s_ref = first particle's first cell, s_lo / s_hi = extremes of the others'
-// first cells relative to it (in [-N/2, N/2) through the seam); called by all lanes
-template <int ORDER>
-struct GcBox {
-    int r[3], l[3], e[3];
-    bool fits;
-};
-__device__ __forceinline__ int gc_rel(int cell, int ref, int N) {
-    int d = cell - ref;
-    d += d < -(N / 2) ? N : 0;
-    d -= d >= N - N / 2 ? N : 0;
-    return d;
-}
-template <int ORDER>
-__device__ __forceinline__ GcBox<ORDER> gc_box(const int (&cell)[kGcPer][3],
-                                               const bool (&valid)[kGcPer], int N, int *s_ref,
-                                               int *s_lo, int *s_hi) {
-    const int tid = threadIdx.x;
-    if (tid == 0) {  // (the chunk's first particle exists)
-        for (int d = 0; d < 3; d++) {
-            s_ref[d] = cell[0][d];
-            s_lo[d] = 0;
-            s_hi[d] = 0;
-        }
-    }
-    __syncthreads();
-    GcBox<ORDER> B;
-    for (int d = 0; d < 3; d++) B.r[d] = s_ref[d];
-    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < kGcPer; u++) {
-        if (!valid[u]) continue;
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            const int v = gc_rel(cell[u][d], B.r[d], N);
-            lo[d] = min(lo[d], v);
-            hi[d] = max(hi[d], v);
-        }
-    }
-#pragma unroll
-    for (int d = 0; d < 3; d++) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            lo[d] = min(lo[d], __shfl_xor(lo[d], m));
-            hi[d] = max(hi[d], __shfl_xor(hi[d], m));
-        }
-        if ((tid & 63) == 0) {
-            atomicMin(&s_lo[d], lo[d]);
-            atomicMax(&s_hi[d], hi[d]);
-        }
-    }
-    __syncthreads();
-    for (int d = 0; d < 3; d++) {
-        B.l[d] = s_lo[d];
-        B.e[d] = s_hi[d] - s_lo[d] + ORDER;
-    }
-    B.fits = (i64)B.e[0] * B.e[1] * B.e[2] <= kGcCells && B.e[0] <= N && B.e[1] <= N && B.e[2] <= N;
-    return B;
-}
-
-template <int ORDER>
-__global__ __launch_bounds__(kGcLanes) void k_deposit_general(const double *__restrict__ pos, i64 n,
-                                                              double *__restrict__ mesh, int N,
-                                                              i64 ny, i64 pad, int g, XMap xm,
-                                                              CicGeom geo, double contribution) {
-#pragma clang fp contract(off)
-    __shared__ double blk[kGcCells];
-    __shared__ int s_ref[3], s_lo[3], s_hi[3];
-    const int tid = threadIdx.x;
-    const i64 base = (i64)blockIdx.x * (kGcLanes * kGcPer);
-    double px[kGcPer][3];
-    int cell[kGcPer][3];
-    bool valid[kGcPer];
-#pragma unroll
-    for (int u = 0; u < kGcPer; u++) {
-        const i64 p = base + tid + (i64)kGcLanes * u;
-        valid[u] = p < n;
-        double w[4];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            px[u][d] = valid[u] ? pos[3 * p + d] : 0.0;
-            cell[u][d] = wrap32(set_weights<ORDER>((px[u][d] - geo.off[d]) * geo.scale, w) - g, N);
-        }
-    }
-    const GcBox<ORDER> B = gc_box<ORDER>(cell, valid, N, s_ref, s_lo, s_hi);
-    const int ncells = B.fits ? B.e[0] * B.e[1] * B.e[2] : 0;
-    for (int i = tid; i < ncells; i += kGcLanes) blk[i] = 0;
-    __syncthreads();
+    __shared__ double blk[kChunkCells];
+    double x[kChunkPer][3];
+    int cell[kChunkPer][3];
+    chunk_load<ORDER>(pos, n, geo, g, N, x, cell);
+    const ChunkBox<ORDER> B = chunk_box<ORDER>(cell, n, N);
+    chunk_zero(B, blk);
 #pragma unroll 1
-    for (int u = 0; u < kGcPer; u++) {
-        if (!valid[u]) continue;
+    for (int u = 0; u < kChunkPer; u++) {
+        if (chunk_particle(u) >= n) continue;
         double wx[4], wy[4], wz[4];
-        const int ii = set_weights<ORDER>((px[u][0] - geo.off[0]) * geo.scale, wx) - g;
-        const int jj = set_weights<ORDER>((px[u][1] - geo.off[1]) * geo.scale, wy) - g;
-        const int kk = set_weights<ORDER>((px[u][2] - geo.off[2]) * geo.scale, wz) - g;
-        const int a0 = gc_rel(cell[u][0], B.r[0], N) - B.l[0],
-                  b0 = gc_rel(cell[u][1], B.r[1], N) - B.l[1],
-                  c0 = gc_rel(cell[u][2], B.r[2], N) - B.l[2];
+        const int ii = set_weights<ORDER>((x[u][0] - geo.off[0]) * geo.scale, wx) - g;
+        const int jj = set_weights<ORDER>((x[u][1] - geo.off[1]) * geo.scale, wy) - g;
+        const int kk = set_weights<ORDER>((x[u][2] - geo.off[2]) * geo.scale, wz) - g;
+        // the ORDER^3 terms, each added at(i, j, k): to the box in LDS or to the mesh
+        auto deposit = [&](auto at) {
 #pragma unroll
-        for (int i = 0; i < ORDER; i++) {
-            double weight_i = wx[i];
-            weight_i *= contribution;  // apply_factor = True
-            const i64 ri = B.fits ? 0 : cg_xlayer(xm, (i64)(ii + i), N) * ny;
+            for (int i = 0; i < ORDER; i++) {
+                double weight_i = wx[i];
+                weight_i *= contribution;  // apply_factor = True
 #pragma unroll
-            for (int j = 0; j < ORDER; j++) {
-                const double wij = weight_i * wy[j];
-                double *row = B.fits ? blk + ((a0 + i) * B.e[1] + (b0 + j)) * B.e[2] + c0
-                                     : mesh + (ri + wrap32(jj + j, N)) * pad;
+                for (int j = 0; j < ORDER; j++) {
+                    const double wij = weight_i * wy[j];
 #pragma unroll
-                for (int k = 0; k < ORDER; k++)
-                    unsafeAtomicAdd(row + (B.fits ? k : wrap32(kk + k, N)),
-                                    ORDER == 1 ? weight_i : wij * wz[k]);
+                    for (int k = 0; k < ORDER; k++)
+                        unsafeAtomicAdd(at(i, j, k), ORDER == 1 ? weight_i : wij * wz[k]);
+                }
             }
-        }
+        };
+        // Up to CIC the two are separate branches (ds_add_f64 and global atomics); TSC and PCS
+        // choose per address (flat atomics).  Measured, 2^27 tile-sorted particles at 256^3:
+        // CIC 1.31 ms per address, 1.22 in branches; PCS 8.06 ms per address, 8.35 in branches.
+        double *q = blk + B.entry_of(cell[u], N);
+        auto on_mesh = [&](int i, int j, int k) {
+            return mesh + (cg_xlayer(xm, (i64)(ii + i), N) * ny + wrap(jj + j, N)) * pad +
+                   wrap(kk + k, N);
+        };
+        auto in_box = [&](int i, int j, int k) { return q + (i * B.e[1] + j) * B.e[2] + k; };
+        if (ORDER <= 2 && B.fits) deposit(in_box);
+        else if (ORDER <= 2) deposit(on_mesh);
+        else
+            deposit([&](int i, int j, int k) {
+                return B.fits ? in_box(i, j, k) : on_mesh(i, j, k);
+            });
     }
-    if (!B.fits) return;  // (uniform)
-    __syncthreads();
-    for (int i = tid; i < ncells; i += kGcLanes) {
-        const double v = blk[i];
-        if (v == 0) continue;
-        const int c = i % B.e[2], b = (i / B.e[2]) % B.e[1], a = i / (B.e[2] * B.e[1]);
-        // (cell index before the wrap in [-N, 2N): |rel| <= N/2, extent <= N)
-        const i64 gi = cg_xlayer(xm, (i64)wrap32(wrap32(B.r[0] + B.l[0], N) + a, N), N);
-        const int gj = wrap32(wrap32(B.r[1] + B.l[1], N) + b, N),
-                  gk = wrap32(wrap32(B.r[2] + B.l[2], N) + c, N);
-        unsafeAtomicAdd(mesh + (gi * ny + gj) * pad + gk, v);
-    }
+    chunk_flush(B, blk, mesh, N, ny, pad, xm);
 }
 
 template <int ORDER>
-__global__ __launch_bounds__(kGcLanes) void k_gather_scalar(const double *__restrict__ pos,
-                                                            double *__restrict__ mom, i64 n,
-                                                            int dim,
-                                                            const double *__restrict__ mesh, int N,
-                                                            i64 ny, i64 pad, int g, XMap xm,
-                                                            CicGeom geo, double factor) {
+__global__ __launch_bounds__(kChunkLanes) void k_gather_scalar(const double *__restrict__ pos,
+                                                               double *__restrict__ mom, i64 n,
+                                                               int dim,
+                                                               const double *__restrict__ mesh,
+                                                               int N, i64 ny, i64 pad, int g,
+                                                               XMap xm, CicGeom geo,
+                                                               double factor) {
 #pragma clang fp contract(off)
-    __shared__ double blk[kGcCells];
-    __shared__ int s_ref[3], s_lo[3], s_hi[3];
-    const int tid = threadIdx.x;
-    const i64 base = (i64)blockIdx.x * (kGcLanes * kGcPer);
-    double px[kGcPer][3];
-    int cell[kGcPer][3];
-    bool valid[kGcPer];
-#pragma unroll
-    for (int u = 0; u < kGcPer; u++) {
-        const i64 p = base + tid + (i64)kGcLanes * u;
-        valid[u] = p < n;
-        double w[4];
-#pragma unroll
-        for (int d = 0; d < 3; d++) {
-            px[u][d] = valid[u] ? pos[3 * p + d] : 0.0;
-            cell[u][d] = wrap32(set_weights<ORDER>((px[u][d] - geo.off[d]) * geo.scale, w) - g, N);
-        }
-    }
-    const GcBox<ORDER> B = gc_box<ORDER>(cell, valid, N, s_ref, s_lo, s_hi);
-    if (B.fits) {
-        const int ncells = B.e[0] * B.e[1] * B.e[2];
-        for (int i = tid; i < ncells; i += kGcLanes) {
-            const int c = i % B.e[2], b = (i / B.e[2]) % B.e[1], a = i / (B.e[2] * B.e[1]);
-            const i64 gi = cg_xlayer(xm, (i64)wrap32(wrap32(B.r[0] + B.l[0], N) + a, N), N);
-            const int gj = wrap32(wrap32(B.r[1] + B.l[1], N) + b, N),
-                      gk = wrap32(wrap32(B.r[2] + B.l[2], N) + c, N);
-            blk[i] = mesh[(gi * ny + gj) * pad + gk];
-        }
-    }
-    __syncthreads();
+    __shared__ double blk[kChunkCells];
+    double x[kChunkPer][3];
+    int cell[kChunkPer][3];
+    chunk_load<ORDER>(pos, n, geo, g, N, x, cell);
+    const ChunkBox<ORDER> B = chunk_box<ORDER>(cell, n, N);
+    chunk_fill(B, blk, mesh, N, ny, pad, xm);
 #pragma unroll 1
-    for (int u = 0; u < kGcPer; u++) {
-        const i64 p = base + tid + (i64)kGcLanes * u;
+    for (int u = 0; u < kChunkPer; u++) {
+        const i64 p = chunk_particle(u);
         if (p >= n) continue;
         double wx[4], wy[4], wz[4];
-        const int ii = set_weights<ORDER>((px[u][0] - geo.off[0]) * geo.scale, wx) - g;
-        const int jj = set_weights<ORDER>((px[u][1] - geo.off[1]) * geo.scale, wy) - g;
-        const int kk = set_weights<ORDER>((px[u][2] - geo.off[2]) * geo.scale, wz) - g;
-        const int a0 = gc_rel(cell[u][0], B.r[0], N) - B.l[0],
-                  b0 = gc_rel(cell[u][1], B.r[1], N) - B.l[1],
-                  c0 = gc_rel(cell[u][2], B.r[2], N) - B.l[2];
+        const int ii = set_weights<ORDER>((x[u][0] - geo.off[0]) * geo.scale, wx) - g;
+        const int jj = set_weights<ORDER>((x[u][1] - geo.off[1]) * geo.scale, wy) - g;
+        const int kk = set_weights<ORDER>((x[u][2] - geo.off[2]) * geo.scale, wz) - g;
+        const double *q = blk + B.entry_of(cell[u], N);
         double value = 0;
 #pragma unroll
         for (int i = 0; i < ORDER; i++) {
@@ -550,11 +357,11 @@ __global__ __launch_bounds__(kGcLanes) void k_gather_scalar(const double *__rest
 #pragma unroll
             for (int j = 0; j < ORDER; j++) {
                 const double wij = wx[i] * wy[j];
-                const double *row = B.fits ? blk + ((a0 + i) * B.e[1] + (b0 + j)) * B.e[2] + c0
-                                           : mesh + (ri + wrap32(jj + j, N)) * pad;
+                const double *row = B.fits ? q + (i * B.e[1] + j) * B.e[2]
+                                           : mesh + (ri + wrap(jj + j, N)) * pad;
 #pragma unroll
                 for (int k = 0; k < ORDER; k++)
-                    value += row[B.fits ? k : wrap32(kk + k, N)] * (ORDER == 1 ? 1.0 : wij * wz[k]);
+                    value += row[B.fits ? k : wrap(kk + k, N)] * (ORDER == 1 ? 1.0 : wij * wz[k]);
             }
         }
         if (factor != 1) value *= factor;  // mesh.py:456-458
@@ -578,8 +385,8 @@ __global__ __launch_bounds__(256) void k_mesh_diff(double *__restrict__ dst,
         auto phi = [&](int s) {
             i64 ii = cg_xlayer(xm, xm.x0 + i + (dim == 0 ? s : 0), N);
             int jj = j, kk = k;
-            if (dim == 1) jj = wrap32(j + s, N);
-            else if (dim == 2) kk = wrap32(k + s, N);
+            if (dim == 1) jj = wrap(j + s, N);
+            else if (dim == 2) kk = wrap(k + s, N);
             return src[(ii * ny + jj) * pad + kk];
         };
         const double gval = fd_value<ORDER>(phi, fc);
@@ -715,10 +522,9 @@ int cgk_fluid_kick(cg_ctx *c, double *J, const double *rho, const double *P, int
 int cgk_deposit_general(cg_ctx *c, const double *pos, i64 n, double contribution, int order,
                         const CicGeom &geo) {
     if (n == 0) return 0;
-    CG_ORDER_SWITCH(order, k_deposit_general,
-                    dim3((unsigned)((n + kGcLanes * kGcPer - 1) / (kGcLanes * kGcPer))),
-                    dim3(kGcLanes), 0, c->stream, pos, n, c->mesh, (int)c->N, c->ny, c->pad,
-                    c->p.nghosts, c->xmap, geo, contribution)
+    CG_ORDER_SWITCH(order, k_deposit_general, dim3(chunk_blocks(n)), dim3(kChunkLanes), 0,
+                    c->stream, pos, n, c->mesh, (int)c->N, c->ny, c->pad, c->p.nghosts, c->xmap,
+                    geo, contribution)
     CG_LAUNCH_CHECK();
     return 0;
 }
@@ -726,10 +532,9 @@ int cgk_deposit_general(cg_ctx *c, const double *pos, i64 n, double contribution
 int cgk_gather_scalar(cg_ctx *c, const double *pos, double *mom, i64 n, int dim, int order,
                       const CicGeom &geo, double factor) {
     if (n == 0) return 0;
-    CG_ORDER_SWITCH(order, k_gather_scalar,
-                    dim3((unsigned)((n + kGcLanes * kGcPer - 1) / (kGcLanes * kGcPer))),
-                    dim3(kGcLanes), 0, c->stream, pos, mom, n, dim, c->mesh, (int)c->N, c->ny,
-                    c->pad, c->p.nghosts, c->xmap, geo, factor)
+    CG_ORDER_SWITCH(order, k_gather_scalar, dim3(chunk_blocks(n)), dim3(kChunkLanes), 0,
+                    c->stream, pos, mom, n, dim, c->mesh, (int)c->N, c->ny, c->pad, c->p.nghosts,
+                    c->xmap, geo, factor)
     CG_LAUNCH_CHECK();
     return 0;
 }

@@ -253,8 +253,7 @@ struct cg_ctx {
     cg_buf<unsigned> err_flags;
 };
 
-// ---- cg_mesh_kernels.hip: CIC deposit and gather, k-space kernel, slab helpers ----
-int cgk_deposit_cic(cg_ctx *c, const double *pos, i64 n, double contribution);
+// ---- cg_mesh_kernels.hip: CIC gather-kick, k-space kernel, slab helpers ----
 int cgk_kspace(cg_ctx *c, int deconv_order, double C, int long_range, double E);
 int cgk_gather_kick(cg_ctx *c, const double *pos, double *mom, i64 n, int diff_order,
                     double factor);

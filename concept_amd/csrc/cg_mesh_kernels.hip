@@ -1,180 +1,13 @@
 // cg_mesh_kernels.hip — hand-written gfx950 kernels of the PM mesh path:
-// CIC deposit (A1/A2), k-space Poisson kernel (A5/A6), CIC gather + finite
-// difference + kick (A9/A10).  FP64 throughout; compiled with
+// k-space Poisson kernel (A5/A6), CIC gather + finite difference + kick
+// (A9/A10) for particles in any order, slab helpers.  (The CIC deposit A1/A2
+// for particles in any order, cg_deposit_cic, is the order-2 instantiation of
+// k_deposit_general in cg_general.hip.)  FP64 throughout; compiled with
 // -ffp-contract=off so every expression is evaluated in the reference's
 // operation order (no FMA contraction).
+#include "cg_chunk_box.h"
 #include "cg_internal.h"
 #include "cg_kspace.h"
-
-// ---------------------------------------------------------------------------
-// CIC index + weights, set_weights_CIC (mesh.py:5319-5324) under the
-// coordinate map of mesh.py:1604-1606 / :430-432.
-// ---------------------------------------------------------------------------
-struct Cic1 {
-    i64 index;  // reference (ghosted) index of the lower cell
-    double w0, w1;
-};
-__device__ __forceinline__ Cic1 cic1(double pos, double off, double scale) {
-    double x = (pos - off) * scale;
-    Cic1 r;
-    r.index = (i64)x;  // int(x); x > 0 always (mesh.py:1602-1603)
-    double dist = x - (double)r.index;
-    r.w0 = 1 - dist;
-    r.w1 = dist;
-    return r;
-}
-__device__ __forceinline__ i64 wrap(i64 a, i64 n) {
-    // a in [-n, 2n)
-    a = a < 0 ? a + n : a;
-    return a >= n ? a - n : a;
-}
-
-// ---------------------------------------------------------------------------
-// A1/A2 deposit, direct form (cg_deposit_cic: particles in any order).  Index and weight
-// arithmetic is the reference's; only the summation order across particles differs.
-// Made for particles whose memory order is compact in space but is not THIS mesh's tile
-// order — BASELINE configs[4]: 512^3 particles, sorted by the tiles of their own 1024^3
-// P3M mesh, deposited onto the 256^3 PM mesh of the (fluid <- particles, fluid) interaction
-// (interactions.py:1985-2335; param/example_nonlinnu:36-45).  Device-scope FP64 atomics execute
-// memory-side on MI355X (8 per particle: 31.7 ms for 2^27 particles).  Here a workgroup takes
-// 2048 consecutive particles, finds the box of their lower cells (relative to the first one's:
-// the periodic seam is no seam), and — when the box with its CIC overhang fits 4096 cells of LDS —
-// accumulates there (ds_add_f64) and adds the box to the mesh once: one device atomic per
-// touched cell instead of eight per particle.  A chunk that is spread out (unsorted particles)
-// takes the direct atomics: 8 device-scope FP64 atomic adds per particle.
-// ---------------------------------------------------------------------------
-constexpr int kDcPer = 4, kDcLanes = 512, kDcCells = 4096;
-__global__ __launch_bounds__(kDcLanes) void k_deposit_cic_chunks(
-    const double *__restrict__ pos, i64 n, double *__restrict__ mesh, i64 N, i64 ny, i64 pad,
-    int g, XMap xm, CicGeom geo, double contribution) {
-    __shared__ double blk[kDcCells];
-    __shared__ int s_ref[3], s_lo[3], s_hi[3];
-    const int tid = threadIdx.x;
-    const i64 base = (i64)blockIdx.x * (kDcLanes * kDcPer);
-    const int Ni = (int)N;
-    double px[kDcPer], py[kDcPer], pz[kDcPer];
-    bool valid[kDcPer];
-#pragma unroll
-    for (int u = 0; u < kDcPer; u++) {
-        const i64 p = base + tid + (i64)kDcLanes * u;
-        valid[u] = p < n;
-        px[u] = py[u] = pz[u] = 0;
-        if (valid[u]) px[u] = pos[3 * p], py[u] = pos[3 * p + 1], pz[u] = pos[3 * p + 2];
-    }
-    auto cells = [&](int u, int (&cell)[3]) {
-        cell[0] = (int)wrap(cic1(px[u], geo.off[0], geo.scale).index - g, N);
-        cell[1] = (int)wrap(cic1(py[u], geo.off[1], geo.scale).index - g, N);
-        cell[2] = (int)wrap(cic1(pz[u], geo.off[2], geo.scale).index - g, N);
-    };
-    if (tid == 0) {  // (the chunk's first particle exists: base < n)
-        int c0[3];
-        cells(0, c0);
-        for (int d = 0; d < 3; d++) {
-            s_ref[d] = c0[d];
-            s_lo[d] = 0;
-            s_hi[d] = 0;
-        }
-    }
-    __syncthreads();
-    const int r0 = s_ref[0], r1 = s_ref[1], r2 = s_ref[2];
-    // lower cells relative to the first particle's, through the periodic seam: in [-N/2, N/2)
-    auto rel = [&](int cell, int ref) {
-        int d = cell - ref;
-        d += d < -(Ni / 2) ? Ni : 0;
-        d -= d >= Ni - Ni / 2 ? Ni : 0;
-        return d;
-    };
-    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < kDcPer; u++) {
-        if (!valid[u]) continue;
-        int cell[3];
-        cells(u, cell);
-        const int d[3] = {rel(cell[0], r0), rel(cell[1], r1), rel(cell[2], r2)};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            lo[k] = min(lo[k], d[k]);
-            hi[k] = max(hi[k], d[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            lo[k] = min(lo[k], __shfl_xor(lo[k], m));
-            hi[k] = max(hi[k], __shfl_xor(hi[k], m));
-        }
-        if ((tid & 63) == 0) {
-            atomicMin(&s_lo[k], lo[k]);
-            atomicMax(&s_hi[k], hi[k]);
-        }
-    }
-    __syncthreads();
-    const int l0 = s_lo[0], l1 = s_lo[1], l2 = s_lo[2];
-    const int e0 = s_hi[0] - l0 + 2, e1 = s_hi[1] - l1 + 2, e2 = s_hi[2] - l2 + 2;
-    const bool fits = (i64)e0 * e1 * e2 <= kDcCells && e0 <= Ni && e1 <= Ni && e2 <= Ni;
-    const int ncells = fits ? e0 * e1 * e2 : 0;
-    for (int i = tid; i < ncells; i += kDcLanes) blk[i] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int u = 0; u < kDcPer; u++) {
-        if (!valid[u]) continue;
-        const Cic1 cx = cic1(px[u], geo.off[0], geo.scale), cy = cic1(py[u], geo.off[1], geo.scale),
-                   cz = cic1(pz[u], geo.off[2], geo.scale);
-        // mesh.py:5142-5155: ((w_x*contribution)*w_y)*w_z
-        const double wi0 = cx.w0 * contribution, wi1 = cx.w1 * contribution;
-        const double w00 = wi0 * cy.w0, w01 = wi0 * cy.w1, w10 = wi1 * cy.w0, w11 = wi1 * cy.w1;
-        if (fits) {
-            const int a = rel((int)wrap(cx.index - g, N), r0) - l0,
-                      b = rel((int)wrap(cy.index - g, N), r1) - l1,
-                      c = rel((int)wrap(cz.index - g, N), r2) - l2;
-            double *q = blk + (a * e1 + b) * e2 + c;
-            unsafeAtomicAdd(q, w00 * cz.w0);
-            unsafeAtomicAdd(q + 1, w00 * cz.w1);
-            unsafeAtomicAdd(q + e2, w01 * cz.w0);
-            unsafeAtomicAdd(q + e2 + 1, w01 * cz.w1);
-            unsafeAtomicAdd(q + e1 * e2, w10 * cz.w0);
-            unsafeAtomicAdd(q + e1 * e2 + 1, w10 * cz.w1);
-            unsafeAtomicAdd(q + e1 * e2 + e2, w11 * cz.w0);
-            unsafeAtomicAdd(q + e1 * e2 + e2 + 1, w11 * cz.w1);
-        } else {
-            const i64 i0 = cg_xlayer(xm, cx.index - g, N), i1 = cg_xlayer(xm, cx.index - g + 1, N);
-            const i64 j0 = wrap(cy.index - g, N), j1 = wrap(cy.index - g + 1, N);
-            const i64 k0 = wrap(cz.index - g, N), k1 = wrap(cz.index - g + 1, N);
-            double *r00 = mesh + (i0 * ny + j0) * pad, *r01 = mesh + (i0 * ny + j1) * pad;
-            double *r10 = mesh + (i1 * ny + j0) * pad, *r11 = mesh + (i1 * ny + j1) * pad;
-            unsafeAtomicAdd(r00 + k0, w00 * cz.w0);
-            unsafeAtomicAdd(r00 + k1, w00 * cz.w1);
-            unsafeAtomicAdd(r01 + k0, w01 * cz.w0);
-            unsafeAtomicAdd(r01 + k1, w01 * cz.w1);
-            unsafeAtomicAdd(r10 + k0, w10 * cz.w0);
-            unsafeAtomicAdd(r10 + k1, w10 * cz.w1);
-            unsafeAtomicAdd(r11 + k0, w11 * cz.w0);
-            unsafeAtomicAdd(r11 + k1, w11 * cz.w1);
-        }
-    }
-    if (!fits) return;  // (uniform)
-    __syncthreads();
-    for (int i = tid; i < ncells; i += kDcLanes) {
-        const double v = blk[i];
-        if (v == 0) continue;
-        const int c = i % e2, b = (i / e2) % e1, a = i / (e2 * e1);
-        // the cell's index on the mesh: in [-N, 2N) before the wrap (|rel| <= N/2, e <= N)
-        const i64 gi = cg_xlayer(xm, wrap((i64)r0 + l0 + a, N), N), gj = wrap((i64)r1 + l1 + b, N),
-                  gk = wrap((i64)r2 + l2 + c, N);
-        unsafeAtomicAdd(mesh + (gi * ny + gj) * pad + gk, v);
-    }
-}
-
-int cgk_deposit_cic(cg_ctx *c, const double *pos, i64 n, double contribution) {
-    if (n <= 0) return 0;
-    const i64 blocks = (n + kDcLanes * kDcPer - 1) / (kDcLanes * kDcPer);
-    hipLaunchKernelGGL(k_deposit_cic_chunks, dim3((unsigned)blocks), dim3(kDcLanes), 0, c->stream,
-                       pos, n, c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->xmap,
-                       c->geom_deposit, contribution);
-    CG_LAUNCH_CHECK();
-    return 0;
-}
 
 // ---------------------------------------------------------------------------
 // A5/A6 k-space kernel on rocFFT's natural output layout complex[i][j][kk]
@@ -230,22 +63,18 @@ int cgk_transpose_fourier(cg_ctx *c, const double *src, double *dst) {
 }
 
 // ---------------------------------------------------------------------------
-// A9/A10 gather + finite difference + kick, direct form (cg_gather_kick: particles in any
-// order).  For each dim the 8 force-cell values are formed exactly as diff_domaingrid forms
-// them (mesh.py:4966-4981) and accumulated in the order of mesh.py:5142-5155 / :445, then
-// value *= factor, mom += value (:456-459).
-// Like the deposit above, a workgroup takes 2048 consecutive particles and, when the box of
-// their cells with the stencil's reach fits 4096 cells, copies that box of the potential into
-// LDS first: particles that are compact in space but not in THIS mesh's tile order (configs[4]:
-// the matter particles, sorted by the tiles of their 1024^3 mesh, kicked by the fluid's
-// potential on the 256^3 mesh) then read the mesh once per box instead of 48 scattered values
-// per particle (5.5 -> 2.x ms for 2^27 particles).  A chunk that is spread out reads the mesh
-// directly.
+// A9/A10 gather + finite difference + kick (cg_gather_kick: particles in any order).  For each
+// dim the 8 force-cell values are formed exactly as diff_domaingrid forms them
+// (mesh.py:4966-4981, fd_value) and accumulated in the order of mesh.py:5142-5155 / :445, then
+// value *= factor, mom += value (:456-459).  Through the chunk boxes of cg_chunk_box.h: the box
+// of the potential a chunk needs is the box of its CIC cells with the difference's reach on
+// both sides.
 // ---------------------------------------------------------------------------
+// phi(a, b, c): the potential at cell (a, b, c) of the particle's (2 + 2H)^3 cells
 template <int ORDER, class Phi>
 __device__ __forceinline__ void gather_force(const Phi &phi, const double (&wx)[2],
                                              const double (&wy)[2], const double (&wz)[2],
-                                             double c1, double c2, double (&val)[3]) {
+                                             const FdCoef &fc, double (&val)[3]) {
     constexpr int H = ORDER / 2;
 #pragma unroll
     for (int i = 0; i < 2; i++)
@@ -256,19 +85,9 @@ __device__ __forceinline__ void gather_force(const Phi &phi, const double (&wx)[
             for (int k = 0; k < 2; k++) {
                 const double w = wij * wz[k];
                 const int a = H + i, b = H + j, cc = H + k;
-                double fx, fy, fz;
-                if (ORDER == 2) {
-                    fx = c1 * (phi(a + 1, b, cc) - phi(a - 1, b, cc));
-                    fy = c1 * (phi(a, b + 1, cc) - phi(a, b - 1, cc));
-                    fz = c1 * (phi(a, b, cc + 1) - phi(a, b, cc - 1));
-                } else {
-                    fx = c1 * (phi(a + 1, b, cc) - phi(a - 1, b, cc)) -
-                         c2 * (phi(a + 2, b, cc) - phi(a - 2, b, cc));
-                    fy = c1 * (phi(a, b + 1, cc) - phi(a, b - 1, cc)) -
-                         c2 * (phi(a, b + 2, cc) - phi(a, b - 2, cc));
-                    fz = c1 * (phi(a, b, cc + 1) - phi(a, b, cc - 1)) -
-                         c2 * (phi(a, b, cc + 2) - phi(a, b, cc - 2));
-                }
+                const double fx = fd_value<ORDER>([&](int s) { return phi(a + s, b, cc); }, fc);
+                const double fy = fd_value<ORDER>([&](int s) { return phi(a, b + s, cc); }, fc);
+                const double fz = fd_value<ORDER>([&](int s) { return phi(a, b, cc + s); }, fc);
                 val[0] += fx * w;
                 val[1] += fy * w;
                 val[2] += fz * w;
@@ -277,104 +96,32 @@ __device__ __forceinline__ void gather_force(const Phi &phi, const double (&wx)[
 }
 
 template <int ORDER>
-__global__ __launch_bounds__(kDcLanes) void k_gather_kick_chunks(
+__global__ __launch_bounds__(kChunkLanes) void k_gather_kick_chunks(
     const double *__restrict__ pos, double *__restrict__ mom, i64 n,
-    const double *__restrict__ mesh, i64 N, i64 ny, i64 pad, int g, XMap xm, CicGeom geo,
-    double c1, double c2, double factor) {
+    const double *__restrict__ mesh, int N, i64 ny, i64 pad, int g, XMap xm, CicGeom geo,
+    FdCoef fc, double factor) {
     constexpr int H = ORDER / 2;      // stencil half width
     constexpr int W = 2 + 2 * H;      // cells needed per dimension
-    __shared__ double blk[kDcCells];
-    __shared__ int s_ref[3], s_lo[3], s_hi[3];
-    const int tid = threadIdx.x;
-    const i64 base = (i64)blockIdx.x * (kDcLanes * kDcPer);
-    const int Ni = (int)N;
-    double px[kDcPer], py[kDcPer], pz[kDcPer];
-    bool valid[kDcPer];
-#pragma unroll
-    for (int u = 0; u < kDcPer; u++) {
-        const i64 p = base + tid + (i64)kDcLanes * u;
-        valid[u] = p < n;
-        px[u] = py[u] = pz[u] = 0;
-        if (valid[u]) px[u] = pos[3 * p], py[u] = pos[3 * p + 1], pz[u] = pos[3 * p + 2];
-    }
-    auto cells = [&](int u, int (&cell)[3]) {
-        cell[0] = (int)wrap(cic1(px[u], geo.off[0], geo.scale).index - g, N);
-        cell[1] = (int)wrap(cic1(py[u], geo.off[1], geo.scale).index - g, N);
-        cell[2] = (int)wrap(cic1(pz[u], geo.off[2], geo.scale).index - g, N);
-    };
-    if (tid == 0) {
-        int c0[3];
-        cells(0, c0);
-        for (int d = 0; d < 3; d++) {
-            s_ref[d] = c0[d];
-            s_lo[d] = 0;
-            s_hi[d] = 0;
-        }
-    }
-    __syncthreads();
-    const int r0 = s_ref[0], r1 = s_ref[1], r2 = s_ref[2];
-    auto rel = [&](int cell, int ref) {
-        int d = cell - ref;
-        d += d < -(Ni / 2) ? Ni : 0;
-        d -= d >= Ni - Ni / 2 ? Ni : 0;
-        return d;
-    };
-    int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
-#pragma unroll
-    for (int u = 0; u < kDcPer; u++) {
-        if (!valid[u]) continue;
-        int cell[3];
-        cells(u, cell);
-        const int d[3] = {rel(cell[0], r0), rel(cell[1], r1), rel(cell[2], r2)};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            lo[k] = min(lo[k], d[k]);
-            hi[k] = max(hi[k], d[k]);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-#pragma unroll
-        for (int m = 1; m < 64; m <<= 1) {
-            lo[k] = min(lo[k], __shfl_xor(lo[k], m));
-            hi[k] = max(hi[k], __shfl_xor(hi[k], m));
-        }
-        if ((tid & 63) == 0) {
-            atomicMin(&s_lo[k], lo[k]);
-            atomicMax(&s_hi[k], hi[k]);
-        }
-    }
-    __syncthreads();
-    // the box: cells lo - H .. hi + 1 + H of every dimension
-    const int l0 = s_lo[0] - H, l1 = s_lo[1] - H, l2 = s_lo[2] - H;
-    const int e0 = s_hi[0] - s_lo[0] + W, e1 = s_hi[1] - s_lo[1] + W, e2 = s_hi[2] - s_lo[2] + W;
-    const bool fits = (i64)e0 * e1 * e2 <= kDcCells && e0 <= Ni && e1 <= Ni && e2 <= Ni;
-    if (fits) {
-        const int ncells = e0 * e1 * e2;
-        for (int i = tid; i < ncells; i += kDcLanes) {
-            const int c = i % e2, b = (i / e2) % e1, a = i / (e2 * e1);
-            const i64 gi = cg_xlayer(xm, wrap((i64)r0 + l0 + a, N), N),
-                      gj = wrap((i64)r1 + l1 + b, N), gk = wrap((i64)r2 + l2 + c, N);
-            blk[i] = mesh[(gi * ny + gj) * pad + gk];
-        }
-    }
-    __syncthreads();
+    __shared__ double blk[kChunkCells];
+    double x[kChunkPer][3];
+    int cell[kChunkPer][3];
+    chunk_load<2>(pos, n, geo, g, N, x, cell);
+    const ChunkBox<W, H> B = chunk_box<W, H>(cell, n, N);
+    chunk_fill(B, blk, mesh, N, ny, pad, xm);
 #pragma unroll 1
-    for (int u = 0; u < kDcPer; u++) {
-        const i64 p = base + tid + (i64)kDcLanes * u;
+    for (int u = 0; u < kChunkPer; u++) {
+        const i64 p = chunk_particle(u);
         if (p >= n) continue;
-        const Cic1 cx = cic1(px[u], geo.off[0], geo.scale), cy = cic1(py[u], geo.off[1], geo.scale),
-                   cz = cic1(pz[u], geo.off[2], geo.scale);
+        const Cic1 cx = cic1(x[u][0], geo.off[0], geo.scale),
+                   cy = cic1(x[u][1], geo.off[1], geo.scale),
+                   cz = cic1(x[u][2], geo.off[2], geo.scale);
         const double wx[2] = {cx.w0, cx.w1}, wy[2] = {cy.w0, cy.w1}, wz[2] = {cz.w0, cz.w1};
         double val[3] = {0, 0, 0};
-        if (fits) {
-            // entry (s_a, s_b, s_c) of the particle's W^3 cells = cell index - g - H + s
-            const double *q = blk +
-                ((rel((int)wrap(cx.index - g, N), r0) - H - l0) * e1 +
-                 (rel((int)wrap(cy.index - g, N), r1) - H - l1)) * e2 +
-                (rel((int)wrap(cz.index - g, N), r2) - H - l2);
-            gather_force<ORDER>([&](int a, int b, int c) { return q[(a * e1 + b) * e2 + c]; }, wx,
-                                wy, wz, c1, c2, val);
+        if (B.fits) {
+            const double *q = blk + B.entry_of(cell[u], N);
+            gather_force<ORDER>(
+                [&](int a, int b, int c) { return q[(a * B.e[1] + b) * B.e[2] + c]; }, wx, wy, wz,
+                fc, val);
         } else {
             i64 ix[W], iy[W], iz[W];
 #pragma unroll
@@ -384,7 +131,7 @@ __global__ __launch_bounds__(kDcLanes) void k_gather_kick_chunks(
                 iz[s] = wrap(cz.index - g - H + s, N);
             }
             gather_force<ORDER>([&](int a, int b, int c) { return mesh[ix[a] + iy[b] + iz[c]]; },
-                                wx, wy, wz, c1, c2, val);
+                                wx, wy, wz, fc, val);
         }
         if (factor != 1) {
             val[0] *= factor;
@@ -400,19 +147,16 @@ __global__ __launch_bounds__(kDcLanes) void k_gather_kick_chunks(
 int cgk_gather_kick(cg_ctx *c, const double *pos, double *mom, i64 n, int diff_order,
                     double factor) {
     if (n <= 0) return 0;
-    const i64 blocks = (n + kDcLanes * kDcPer - 1) / (kDcLanes * kDcPer);
-    double dx = c->p.boxsize / (double)c->N;  // interactions.py:2133
-    if (diff_order == 2) {
-        double c1 = (1.0 / 2) / dx;  // mesh.py:4967
-        hipLaunchKernelGGL(k_gather_kick_chunks<2>, dim3((unsigned)blocks), dim3(kDcLanes), 0,
-                           c->stream, pos, mom, n, c->mesh, c->N, c->ny, c->pad, c->p.nghosts,
-                           c->xmap, c->geom_gather, c1, 0.0, factor);
-    } else {
-        double c1 = (2.0 / 3) / dx, c2 = (1.0 / 12) / dx;  // mesh.py:4973-4977
-        hipLaunchKernelGGL(k_gather_kick_chunks<4>, dim3((unsigned)blocks), dim3(kDcLanes), 0,
-                           c->stream, pos, mom, n, c->mesh, c->N, c->ny, c->pad, c->p.nghosts,
-                           c->xmap, c->geom_gather, c1, c2, factor);
-    }
+    FdCoef fc;
+    fd_coefficients(diff_order, c->p.boxsize / (double)c->N, fc);  // dx: interactions.py:2133
+    if (diff_order == 2)
+        hipLaunchKernelGGL(k_gather_kick_chunks<2>, dim3(chunk_blocks(n)), dim3(kChunkLanes), 0,
+                           c->stream, pos, mom, n, c->mesh, (int)c->N, c->ny, c->pad,
+                           c->p.nghosts, c->xmap, c->geom_gather, fc, factor);
+    else
+        hipLaunchKernelGGL(k_gather_kick_chunks<4>, dim3(chunk_blocks(n)), dim3(kChunkLanes), 0,
+                           c->stream, pos, mom, n, c->mesh, (int)c->N, c->ny, c->pad,
+                           c->p.nghosts, c->xmap, c->geom_gather, fc, factor);
     CG_LAUNCH_CHECK();
     return 0;
 }
@@ -465,7 +209,7 @@ int cgk_layers_write(cg_ctx *c, i64 layer0, i64 nlayers, const double *src, int 
 
 // Owner domain of each particle: the x-slab that holds its lower CIC cell
 // (counterpart of which_domain(), communication.py:756-772, for slab domains).
-__global__ void k_owner_rank(const double *__restrict__ pos, i64 n, CicGeom geo, int g, i64 N,
+__global__ void k_owner_rank(const double *__restrict__ pos, i64 n, CicGeom geo, int g, int N,
                              i64 nxl, int *__restrict__ owner) {
     i64 p = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
@@ -478,7 +222,7 @@ __global__ void k_owner_rank(const double *__restrict__ pos, i64 n, CicGeom geo,
 // on the device, so the host enqueues this right behind the gather-kick without waiting.
 __global__ void k_emigrant_dest(const double *__restrict__ pos, const double *__restrict__ mom,
                                 const i64 *__restrict__ idx, const unsigned *__restrict__ count,
-                                i64 cap, double dtm, double L, CicGeom geo, int g, i64 N, i64 nxl,
+                                i64 cap, double dtm, double L, CicGeom geo, int g, int N, i64 nxl,
                                 int *__restrict__ dest, int *__restrict__ send_counts) {
     i64 t = (i64)blockIdx.x * blockDim.x + threadIdx.x;
     i64 n = (i64)*count < cap ? (i64)*count : cap;
@@ -496,7 +240,7 @@ __global__ void k_emigrant_dest(const double *__restrict__ pos, const double *__
         if (m == L) m = 0;
         x = m;
     }
-    int d = (int)(wrap(cic1(x, geo.off[0], geo.scale).index - g, N) / nxl);
+    int d = (int)((i64)wrap(cic1(x, geo.off[0], geo.scale).index - g, N) / nxl);
     dest[t] = d;
     atomicAdd(&send_counts[d], 1);
 }
@@ -506,7 +250,7 @@ int cgk_emigrant_dest(cg_ctx *c, const double *pos, const double *mom, const i64
     if (cap == 0) return 0;
     hipLaunchKernelGGL(k_emigrant_dest, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0,
                        c->stream, pos, mom, idx, count, cap, dtm, c->p.boxsize, c->geom_deposit,
-                       c->p.nghosts, c->N, c->xmap.nxl, dest, send_counts);
+                       c->p.nghosts, (int)c->N, c->xmap.nxl, dest, send_counts);
     CG_LAUNCH_CHECK();
     return 0;
 }
@@ -514,7 +258,7 @@ int cgk_emigrant_dest(cg_ctx *c, const double *pos, const double *mom, const i64
 int cgk_owner_rank(cg_ctx *c, const double *pos, i64 n, int *owner) {
     if (n == 0) return 0;
     hipLaunchKernelGGL(k_owner_rank, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream,
-                       pos, n, c->geom_deposit, c->p.nghosts, c->N, c->xmap.nxl, owner);
+                       pos, n, c->geom_deposit, c->p.nghosts, (int)c->N, c->xmap.nxl, owner);
     CG_LAUNCH_CHECK();
     return 0;
 }

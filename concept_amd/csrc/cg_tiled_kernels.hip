@@ -12,32 +12,12 @@
 // Arithmetic per particle and per cell is the reference's (see
 // cg_mesh_kernels.hip); only the order in which particles are added to a
 // cell differs.  Compiled with -ffp-contract=off.
+#include "cg_chunk_box.h"  // the CIC index and weights (cic1, in 32-bit cell arithmetic), wrap
 #include "cg_internal.h"
 #include "cg_tiles.h"
 
-// 32-bit cell arithmetic: x is positive and < gridsize + 2*nghosts + 1 (positions are in
-// [0, boxsize)), so the reference's truncation to Py_ssize_t equals truncation to int —
-// one v_cvt_i32_f64 instead of the ~15-instruction double -> int64 sequence, and every
-// index below (N <= 2048 and change) stays in 32-bit registers.
 // two doubles at 8-byte alignment (the xy of an xyz record)
 typedef double d2u8 __attribute__((ext_vector_type(2), aligned(8)));
-struct Cic1 {
-    int index;
-    double w0, w1;
-};
-__device__ __forceinline__ Cic1 cic1(double pos, double off, double scale) {
-    double x = (pos - off) * scale;
-    Cic1 r;
-    r.index = (int)x;
-    double dist = x - (double)r.index;
-    r.w0 = 1 - dist;
-    r.w1 = dist;
-    return r;
-}
-__device__ __forceinline__ int wrap(int a, int n) {
-    a = a < 0 ? a + n : a;
-    return a >= n ? a - n : a;
-}
 
 // blockIdx -> tile.  Consecutive workgroups land on different XCDs
 // (block b -> XCD b % 8, observed); give each XCD a contiguous eighth of the

@@ -25,6 +25,19 @@ __device__ __forceinline__ double wave_max_down(double v) {
     return v;
 }
 
+// Smallest and largest int of the 64 lanes by xor butterfly, m = 1, 2, ..., 32.  Every lane ends
+// with the result.
+__device__ __forceinline__ int wave_min_xor(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = min(v, __shfl_xor(v, m));
+    return v;
+}
+__device__ __forceinline__ int wave_max_xor(int v) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v = max(v, __shfl_xor(v, m));
+    return v;
+}
+
 // v + the DPP move of v (0 where the move has no source lane or the row is masked out)
 template <int kCtrl, int kRows>
 __device__ __forceinline__ double dpp_add(double v) {

@@ -1,6 +1,6 @@
 """GPU tests of the general-order deposit and scalar gather (cg_deposit / cg_gather_scalar:
 k_deposit_general<1..4>, k_gather_scalar<1..4> in cg_general.hip) and of the untiled CIC deposit
-(cg_deposit_cic in cg_mesh_kernels.hip), on BOTH of their code paths.
+(cg_deposit_cic: the order-2 deposit with the context's own geometry), on BOTH of their code paths.
 
 A workgroup of these kernels takes 2048 consecutive particles.  When the first cells of their
 stencils span a box that fits 4096 cells of LDS (stencil width included) the chunk works in LDS
@@ -37,7 +37,7 @@ ORDER_NAMES = {1: 'NGP', 2: 'CIC', 3: 'TSC', 4: 'PCS'}
 # t-space: a particle with coordinate t (in cells) has floor(t) as the first cell of its stencil;
 # the grid coordinate the kernels see is t + nghosts + T_SHIFT[order]
 T_SHIFT = {1: -0.5, 2: 0.0, 3: 0.5, 4: 1.0}
-KINDS = [1, 2, 3, 4, 'cic']        # 'cic': PotentialMesh.deposit, the sibling kernel
+KINDS = [1, 2, 3, 4, 'cic']        # 'cic': PotentialMesh.deposit (cg_deposit_cic)
 L_BOX = 100.0                      # cell sizes 100/64, 100/256, 100/16: exact in binary
 
 
