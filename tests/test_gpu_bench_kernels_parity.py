@@ -22,6 +22,8 @@ Bars (reference: test/pure_python_pm/analyze.py:125, 1e-10 on positions over a w
 import numpy as np
 import pytest
 
+import tile_order_refs
+
 pytestmark = pytest.mark.gpu
 
 
@@ -162,6 +164,7 @@ def test_bench_sequence_two_steps_vs_oracle(npart, N, dist):
             assert 8 < want.size <= mesh.ntiles//8
             assert np.array_equal(np.sort(heavy), want)
             assert (np.diff(np.minimum(pops[heavy]//(thr//3), 63)) <= 0).all()
+            assert tile_order_refs.check_list(heavy, pops, 1536).thr == thr
         else:
             assert heavy is not None and heavy.size == 0
         pos_prev = np.empty((n, 3))
