@@ -138,3 +138,27 @@ __device__ __forceinline__ double kspace_factor_sep(const KspaceFixedS &F, int N
     const double f = t_a * F.g / (double)(k2 == 0 ? 1 : k2);
     return (F.dead | (a == nyq) | (k2 == 0)) ? 0.0 : f;
 }
+
+// The walk of the streaming k-space kernels (cg_lpt.hip): mode number e of a Fourier view seen as
+// complex[N][nj][N/2 + 1] (cg_ctx::four, rows b = j0 + bl of the view), with the signed wave
+// numbers and k2 in the reference's order of summation (ic.py:714).
+struct KspaceMode {
+    int a, bl, kk;  // array indices; bl counts from the view's first row
+    i64 ki, kj;     // signed wave numbers of a and b (kk is its own)
+    i64 k2;
+    bool live;      // off the origin and the three Nyquist planes (nullify_modes)
+};
+__device__ __forceinline__ KspaceMode kspace_mode(i64 e, int N, int j0, int nj) {
+    const int nyq = N / 2, nk = nyq + 1;
+    KspaceMode m;
+    const int row = (int)(e / nk);
+    m.kk = (int)(e - (i64)row * nk);
+    m.a = row / nj;
+    m.bl = row - m.a * nj;
+    const int b = j0 + m.bl;
+    m.ki = m.a - (m.a >= nyq ? N : 0);
+    m.kj = b - (b >= nyq ? N : 0);
+    m.k2 = (m.kj * m.kj + m.ki * m.ki) + (i64)m.kk * m.kk;
+    m.live = m.a != nyq && b != nyq && m.kk != nyq && m.k2 != 0;
+    return m;
+}

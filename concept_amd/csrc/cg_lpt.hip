@@ -1,18 +1,23 @@
-// cg_lpt.hip — the mesh and particle passes of the 1LPT / 2LPT particle realisation.
+// cg_lpt.hip — the mesh and particle passes of the realisations: 1LPT / 2LPT particles, fluids.
 //   k_lpt_potential  realize_grid (scalar case)         ic.py:711-764
 //                    fused with laplacian_inverse       mesh.py:3422-3437
 //   k_lpt_diff       fourier_diff                       mesh.py:3466-3510
 //   k_lpt_product    the grid product and the move to the output grid of handle_lpt_term
 //                                                       ic.py:2020-2057
 //   k_lpt_displace   displace_particles                 ic.py:2249-2280
-// All four are streaming maps: one grid-stride loop, a thread per complex mode or per pair of
+//   k_realize_grid   realize_grid (scalar and vector)   ic.py:708-764
+//   k_fluid_from_mesh  domain_decompose and the move to ϱ or Jⁱ of realize_fluid
+//                                                       ic.py:418-456
+// All six are streaming maps: one grid-stride loop, a thread per complex mode or per pair of
 // neighbouring real cells (16-byte loads and stores), no LDS, no atomics, nothing wave-level.
 // The k-space kernels walk the Fourier view of the contexts (cg_ctx::four, the view
 // k_fourier_operate walks) over the N/2 + 1 modes of every row, the real-space kernels the N
 // cells of the N rows of the owned layers: the row padding and the unused row of a layer are
 // neither read nor written.  Compiled with -ffp-contract=off: every product and sum is rounded
-// on its own, in the reference's order.  FP64 throughout.
+// on its own, in the reference's order.  FP64 throughout.  The k-space kernels share their walk
+// over the modes: kspace_mode (cg_kspace.h).
 #include "cg_internal.h"
+#include "cg_kspace.h"
 
 namespace {
 
@@ -43,34 +48,31 @@ __global__ __launch_bounds__(kThreads) void k_lpt_potential(double2 *dst, const 
                                                             int N, i64 dst_si, i64 src_si, i64 cp,
                                                             int j0, int nj, LptPotential P) {
 #pragma clang fp contract(off)
-    const int nyq = N / 2, nk = nyq + 1;
-    const i64 total = (i64)N * nj * nk;
+    const i64 total = (i64)N * nj * (N / 2 + 1);
     for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
          e += (i64)gridDim.x * kThreads) {
-        const int row = (int)(e / nk), kk = (int)(e - (i64)row * nk);
-        const int a = row / nj, bl = row - a * nj, b = j0 + bl;
-        const i64 ki = a - (a >= nyq ? N : 0), kj = b - (b >= nyq ? N : 0);
-        const i64 k2 = (kj * kj + ki * ki) + (i64)kk * kk;  // ic.py:714
+        const KspaceMode m = kspace_mode(e, N, j0, nj);
         double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
-        if (a != nyq && b != nyq && kk != nyq && k2 != 0) {
-            const double2 z = src[(i64)a * src_si + (i64)bl * cp + kk];
+        if (m.live) {
+            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
             double re = z.x, im = z.y;
             if (P.shifted) {  // mesh.py:2873-2888, ic.py:719-726
-                const double theta = ((double)ki * P.A + (double)kj * P.B) + (double)kk * P.Cc;
+                const double theta =
+                    ((double)m.ki * P.A + (double)m.kj * P.B) + (double)m.kk * P.Cc;
                 const double c = cos(theta), s = sin(theta);
                 const double re2 = re * c - im * s, im2 = re * s + im * c;
                 re = re2;
                 im = im2;
             }
             if (P.amp) {  // ic.py:715, 761-762
-                const double amplitude = P.amp[k2];
+                const double amplitude = P.amp[m.k2];
                 re = amplitude * re;
                 im = amplitude * im;
             }
-            const double inv = P.lap / (double)k2;  // mesh.py:3434-3436
+            const double inv = P.lap / (double)m.k2;  // mesh.py:3434-3436
             out = make_double2(re * inv, im * inv);
         }
-        dst[(i64)a * dst_si + (i64)bl * cp + kk] = out;
+        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
     }
 }
 
@@ -80,27 +82,24 @@ __global__ __launch_bounds__(kThreads) void k_lpt_diff(double2 *dst, const doubl
                                                        i64 dst_si, i64 src_si, i64 cp, int j0,
                                                        int nj, int dim0, int dim1, double scale) {
 #pragma clang fp contract(off)
-    const int nyq = N / 2, nk = nyq + 1;
-    const i64 total = (i64)N * nj * nk;
+    const i64 total = (i64)N * nj * (N / 2 + 1);
     for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
          e += (i64)gridDim.x * kThreads) {
-        const int row = (int)(e / nk), kk = (int)(e - (i64)row * nk);
-        const int a = row / nj, bl = row - a * nj, b = j0 + bl;
-        const int ki = a - (a >= nyq ? N : 0), kj = b - (b >= nyq ? N : 0);
+        const KspaceMode m = kspace_mode(e, N, j0, nj);
         double2 out = make_double2(0.0, 0.0);
-        if (a != nyq && b != nyq && kk != nyq && (ki | kj | kk) != 0) {
-            const double2 z = src[(i64)a * src_si + (i64)bl * cp + kk];
-            const int kl0 = dim0 == 0 ? ki : (dim0 == 1 ? kj : kk);
+        if (m.live) {
+            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
+            const i64 kl0 = dim0 == 0 ? m.ki : (dim0 == 1 ? m.kj : m.kk);
             if (dim1 < 0) {
                 const double amplitude = scale * (double)kl0;  // mesh.py:3496
                 out = make_double2(amplitude * -z.y, amplitude * z.x);
             } else {
-                const int kl1 = dim1 == 0 ? ki : (dim1 == 1 ? kj : kk);
+                const i64 kl1 = dim1 == 0 ? m.ki : (dim1 == 1 ? m.kj : m.kk);
                 const double amplitude = scale * (double)kl0 * (double)kl1;  // mesh.py:3506
                 out = make_double2(amplitude * -z.x, amplitude * -z.y);
             }
         }
-        dst[(i64)a * dst_si + (i64)bl * cp + kk] = out;
+        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
     }
 }
 
@@ -154,6 +153,58 @@ __global__ __launch_bounds__(kThreads) void k_lpt_displace(const double *psi, in
             mom[r] = mom[r] + mom_factor * v.x;
             mom[r + 3] = mom[r + 3] + mom_factor * v.y;
         }
+    }
+}
+
+// dst = amp[k2] * src (rank 0) or (amp[k2] * ((vec * k_index0) / k2)) * i src (rank 1) off the
+// origin and the Nyquist planes, 0 on them; vec = ℝ[-boxsize/(2*π)] of ic.py:741
+template <int kRank>
+__global__ __launch_bounds__(kThreads) void k_realize_grid(double2 *dst, const double2 *src, int N,
+                                                           i64 dst_si, i64 src_si, i64 cp, int j0,
+                                                           int nj, const double *amp, int index0,
+                                                           double vec) {
+#pragma clang fp contract(off)
+    const i64 total = (i64)N * nj * (N / 2 + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const KspaceMode m = kspace_mode(e, N, j0, nj);
+        double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
+        if (m.live) {
+            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
+            double amplitude = amp[m.k2];  // ic.py:715
+            double re = z.x, im = z.y;
+            if (kRank == 1) {  // K(k) = -i k^l/k², ic.py:732-742
+                const i64 kl = index0 == 0 ? m.ki : (index0 == 1 ? m.kj : m.kk);
+                amplitude = amplitude * ((vec * (double)kl) / (double)m.k2);
+                re = -z.y;
+                im = z.x;
+            }
+            out = make_double2(amplitude * re, amplitude * im);  // ic.py:761-762
+        }
+        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
+    }
+}
+
+// out[layer][j][k] (dense) from the real cells of the mesh's owned layers.
+// kVar 0: c0 * (1 + v); 1: the same after v += c1 * v²; 2: v * c0
+template <int kVar>
+__global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh, double *out,
+                                                              int N, i64 nrows, i64 ny, i64 pad,
+                                                              double c0, double c1) {
+#pragma clang fp contract(off)
+    const int half = N / 2;  // pairs of cells per row (N is even)
+    const i64 total = nrows * half;
+    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
+         t += (i64)gridDim.x * kThreads) {
+        const i64 row = t / half;
+        const int p = (int)(t - row * half);
+        const i64 layer = row / N;
+        double2 v = *(const double2 *)(mesh + (layer * ny + (row - layer * N)) * pad + 2 * p);
+        if (kVar == 1)  // ic.py:436
+            v = make_double2(v.x + c1 * (v.x * v.x), v.y + c1 * (v.y * v.y));
+        if (kVar == 2) v = make_double2(v.x * c0, v.y * c0);  // ic.py:456
+        else v = make_double2(c0 * (1 + v.x), c0 * (1 + v.y));  // ic.py:437
+        *(double2 *)(out + row * N + 2 * p) = v;
     }
 }
 
@@ -255,6 +306,53 @@ extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
                        (const double *)psi->mesh0, (int)psi->N, psi->ny, psi->pad,
                        pos ? pos + 3 * index_bgn : nullptr, mom ? mom + 3 * index_bgn : nullptr,
                        dim, pos_factor, mom_factor);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitudes, int64_t k2_max,
+                               int tensor_rank, int index0) {
+    if (fourier_pair_checks("cg_realize_grid", out, noise)) return 1;
+    const i64 nyq = out->N / 2;
+    CG_CHECK(amplitudes != nullptr, "cg_realize_grid: no amplitudes");
+    CG_CHECK(k2_max == 3 * (nyq - 1) * (nyq - 1),
+             "cg_realize_grid: %lld amplitudes for grid size %lld, which needs "
+             "3*(nyquist - 1)**2 + 1 = %lld", (long long)(k2_max + 1), (long long)out->N,
+             (long long)(3 * (nyq - 1) * (nyq - 1) + 1));
+    CG_CHECK(tensor_rank == 0 || tensor_rank == 1,
+             "cg_realize_grid: tensor rank %d (0 and 1 are implemented)", tensor_rank);
+    CG_CHECK(tensor_rank == 0 || (index0 >= 0 && index0 < 3),
+             "cg_realize_grid: index %d not in {0, 1, 2}", index0);
+    const double vec = -out->p.boxsize / (2 * kPi);  // ℝ[-boxsize/(2*π)], ic.py:741
+    const i64 total = out->N * (i64)out->f_nj * (nyq + 1);
+#define CG_REALIZE_GRID(RANK)                                                                     \
+    hipLaunchKernelGGL(k_realize_grid<RANK>, dim3(grid_for(total)), dim3(kThreads), 0,           \
+                       out->stream, out->four, (const double2 *)noise->four, (int)out->N,        \
+                       out->f_si, noise->f_si, out->pad / 2, out->f_j0, out->f_nj, amplitudes,   \
+                       index0, vec)
+    if (tensor_rank == 0) CG_REALIZE_GRID(0);
+    else CG_REALIZE_GRID(1);
+#undef CG_REALIZE_GRID
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_from_mesh(cg_ctx *mesh, double *out, int mode, double c0, double c1) {
+    CG_CHECK(mesh && out, "cg_fluid_from_mesh: null %s", mesh ? "output grid" : "context");
+    CG_CHECK(mode == 0 || mode == 1, "cg_fluid_from_mesh: mode %d not in {0 ϱ, 1 J}", mode);
+    CG_CHECK(mesh->N >= 2 && mesh->N % 2 == 0, "cg_fluid_from_mesh: grid size %lld is not even",
+             (long long)mesh->N);
+    CG_CHECK((uintptr_t)out % 16 == 0, "cg_fluid_from_mesh: the output grid is not 16-byte aligned");
+    const i64 nrows = mesh->xmap.nxl * mesh->N;
+    const i64 total = nrows * (mesh->N / 2);
+#define CG_FLUID_FROM_MESH(VAR)                                                                   \
+    hipLaunchKernelGGL(k_fluid_from_mesh<VAR>, dim3(grid_for(total)), dim3(kThreads), 0,         \
+                       mesh->stream, (const double *)mesh->mesh0, out, (int)mesh->N, nrows,      \
+                       mesh->ny, mesh->pad, c0, c1)
+    if (mode == 1) CG_FLUID_FROM_MESH(2);
+    else if (c1 != 0) CG_FLUID_FROM_MESH(1);
+    else CG_FLUID_FROM_MESH(0);
+#undef CG_FLUID_FROM_MESH
     CG_LAUNCH_CHECK();
     return 0;
 }

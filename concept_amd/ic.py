@@ -1,5 +1,6 @@
-"""Initial conditions: 1LPT / 2LPT particle realisation (ic.py:67-232, 599-627, 928-1589,
-1895-2280 of the reference).
+"""Initial conditions: 1LPT / 2LPT particle realisation and the realisation of the fluid
+variables ϱ and J (ic.py:67-232, 297-477, 599-627, 708-764, 928-1589, 1895-2280 of the
+reference).
 
 The reference gets two things from CLASS — a table of amplitudes T(k)·ζ(k) indexed by k² and a
 handful of growth factors — and does everything after that on meshes.  Here both are inputs
@@ -13,8 +14,14 @@ GPU (csrc/cg_lpt.hip through PotentialMesh.lpt_*):
     2LPT: the six products of second derivatives of Φ⁽¹⁾ (lpt_diff, lpt_product) summed into
     the source of Φ⁽²⁾, transformed, ∇⁻², and displaced the same way.
 
-Out of scope, refused by name: 3LPT, Orszag dealiasing, non-Gaussianity, non-primordial
-structure, fluid components, N without a cubic lattice, several domains."""
+    fluids (realize_fluid, realize): the same noise
+      -> amplitude·noise (ϱ) or amplitude·(-i kⁱ/k²)·noise (Jⁱ)   realize_grid
+      -> back to real space                                       the mesh's inverse transform
+      -> ϱ = ϱ_bar(1 + δ) or Jⁱ = a**(1 - 3w_eff)ϱ_bar(1 + w)uⁱ    fluid_from_mesh
+
+Out of scope, refused by name.  Particles: 3LPT, Orszag dealiasing, non-Gaussianity, non-primordial
+structure, N without a cubic lattice.  Fluids: the variables above J (ς, δP), closure 'class'.
+Both: several domains."""
 import contextlib
 import math
 
@@ -512,13 +519,109 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
     return {'Φ1': Φ1, 'Φ2': Φ2, 'gridsize': gridsize}
 
 
-def _amplitudes_dev(component, amplitudes, gridsize):
+# ---- fluids (ic.py:297-511, 708-764) ---------------------------------------------------------------
+def _check_fluid_scope(component, variable, multi_index):
+    name = component.name
+    if component.representation != 'fluid':
+        raise ConceptGPUError(f'realize_fluid() called with non-fluid component {name}')
+    if variable not in (0, 1):
+        raise ConceptGPUError(f'{name}: realize_fluid() got non-implemented variable = {variable} '
+                              '(ϱ and J are implemented; ς, δP and the "class" closure are not)')
+    if variable > component.boltzmann_order:
+        raise ConceptGPUError(f'{name}: fluid variable {variable} exceeds the Boltzmann order '
+                              f'{component.boltzmann_order} of the component (realisation from '
+                              'the "class" closure is not implemented)')
+    if variable == 1 and multi_index not in (0, 1, 2):
+        raise ConceptGPUError(f'{name}: realize_fluid() of J needs multi_index 0, 1 or 2, not '
+                              f'{multi_index!r}')
+    if _comm.active() is not None or getattr(component, 'nprocs', 1) > 1:
+        raise ConceptGPUError(f'{name}: realize_fluid() with an active comm process group: '
+                              'multi-GPU realisation is not implemented')
+
+
+def _realization_mesh(component, role):
+    from .mesh import get_mesh
+    p = component.params
+    return get_mesh(component.gridsize, p.boxsize, p.nghosts, p.cell_centered, role=role,
+                    device=component.device)
+
+
+def realize_fluid(component, a, amplitudes, variable=0, multi_index=0, noise=None, timings=None):
+    """Realise one fluid scalar of a fluid component at scale factor a (realize_fluid,
+    ic.py:400-477): ϱ (variable 0) or J[multi_index] (variable 1) from the primordial noise.
+
+    amplitudes: the k²-indexed table (amplitudes_from_power) of δ for ϱ, of θ for J.
+    noise: a mesh that holds the primordial noise in Fourier space (what an earlier call
+      returned); without it the noise is generated on the host and uploaded.
+    timings: a dict that receives milliseconds by kind of pass (synchronises).
+    Returns the noise mesh.  realization_options['structure'] plays no part: a variable within
+    the Boltzmann order is realised from the primordial structure (ic.py:819-823)."""
+    _check_fluid_scope(component, variable, multi_index)
+    p = component.params
+    gridsize = component.gridsize
+    amplitudes_dev = _amplitudes_dev(component, amplitudes, gridsize, 'a fluid grid of {}³ cells')
+    watch = _Stopwatch(timings)
+    if noise is None:
+        noise = _realization_mesh(component, 'realize noise')
+        with _host_timer(timings, 'noise (host)'):
+            slab = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
+                                             p.primordial_phase_shift, p)
+        with watch('upload'):
+            noise.upload_fourier(slab)
+    elif noise.gridsize != gridsize:
+        raise ConceptGPUError(f'{component.name}: a noise mesh of grid size {noise.gridsize} for '
+                              f'a fluid of grid size {gridsize}')
+    work = _realization_mesh(component, 'realize work')
+    with watch('k-space'):
+        work.realize_grid(noise, amplitudes_dev, tensor_rank=variable, index0=multi_index)
+    with watch('transforms'):
+        work.poisson_backward()
+    # δ → ϱ, uⁱ → Jⁱ (ic.py:428-456), the constants as the reference hoists them
+    ϱ_bar = component.ϱ_bar
+    w = component.w(a=a)
+    w_eff = component.w_eff(a=a)
+    with watch('stores'):
+        if variable == 0:
+            nongaussianity = realization_options(component)['nongaussianity']
+            work.fluid_from_mesh(component.ϱ, 0, ϱ_bar, nongaussianity)
+        else:
+            work.fluid_from_mesh(component.J[multi_index], 1, a**(1 - 3*w_eff)*ϱ_bar*(1 + w))
+    watch.finish()
+    return noise
+
+
+def realize(component, a, amplitudes, amplitudes_θ=None, **kw):
+    """Realise a component at scale factor a (realize, ic.py:297-364).  Particles go to
+    realize_particles(component, a, amplitudes, amplitudes_θ, **kw).  A fluid gets ϱ and, with
+    a Boltzmann order of 1 or more, J[0..2] (amplitudes_θ is then needed), all from one noise
+    slab generated and uploaded once; 𝒫 = c²wϱ follows (realize_approximative,
+    ic.py:495-511; w is constant here).  kw for a fluid: timings."""
+    if component.representation == 'particles':
+        return realize_particles(component, a, amplitudes, amplitudes_θ, **kw)
+    timings = kw.pop('timings', None)
+    if kw:
+        raise ConceptGPUError(f'{component.name}: realize() of a fluid component takes no '
+                              f'{sorted(kw)}')
+    with_J = component.boltzmann_order >= 1
+    if with_J and amplitudes_θ is None:
+        raise ConceptGPUError(f'{component.name}: J comes from the amplitudes of θ: pass '
+                              'amplitudes_θ')
+    noise = realize_fluid(component, a, amplitudes, 0, timings=timings)
+    if with_J:
+        for multi_index in range(3):
+            realize_fluid(component, a, amplitudes_θ, 1, multi_index, noise=noise, timings=timings)
+    # 𝒫 = ϱ·ℝ[light_speed**2*w] (ic.py:504-508)
+    torch.mul(component.ϱ, component.params.light_speed**2*component.w(a=a), out=component.𝒫)
+    return noise
+
+
+def _amplitudes_dev(component, amplitudes, gridsize, what='a lattice of {}³ particles'):
     amplitudes = np.ascontiguousarray(np.asarray(amplitudes, dtype=np.float64))
     k2_max = 3*(gridsize//2 - 1)**2
     if amplitudes.shape != (k2_max + 1,):
         raise ConceptGPUError(
-            f'{component.name}: {amplitudes.shape} amplitudes for a lattice of {gridsize}³ '
-            f'particles, which needs 3*(nyquist - 1)**2 + 1 = {k2_max + 1}')
+            f'{component.name}: {amplitudes.shape} amplitudes for {what.format(gridsize)}, '
+            f'which needs 3*(nyquist - 1)**2 + 1 = {k2_max + 1}')
     return torch.from_numpy(amplitudes).to(component.device)
 
 

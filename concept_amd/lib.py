@@ -162,6 +162,8 @@ SYMBOLS = {
     'cg_lpt_diff': (_int, [_vp, _vp, _int, _int, _dbl]),
     'cg_lpt_product': (_int, [_vp, _vp, _vp, _int, _dbl]),
     'cg_lpt_displace': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _dbl, _dbl]),
+    'cg_realize_grid': (_int, [_vp, _vp, _vp, _i64, _int, _int]),
+    'cg_fluid_from_mesh': (_int, [_vp, _vp, _int, _dbl, _dbl]),
     'cg_fluid_kt_step': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _dbl, _dbl,
                                 _dbl, _dbl, _dbl, _dbl, _dbl]),
 }

@@ -564,6 +564,26 @@ class PotentialMesh:
         check(_L.cg_lpt_displace(self._ctx, _ptr(pos), _ptr(mom), n, int(index_bgn), int(dim),
                                  float(pos_factor), float(mom_factor)))
 
+    def realize_grid(self, noise, amplitudes, tensor_rank=0, index0=0):
+        """realize_grid (ic.py:708-764) without a lattice shift: the Fourier content of `noise`
+        times amplitudes[k2] (rank 0), and for rank 1 times -i·k_index0/k², into this mesh."""
+        if (amplitudes.dtype != torch.float64 or amplitudes.device != self.device
+                or not amplitudes.is_contiguous() or amplitudes.dim() != 1):
+            raise lib.ConceptGPUError(
+                f'realize_grid(): amplitudes must be a contiguous 1D float64 tensor on '
+                f'{self.device}')
+        check(_L.cg_realize_grid(self._ctx, noise._ctx, _ptr(amplitudes), amplitudes.numel() - 1,
+                                 int(tensor_rank), int(index0)))
+        return self
+
+    def fluid_from_mesh(self, out, variable, c0, c1=0.0):
+        """This mesh's real-space content into the dense fluid grid `out` (this domain's
+        layers) as ϱ = c0·(1 + δ), δ += c1·δ² first when c1 ≠ 0 (variable 0), or as
+        J = u·c0 (variable 1): domain_decompose and ic.py:428-456 in one pass."""
+        self._check_fluid(out)
+        check(_L.cg_fluid_from_mesh(self._ctx, _ptr(out), int(variable), float(c0), float(c1)))
+        return out
+
     def render2D_project(self, axis, plane_bgn, plane_end, frac_bgn, frac_end, factor, out=None):
         """project_render2D (graphics.py:1374-1532) of this mesh's real-space values: the N x N
         image, in its final orientation, of this domain's part of the planes

@@ -863,6 +863,26 @@ int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double factor);
 int cg_lpt_displace(cg_ctx *psi, double *pos /*DEV or NULL*/, double *mom /*DEV or NULL*/,
                     int64_t n, int64_t index_bgn, int dim, double pos_factor, double mom_factor);
 
+/* --- initial conditions: fluid realisation (ic.py:400-477, 708-764) -----------------------
+ * cg_realize_grid: realize_grid (ic.py:708-764) without a lattice shift, for the scalar
+ *   (tensor_rank 0) and the vector (tensor_rank 1, component index0) structure, from the
+ *   Fourier view of `noise` into that of `out` (one grid size, one domain; out may be noise).
+ *   Every mode of fourier_loop(skip_origin=True): k2 = (kj^2 + ki^2) + kk^2,
+ *   amplitude = amplitudes[k2]; rank 1: amplitude *= ((-boxsize/(2*pi))*k_index0)/k2 and
+ *   (re, im) -> (-im, re) (K = -i k/k^2, ic.py:732-742); out = (amplitude*re, amplitude*im).
+ *   The origin and the three Nyquist planes are written as 0 (nullify_modes, ic.py:764).
+ *   amplitudes: DEV double[k2_max + 1], k2_max = 3*(N/2 - 1)^2.
+ * cg_fluid_from_mesh: domain_decompose (ic.py:418) and the transformation to the variable of
+ *   the fluid equations (ic.py:428-456) in one pass over the real-space content of `mesh` (as
+ *   cg_poisson_backward leaves it): cell (x, j, k) of this domain's nxl layers, read from the
+ *   padded rows (the padding is never read), lands at out[(x*N + j)*N + k].
+ *   mode 0 (rho): value += c1*value^2 when c1 != 0 (f_NL, ic.py:436), out = c0*(1 + value),
+ *   c0 = rho_bar; mode 1 (J): out = value*c0, c0 = a^(1 - 3 w_eff)*rho_bar*(1 + w) (ic.py:456).
+ *   Every product and sum is rounded on its own.  out: DEV double[nxl*N*N], 16-byte aligned. */
+int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitudes /*DEV k2_max + 1*/,
+                    int64_t k2_max, int tensor_rank, int index0);
+int cg_fluid_from_mesh(cg_ctx *mesh, double *out /*DEV nxl*N*N*/, int mode, double c0, double c1);
+
 /* --- debug fetch (parity tests) -------------------------------------------- */
 int cg_fetch(cg_ctx *ctx, int which, double *out /*HOST*/, int64_t n_doubles);
 /* CIC cell indices exactly as set_weights_CIC returns them for the deposit
