@@ -427,7 +427,8 @@ static int ctx_init(cg_ctx *c) {
     return 0;
 }
 
-// (the buffers go with the context, after the plans that use them)
+// (the buffers go with the context, after the plans that use them; a deferred sub-step pass
+// that nothing has launched is dropped: it holds pointers to arrays the caller may have freed)
 extern "C" int cg_destroy(cg_ctx *c) {
     if (!c) return 0;
     dist_plans_destroy(c);
@@ -455,14 +456,14 @@ extern "C" int cg_destroy(cg_ctx *c) {
 }
 
 extern "C" int cg_set_stream(cg_ctx *c, void *s) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WHOLE_CONTEXT(c);
     CG_CHECK(c, "cg_set_stream: null context");
     c->stream = (hipStream_t)s;
     return 0;
 }
 
 extern "C" int cg_synchronize(cg_ctx *c) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WHOLE_CONTEXT(c);
     CG_CHECK(c, "cg_synchronize: null context");
     CG_HIP(hipStreamSynchronize(c->stream));
     return 0;
@@ -479,8 +480,8 @@ extern "C" int cg_error_flags(cg_ctx *c, uint32_t *flags_out) {
 }
 
 extern "C" int cg_prepare_invalidate(cg_ctx *c) {
+    CG_WRITES_PARTICLES(c);  // (the caller's word that pos or mom were written outside the library)
     CG_CHECK(c, "cg_prepare_invalidate: null context");
-    c->prep_valid = false;
     return 0;
 }
 
@@ -491,7 +492,7 @@ extern "C" int cg_mesh_zero(cg_ctx *c) {
 }
 
 extern "C" int cg_deposit_cic(cg_ctx *c, const double *pos, int64_t n, double contribution) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (pos || n == 0), "cg_deposit_cic: null argument");
     CG_CHECK(n >= 0, "cg_deposit_cic: negative particle count");
     if (n == 0) return 0;
@@ -505,6 +506,40 @@ extern "C" int cg_deposit_cic(cg_ctx *c, const double *pos, int64_t n, double co
 // buffer bound with cg_dist_bind_fourier on x-slab domains
 #define CG_FOURIER(c, name) \
     CG_CHECK((c)->four != nullptr, name ": no Fourier buffer bound (cg_dist_bind_fourier)")
+
+// ---- argument checks that several entries share: the messages begin with the entry's `name` ----
+// the gather-kick kernels: the orders built, and the ghost layers their stencil reaches into
+static int diff_order_checks(const char *name, const cg_ctx *c, int diff_order) {
+    CG_CHECK(diff_order == 2 || diff_order == 4,
+             "%s: differentiation order %d not built (2 and 4 are)", name, diff_order);
+    CG_CHECK((diff_order + 1) / 2 <= c->p.nghosts,
+             "%s: differentiation order %d needs nghosts >= %d (commons.py:4411-4432)", name,
+             diff_order, (diff_order + 1) / 2);
+    return 0;
+}
+// a short-range list of n particles over nt tiles across the box.  nt_max: its bins are counted
+// in 32 bits, 2^30 of them at the most — 8 nt^3 half-tile cells (512) or nt^3 tiles (1024)
+static int tiling_checks(const char *name, const cg_ctx *c, int64_t n, int64_t nt, int64_t nt_max,
+                         double tile_extent) {
+    CG_CHECK(nt >= 4, "The global gravity tiling needs to have at least 4 tiles across the box in "
+                      "every direction (species.py:3971); got %lld", (long long)nt);
+    CG_CHECK(nt <= nt_max && n < (1ll << 32), "%s: size out of range", name);
+    // the sweeps take the tile extent from the box (species.py:607-609): a list made with another
+    // one would put a particle on a tile border into one tile here and into its neighbour there.
+    // The list is made with boxsize/nt itself; the argument only has to agree with it (4 ulp: a
+    // caller may have formed it as boxsize*(1/nt)).
+    const double ext = c->p.boxsize / (double)nt;
+    CG_CHECK(fabs(tile_extent - ext) <= 4 * kMachineEps * ext,
+             "%s: tile_extent must be boxsize/nt (%.17g), got %.17g", name, ext, tile_extent);
+    return 0;
+}
+// N_rungs: int8 rungs and jump codes (up to 3 N_rungs - 1) take 42; a rung table that goes to its
+// kernel by value takes 3 N_rungs - 1 <= CG_RUNG_TABLE_MAX entries
+static int n_rungs_checks(const char *name, int N_rungs, bool by_value) {
+    CG_CHECK(N_rungs >= 1 && (by_value ? 3 * N_rungs - 1 <= CG_RUNG_TABLE_MAX : N_rungs <= 42),
+             "%s: N_rungs = %d", name, N_rungs);
+    return 0;
+}
 
 extern "C" int cg_fluid_add(cg_ctx *c, const double *fluid, double factor, int op_add) {
     CG_CHECK(c && fluid, "cg_fluid_add: null argument");
@@ -585,7 +620,7 @@ extern "C" int cg_copy_modes_unpack(cg_ctx *onto, cg_ctx *from, int64_t n_small,
 
 extern "C" int cg_deposit(cg_ctx *c, const double *pos, int64_t n, double contribution, int order,
                           const double *shift) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (pos || n == 0), "cg_deposit: null argument");
     CG_CHECK(order >= 1 && order <= 4,
              "interpolate_particles() called with order = %d not in {1 (NGP), 2 (CIC), 3 (TSC), 4 (PCS)}",
@@ -597,7 +632,7 @@ extern "C" int cg_deposit(cg_ctx *c, const double *pos, int64_t n, double contri
 
 extern "C" int cg_gather_scalar(cg_ctx *c, const double *pos, double *mom, int64_t n, int dim,
                                 int order, const double *shift, double factor) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && ((pos && mom) || n == 0), "cg_gather_scalar: null argument");
     CG_CHECK(order >= 1 && order <= 4,
              "interpolate_domaingrid_to_particles() called with order = %d not in {1, 2, 3, 4}",
@@ -605,7 +640,6 @@ extern "C" int cg_gather_scalar(cg_ctx *c, const double *pos, double *mom, int64
     CG_CHECK(dim >= 0 && dim < 3,
              "apply_particle_mesh_force() called with dim = %d not in {0, 1, 2}", dim);
     double cellsize = c->p.boxsize / (double)c->p.gridsize;  // mesh.py:408 (one domain)
-    c->prep_valid = false;
     return cgk_gather_scalar(c, pos, mom, n, dim, order,
                              make_geom_shift(cellsize, c->p.nghosts, c->p.cell_centered, shift, +1),
                              factor);
@@ -637,7 +671,7 @@ extern "C" int cg_pp_kick(cg_ctx *c, const double *pos_r, int64_t n_r, double *d
                           int ewald_gridsize, double softening, int kernel, double factor,
                           const double *factors, const signed char *rung,
                           const signed char *rung_jumped, int lowest_active) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && ((pos_r && dmom_r) || n_r == 0) && (pos_s || n_s == 0),
              "cg_pp_kick: null argument");
     CG_CHECK(kernel >= 0 && kernel <= 2, "Softening kernel %d not understood", kernel);
@@ -742,30 +776,24 @@ extern "C" int cg_poisson_solve_timed(cg_ctx *c, int deconv_order, double C, int
 
 extern "C" int cg_gather_kick(cg_ctx *c, const double *pos, double *mom, int64_t n, int diff_order,
                               double factor) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && ((pos && mom) || n == 0), "cg_gather_kick: null argument");
-    CG_CHECK(diff_order == 2 || diff_order == 4,
-             "cg_gather_kick: differentiation order %d not built (2 and 4 are)", diff_order);
-    CG_CHECK((diff_order + 1) / 2 <= c->p.nghosts,
-             "cg_gather_kick: differentiation order %d needs nghosts >= %d (commons.py:4411-4432)",
-             diff_order, (diff_order + 1) / 2);
+    if (diff_order_checks("cg_gather_kick", c, diff_order)) return 1;
     if (n == 0) return 0;
-    c->prep_valid = false;
     return cgk_gather_kick(c, pos, mom, n, diff_order, factor);
 }
 
 extern "C" int cg_drift(cg_ctx *c, double *pos, const double *mom, int64_t n,
                         double dt_over_mass) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && ((pos && mom) || n == 0), "cg_drift: null argument");
     if (n == 0) return 0;
-    c->prep_valid = false;
     return cgk_drift(c, pos, mom, n, dt_over_mass);
 }
 
 extern "C" int cg_measure_momentum(cg_ctx *c, const double *mom, int64_t n, double *out,
                                    double *scratch) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && out && scratch && (mom || n == 0), "cg_measure_momentum: null argument");
     CG_CHECK(n >= 0, "cg_measure_momentum: n out of range");
     return cgk_measure_mom(c, mom, n, out, scratch);
@@ -773,6 +801,7 @@ extern "C" int cg_measure_momentum(cg_ctx *c, const double *mom, int64_t n, doub
 
 extern "C" int cg_measure_momentum_regions(cg_ctx *c, const double *mom, const uint32_t *start,
                                            const uint32_t *count, double *out, double *scratch) {
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && mom && start && out && scratch, "cg_measure_momentum_regions: null argument");
     return cgk_measure_mom_regions(c, mom, start, count, out, scratch);
 }
@@ -788,7 +817,7 @@ extern "C" int cg_tile_info(const cg_ctx *c, int64_t info[3]) {
 extern "C" int cg_deposit_cic_tiled(cg_ctx *c, const double *pos, int64_t n,
                                     const uint32_t *tile_offset, double contribution,
                                     int accumulate) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && tile_offset && (pos || n == 0), "cg_deposit_cic_tiled: null argument");
     CG_CHECK(n >= 0 && n < (1ll << 32), "cg_deposit_cic_tiled: n out of range");
     return cgk_deposit_cic_tiled(c, pos, n, tile_offset, nullptr, contribution, accumulate);
@@ -797,6 +826,7 @@ extern "C" int cg_deposit_cic_tiled(cg_ctx *c, const double *pos, int64_t n,
 extern "C" int cg_deposit_cic_regions(cg_ctx *c, const double *pos, const uint32_t *start,
                                       const uint32_t *count, double contribution,
                                       int accumulate) {
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && pos && start && count, "cg_deposit_cic_regions: null argument");
     return cgk_deposit_cic_tiled(c, pos, 0, start, count, contribution, accumulate);
 }
@@ -831,6 +861,7 @@ extern "C" int cg_gather_kick_drift_scatter(
     int64_t *ids_out, const uint32_t *start_out, uint32_t *count_out, int diff_order,
     double factor, double dt_over_mass, const int64_t *aux_in, int64_t *aux_out,
     int64_t out_capacity) {
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && pos_in && mom_in && start_in && pos_out && mom_out && start_out && count_out,
              "cg_gather_kick_drift_scatter: null argument");
     CG_CHECK(pos_in != pos_out && mom_in != mom_out,
@@ -839,31 +870,22 @@ extern "C" int cg_gather_kick_drift_scatter(
              "cg_gather_kick_drift_scatter: ids_in and ids_out must both be given or both be null");
     CG_CHECK((aux_in == nullptr) == (aux_out == nullptr),
              "cg_gather_kick_drift_scatter: aux_in and aux_out must both be given or both be null");
-    CG_CHECK(diff_order == 2 || diff_order == 4,
-             "cg_gather_kick_drift_scatter: differentiation order %d not built", diff_order);
-    CG_CHECK((diff_order + 1) / 2 <= c->p.nghosts,
-             "cg_gather_kick_drift_scatter: differentiation order %d needs nghosts >= %d",
-             diff_order, (diff_order + 1) / 2);
+    if (diff_order_checks("cg_gather_kick_drift_scatter", c, diff_order)) return 1;
     CG_CHECK(c->p.nprocs == 1 || c->emig_rows,
              "cg_gather_kick_drift_scatter: on x-slab domains the particles leaving the slab need "
              "a row buffer (cg_set_emigrant_rows)");
     CG_CHECK(out_capacity > 0, "cg_gather_kick_drift_scatter: out_capacity must be positive");
     FusedScatter fs{count_in, start_out, count_out, pos_out, mom_out, ids_in, ids_out,
                     aux_in, aux_out, out_capacity};
-    c->prep_valid = false;
     return cgk_gather_kick_tiled(c, pos_in, const_cast<double *>(mom_in), 0, start_in, diff_order,
                                  factor, 0, dt_over_mass, &fs);
 }
 
 extern "C" int cg_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, int64_t n,
                                     const uint32_t *tile_offset, int diff_order, double factor) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && tile_offset && ((pos && mom) || n == 0), "cg_gather_kick_tiled: null argument");
-    CG_CHECK(diff_order == 2 || diff_order == 4,
-             "cg_gather_kick_tiled: differentiation order %d not built (2 and 4 are)", diff_order);
-    CG_CHECK((diff_order + 1) / 2 <= c->p.nghosts,
-             "cg_gather_kick_tiled: differentiation order %d needs nghosts >= %d "
-             "(commons.py:4411-4432)", diff_order, (diff_order + 1) / 2);
+    if (diff_order_checks("cg_gather_kick_tiled", c, diff_order)) return 1;
     if (n == 0) return 0;
     return cgk_gather_kick_tiled(c, pos, mom, n, tile_offset, diff_order, factor, 0, 0.0);
 }
@@ -871,14 +893,10 @@ extern "C" int cg_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i
 extern "C" int cg_gather_kick_tiled_prepare(cg_ctx *c, const double *pos, double *mom, int64_t n,
                                             const uint32_t *tile_offset, int diff_order,
                                             double factor, double next_dt_over_mass) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES(c);  // (what the pass prepares is valid from its end on)
     CG_CHECK(c && tile_offset && ((pos && mom) || n == 0),
              "cg_gather_kick_tiled_prepare: null argument");
-    CG_CHECK(diff_order == 2 || diff_order == 4,
-             "cg_gather_kick_tiled_prepare: differentiation order %d not built", diff_order);
-    CG_CHECK((diff_order + 1) / 2 <= c->p.nghosts,
-             "cg_gather_kick_tiled_prepare: differentiation order %d needs nghosts >= %d",
-             diff_order, (diff_order + 1) / 2);
+    if (diff_order_checks("cg_gather_kick_tiled_prepare", c, diff_order)) return 1;
     if (n == 0) return 0;
     return cgk_gather_kick_tiled(c, pos, mom, n, tile_offset, diff_order, factor, 1,
                                  next_dt_over_mass);
@@ -912,6 +930,7 @@ extern "C" int cg_set_momentum_sum(cg_ctx *c, double *sum_out) {
 
 extern "C" int cg_emigrant_rows_dest(cg_ctx *c, const double *rows, const uint32_t *count,
                                      int64_t cap, int32_t *dest, int32_t *send_counts) {
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && send_counts && (cap == 0 || (rows && count && dest)),
              "cg_emigrant_rows_dest: null argument");
     return cgk_emigrant_rows_dest(c, rows, count, cap, dest, send_counts);
@@ -920,6 +939,7 @@ extern "C" int cg_emigrant_rows_dest(cg_ctx *c, const double *rows, const uint32
 extern "C" int cg_region_insert(cg_ctx *c, const double *rows, int64_t m, const uint32_t *start,
                                 uint32_t *count, double *pos_out, double *mom_out,
                                 int64_t *ids_out, int64_t *aux_out, int64_t capacity) {
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && start && count && pos_out && mom_out && (m == 0 || rows),
              "cg_region_insert: null argument");
     CG_CHECK(m >= 0, "cg_region_insert: negative row count");
@@ -927,54 +947,56 @@ extern "C" int cg_region_insert(cg_ctx *c, const double *rows, int64_t m, const 
                              capacity);
 }
 
+// cg_sort_particles (drift = 0) and cg_drift_sort behind their gates
+static int sort_entry(const char *name, cg_ctx *c, const double *pos_in, const double *mom_in,
+                      const int64_t *ids_in, double *pos_out, double *mom_out, int64_t *ids_out,
+                      int64_t n, uint32_t *tile_offset_out, int drift, double dt_over_mass) {
+    // (an empty set — a domain without particles — may come with null arrays)
+    CG_CHECK(c && tile_offset_out && (n == 0 || (pos_in && mom_in && pos_out && mom_out)),
+             "%s: null argument", name);
+    CG_CHECK(n == 0 || (pos_in != pos_out && mom_in != mom_out), "%s: in/out must not alias", name);
+    CG_CHECK(n == 0 || (ids_in == nullptr) == (ids_out == nullptr),
+             "%s: ids_in and ids_out must both be given or both be null", name);
+    CG_CHECK(n >= 0 && n < (1ll << 32), "%s: n out of range", name);
+    // x-slab domains: particles whose drifted position leaves the slab are dropped (the host
+    // ships them beforehand: cg_owner_rank_drifted + exchange + cg_prepare_rebind)
+    // a histogram prepared by cg_gather_kick_tiled_prepare for exactly these arrays and this
+    // drift replaces the first pass.  An entry that writes pos or mom in between voids it
+    // (CG_WRITES_PARTICLES); a write outside the library is the caller's (cg_prepare_invalidate)
+    int use_prepared = drift && c->prep_valid && c->prep_pos == pos_in && c->prep_mom == mom_in &&
+                       c->prep_n == n && c->prep_dtm == dt_over_mass;
+    return cgk_sort(c, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n, tile_offset_out,
+                    drift, dt_over_mass, use_prepared);
+}
+
+// (read-kind both: the copies are the sort's own, and cgk_sort consumes or voids what was prepared)
 extern "C" int cg_sort_particles(cg_ctx *c, const double *pos_in, const double *mom_in,
                                  const int64_t *ids_in, double *pos_out, double *mom_out,
                                  int64_t *ids_out, int64_t n, uint32_t *tile_offset_out) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
-    // (an empty set — a domain without particles — may come with null arrays)
-    CG_CHECK(c && tile_offset_out && (n == 0 || (pos_in && mom_in && pos_out && mom_out)),
-             "cg_sort_particles: null argument");
-    CG_CHECK(n == 0 || (pos_in != pos_out && mom_in != mom_out),
-             "cg_sort_particles: in/out must not alias");
-    CG_CHECK(n == 0 || (ids_in == nullptr) == (ids_out == nullptr),
-             "cg_sort_particles: ids_in and ids_out must both be given or both be null");
-    CG_CHECK(n >= 0 && n < (1ll << 32), "cg_sort_particles: n out of range");
-    return cgk_sort(c, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n, tile_offset_out, 0,
-                    0.0, 0);
+    CG_READS_PARTICLES(c);
+    return sort_entry("cg_sort_particles", c, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n,
+                      tile_offset_out, 0, 0.0);
 }
 
 extern "C" int cg_drift_sort(cg_ctx *c, const double *pos_in, const double *mom_in,
                              const int64_t *ids_in, double *pos_out, double *mom_out,
                              int64_t *ids_out, int64_t n, double dt_over_mass,
                              uint32_t *tile_offset_out) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
-    CG_CHECK(c && tile_offset_out && (n == 0 || (pos_in && mom_in && pos_out && mom_out)),
-             "cg_drift_sort: null argument");
-    CG_CHECK(n == 0 || (pos_in != pos_out && mom_in != mom_out),
-             "cg_drift_sort: in/out must not alias");
-    CG_CHECK(n == 0 || (ids_in == nullptr) == (ids_out == nullptr),
-             "cg_drift_sort: ids_in and ids_out must both be given or both be null");
-    CG_CHECK(n >= 0 && n < (1ll << 32), "cg_drift_sort: n out of range");
-    // x-slab domains: particles whose drifted position leaves the slab are dropped (the host
-    // ships them beforehand: cg_owner_rank_drifted + exchange + cg_prepare_rebind)
-    // a histogram prepared by cg_gather_kick_tiled_prepare for exactly these arrays and this
-    // drift replaces the first pass (anything else touching pos/mom in between is a caller bug
-    // the pointers cannot reveal: the prepared state is consumed by the very next sort only)
-    int use_prepared = c->prep_valid && c->prep_pos == pos_in && c->prep_mom == mom_in &&
-                       c->prep_n == n && c->prep_dtm == dt_over_mass;
-    return cgk_sort(c, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n, tile_offset_out, 1,
-                    dt_over_mass, use_prepared);
+    CG_READS_PARTICLES(c);
+    return sort_entry("cg_drift_sort", c, pos_in, mom_in, ids_in, pos_out, mom_out, ids_out, n,
+                      tile_offset_out, 1, dt_over_mass);
 }
 
 extern "C" int cg_owner_rank_drifted(cg_ctx *c, const double *pos, const double *mom, int64_t n,
                                      double dt_over_mass, int32_t *owner) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (n == 0 || (pos && mom && owner)), "cg_owner_rank_drifted: null argument");
     return cgk_owner_rank_drifted(c, pos, mom, n, dt_over_mass, owner);
 }
 
 extern "C" int cg_prepare_rebind(cg_ctx *c, const double *pos, const double *mom, int64_t n_total,
                                  const double *add_pos, const double *add_mom, int64_t n_add) {
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (n_total == 0 || (pos && mom)) && (n_add == 0 || (add_pos && add_mom)),
              "cg_prepare_rebind: null argument");
     CG_CHECK(n_total >= 0 && n_add >= 0 && n_total < (1ll << 32), "cg_prepare_rebind: sizes");
@@ -983,36 +1005,19 @@ extern "C" int cg_prepare_rebind(cg_ctx *c, const double *pos, const double *mom
 
 extern "C" int cg_cic_indices(cg_ctx *c, const double *pos, int64_t n, int for_gather,
                               int64_t *idx_out) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (n == 0 || (pos && idx_out)), "cg_cic_indices: null argument");
     if (n == 0) return 0;
     return cgk_cic_indices(c, pos, n, for_gather, idx_out);
 }
 
-static int shortrange_cells_checks(cg_ctx *c, const void *pos, int64_t n, int64_t nt,
-                                   double tile_extent, const void *order_out,
-                                   const void *offset_out, const void *pos_sorted_out) {
-    CG_CHECK(c && offset_out && (n == 0 || (pos && order_out && pos_sorted_out)),
-             "cg_shortrange_cells: null argument");
-    CG_CHECK(nt >= 4, "The global gravity tiling needs to have at least 4 tiles across the box in "
-                      "every direction (species.py:3971); got %lld", (long long)nt);
-    CG_CHECK(nt <= 512 && n < (1ll << 32), "cg_shortrange_cells: size out of range");
-    // the sweeps take the tile extent from the box (species.py:607-609): a list made with another
-    // one would put a particle on a tile border into one tile here and into its neighbour there.
-    // The list is made with boxsize/nt itself; the argument only has to agree with it (4 ulp: a
-    // caller may have formed it as boxsize*(1/nt)).
-    const double ext = c->p.boxsize / (double)nt;
-    CG_CHECK(fabs(tile_extent - ext) <= 4 * 2.220446049250313e-16 * ext,
-             "cg_shortrange_cells: tile_extent must be boxsize/nt (%.17g), got %.17g", ext,
-             tile_extent);
-    return 0;
-}
-
 extern "C" int cg_shortrange_cells(cg_ctx *c, const double *pos, int64_t n, int64_t nt,
                                    double tile_extent, uint32_t *order_out,
                                    uint32_t *offset_out, double *pos_sorted_out) {
-    if (shortrange_cells_checks(c, pos, n, nt, tile_extent, order_out, offset_out, pos_sorted_out))
-        return 1;
+    CG_ADOPTS_PENDING_PASS(c);
+    CG_CHECK(c && offset_out && (n == 0 || (pos && order_out && pos_sorted_out)),
+             "cg_shortrange_cells: null argument");
+    if (tiling_checks("cg_shortrange_cells", c, n, nt, 512, tile_extent)) return 1;
     return cgk_shortrange_cells(c, pos, n, nt, c->p.boxsize / (double)nt, order_out, offset_out,
                                 pos_sorted_out, nullptr, nullptr, 0, nullptr, nullptr);
 }
@@ -1023,10 +1028,12 @@ extern "C" int cg_shortrange_cells_rungs(cg_ctx *c, const double *pos, int64_t n
                                          uint32_t *order_out, uint32_t *offset_out,
                                          double *pos_sorted_out, uint32_t *nact_out,
                                          int8_t *rung_jumped_sorted_out) {
-    if (shortrange_cells_checks(c, pos, n, nt, tile_extent, order_out, offset_out, pos_sorted_out))
-        return 1;
-    CG_CHECK(nact_out && (n == 0 || (rung && (rung_jumped || !rung_jumped_sorted_out))),
+    CG_ADOPTS_PENDING_PASS(c);
+    CG_CHECK(c && offset_out && nact_out &&
+                 (n == 0 || (pos && order_out && pos_sorted_out && rung &&
+                             (rung_jumped || !rung_jumped_sorted_out))),
              "cg_shortrange_cells_rungs: null argument");
+    if (tiling_checks("cg_shortrange_cells_rungs", c, n, nt, 512, tile_extent)) return 1;
     return cgk_shortrange_cells(c, pos, n, nt, c->p.boxsize / (double)nt, order_out, offset_out,
                                 pos_sorted_out, (const signed char *)rung,
                                 (const signed char *)rung_jumped, lowest_active_rung, nact_out,
@@ -1058,7 +1065,7 @@ extern "C" int cg_shortrange_sweep_cells(cg_ctx *c, const double *pos_r_sorted,
                                          const uint32_t *offset_s, int64_t nt,
                                          const double *table, int64_t tablesize,
                                          double r2_index_scaling, double r2_max, double factor) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     if (sweep_cells_checks(c, pos_r_sorted, order_r, offset_r, dmom_r, pos_s_sorted, offset_s,
                            table, nt, tablesize, r2_index_scaling, r2_max))
         return 1;
@@ -1073,7 +1080,7 @@ extern "C" int cg_shortrange_sweep_cells_rungs(
     const double *table, int64_t tablesize, double r2_index_scaling, double r2_max,
     const double *factors, const int8_t *rung_r, const int8_t *rung_jumped_r,
     int lowest_active_rung) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     if (sweep_cells_checks(c, pos_r_sorted, order_r, offset_r, dmom_r, pos_s_sorted, offset_s,
                            table, nt, tablesize, r2_index_scaling, r2_max))
         return 1;
@@ -1093,7 +1100,7 @@ extern "C" int cg_shortrange_sweep_cells_active(
     int64_t tablesize, double r2_index_scaling, double r2_max, const double *factors,
     const int8_t *rung_r, const int8_t *rung_jumped_r, int lowest_active_rung,
     int64_t n_active_max) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     if (sweep_cells_checks(c, pos_r_sorted, order_r, offset_r, dmom_r, pos_s_sorted, offset_s,
                            table, nt, tablesize, r2_index_scaling, r2_max))
         return 1;
@@ -1128,39 +1135,31 @@ extern "C" int cg_shortrange_tiles(cg_ctx *c, const double *pos, int64_t n, int6
                                    double tile_extent, const int8_t *rung,
                                    int lowest_active_rung, uint32_t *order_out,
                                    uint32_t *offset_out, double *pos_sorted_out) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && offset_out && (n == 0 || (pos && order_out)),
              "cg_shortrange_tiles: null argument");
-    CG_CHECK(nt >= 4, "The global gravity tiling needs to have at least 4 tiles across the box in "
-                      "every direction (species.py:3971); got %lld", (long long)nt);
-    CG_CHECK(nt <= 1024 && n < (1ll << 32), "cg_shortrange_tiles: size out of range");
-    CG_CHECK(fabs(tile_extent - c->p.boxsize / (double)nt) <=
-                 4 * 2.220446049250313e-16 * (c->p.boxsize / (double)nt),
-             "cg_shortrange_tiles: tile_extent must be boxsize/nt (%.17g), got %.17g",
-             c->p.boxsize / (double)nt, tile_extent);
-    tile_extent = c->p.boxsize / (double)nt;
-    return cgk_shortrange_tiles(c, pos, n, nt, tile_extent, (const signed char *)rung,
+    if (tiling_checks("cg_shortrange_tiles", c, n, nt, 1024, tile_extent)) return 1;
+    return cgk_shortrange_tiles(c, pos, n, nt, c->p.boxsize / (double)nt, (const signed char *)rung,
                                 lowest_active_rung, order_out, offset_out, pos_sorted_out);
 }
 
 extern "C" int cg_dmom_nullify(cg_ctx *c, double *dmom, const int8_t *rung, int64_t n,
                                int lowest_active_rung) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (dmom || n == 0), "cg_dmom_nullify: null argument");
     return cgk_dmom_active(c, nullptr, dmom, (const signed char *)rung, n, lowest_active_rung, 0);
 }
 extern "C" int cg_dmom_apply(cg_ctx *c, double *mom, const double *dmom, const int8_t *rung,
                              int64_t n, int lowest_active_rung) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES(c);
     CG_CHECK(c && ((mom && dmom) || n == 0), "cg_dmom_apply: null argument");
-    c->prep_valid = false;  // mom changes: a prepared drift histogram no longer describes it
     return cgk_dmom_active(c, mom, (double *)dmom, (const signed char *)rung, n,
                            lowest_active_rung, 1);
 }
 extern "C" int cg_dmom_to_acc(cg_ctx *c, double *dmom, const int8_t *rung,
                               const int8_t *rung_jumped, int64_t n, int lowest_active_rung,
                               const double *conversion_factors, int any_rung_jumps) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && conversion_factors && ((dmom && rung && rung_jumped) || n == 0),
              "cg_dmom_to_acc: null argument");
     return cgk_dmom_to_acc(c, dmom, (const signed char *)rung, (const signed char *)rung_jumped, n,
@@ -1168,9 +1167,9 @@ extern "C" int cg_dmom_to_acc(cg_ctx *c, double *dmom, const int8_t *rung,
 }
 extern "C" int cg_assign_rungs(cg_ctx *c, const double *acc, int8_t *rung, int8_t *rung_jumped,
                                int64_t n, double rung_factor, int N_rungs) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && ((acc && rung && rung_jumped) || n == 0), "cg_assign_rungs: null argument");
-    CG_CHECK(N_rungs >= 1 && N_rungs <= 42, "cg_assign_rungs: N_rungs = %d", N_rungs);
+    if (n_rungs_checks("cg_assign_rungs", N_rungs, false)) return 1;
     return cgk_assign_rungs(c, acc, (signed char *)rung, (signed char *)rung_jumped, n, rung_factor,
                             N_rungs);
 }
@@ -1178,24 +1177,24 @@ extern "C" int cg_flag_rung_jumps(cg_ctx *c, const double *acc, const int8_t *ru
                                   int8_t *rung_jumped, int64_t n, int lowest_active_rung,
                                   const double *integrals_1, double rung_factor_up,
                                   double rung_factor_down, int N_rungs, int32_t *any_out) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && integrals_1 && any_out && ((acc && rung && rung_jumped) || n == 0),
              "cg_flag_rung_jumps: null argument");
-    CG_CHECK(N_rungs >= 1 && N_rungs <= 42, "cg_flag_rung_jumps: N_rungs = %d", N_rungs);
+    if (n_rungs_checks("cg_flag_rung_jumps", N_rungs, false)) return 1;
     return cgk_flag_rung_jumps(c, acc, (const signed char *)rung, (signed char *)rung_jumped, n,
                                lowest_active_rung, integrals_1, rung_factor_up, rung_factor_down,
                                N_rungs, any_out);
 }
 extern "C" int cg_apply_rung_jumps(cg_ctx *c, int8_t *rung, int8_t *rung_jumped, int64_t n,
                                    int N_rungs) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && ((rung && rung_jumped) || n == 0), "cg_apply_rung_jumps: null argument");
     return cgk_apply_rung_jumps(c, (signed char *)rung, (signed char *)rung_jumped, n, N_rungs);
 }
 
 extern "C" int cg_permute_rows(cg_ctx *c, const int64_t *perm, int64_t n, int ncols,
                                const void *const *src, void *const *dst, const int *row_bytes) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && ncols >= 0 && (n == 0 || ncols == 0 || (perm && src && dst && row_bytes)),
              "cg_permute_rows: null argument");
     for (int k = 0; k < ncols && n > 0; k++) {
@@ -1214,12 +1213,12 @@ extern "C" int cg_substep_begin(cg_ctx *c, double *pos, const double *mom, doubl
                                 const double *integrals_1, double rung_factor_up,
                                 double rung_factor_down, int N_rungs, int32_t *any_out,
                                 int64_t *counts_after, int defer) {
+    // (no gate, this is the pass: cgk_substep_begin flushes an earlier one and voids the histogram)
     CG_CHECK(c && (n == 0 || ((!do_drift || (pos && mom)) &&
                               (!do_flag || (dmom && rung && rung_jumped)))) &&
                  (!do_flag || (integrals_1 && any_out)),
              "cg_substep_begin: null argument");
-    CG_CHECK(N_rungs >= 1 && 3 * N_rungs - 1 <= CG_RUNG_TABLE_MAX, "cg_substep_begin: N_rungs = %d",
-             N_rungs);
+    if (n_rungs_checks("cg_substep_begin", N_rungs, true)) return 1;
     return cgk_substep_begin(c, pos, mom, dmom, (const signed char *)rung,
                              (signed char *)rung_jumped, n, do_drift, dt_over_mass, do_flag,
                              lowest_active_rung, integrals_1, rung_factor_up, rung_factor_down,
@@ -1233,12 +1232,11 @@ extern "C" int cg_substep_end(cg_ctx *c, double *mom, double *dmom, int8_t *rung
                               int8_t *rung_jumped, int64_t n, int do_apply,
                               int lowest_active_rung, const double *conversion_factors,
                               int N_rungs, int64_t *counts) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_WRITES_PARTICLES_IF(c, do_apply != 0);  // (mom += Δmom)
     CG_CHECK(c && (n == 0 || (rung && rung_jumped && (!do_apply || (mom && dmom)))) &&
                  (!do_apply || conversion_factors),
              "cg_substep_end: null argument");
-    CG_CHECK(N_rungs >= 1 && 3 * N_rungs - 1 <= CG_RUNG_TABLE_MAX, "cg_substep_end: N_rungs = %d",
-             N_rungs);
+    if (n_rungs_checks("cg_substep_end", N_rungs, true)) return 1;
     return cgk_substep_end(c, mom, dmom, (signed char *)rung, (signed char *)rung_jumped, n,
                            do_apply, lowest_active_rung, conversion_factors, N_rungs,
                            (long long *)counts);
@@ -1249,7 +1247,7 @@ extern "C" int cg_shortrange_sparse(cg_ctx *c, const double *pos_r, const int64_
                                    const double *table, int64_t tablesize,
                                    double r2_index_scaling, double r2_max, double factor,
                                    const double *factors, const int8_t *rung_jumped) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && pos_r && active && dmom_r && table && (pos_s || n_s == 0),
              "cg_shortrange_sparse: null argument");
     CG_CHECK(tablesize >= 2 && (double)(tablesize - 1) >= r2_max * r2_index_scaling,
@@ -1265,7 +1263,7 @@ extern "C" int cg_shortrange_sparse(cg_ctx *c, const double *pos_r, const int64_
 
 extern "C" int cg_rung_populations(cg_ctx *c, const int8_t *rung, int64_t n, int N_rungs,
                                    int64_t *counts) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && counts && (rung || n == 0), "cg_rung_populations: null argument");
     CG_CHECK(N_rungs >= 1 && N_rungs <= 64, "cg_rung_populations: N_rungs out of range");
     return cgk_rung_populations(c, (const signed char *)rung, n, N_rungs, (long long *)counts);
@@ -1349,6 +1347,7 @@ extern "C" int cg_dist_fft_x(cg_ctx *c, double *buf, int inverse) {
 extern "C" int cg_emigrant_dest(cg_ctx *c, const double *pos, const double *mom,
                                 const int64_t *idx, const uint32_t *count, int64_t cap,
                                 double dt_over_mass, int32_t *dest, int32_t *send_counts) {
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && send_counts && (cap == 0 || (pos && mom && idx && count && dest)),
              "cg_emigrant_dest: null argument");
     return cgk_emigrant_dest(c, pos, mom, idx, count, cap, dt_over_mass, dest, send_counts);
@@ -1366,7 +1365,7 @@ extern "C" int cg_dist_fft_backward_layers(cg_ctx *c, const double *recv_buf, in
     return dist_fft(c, SlabOp::ZYBackward, recv_buf, 0, 0.0, 0, 0.0, layer0, nlayers);
 }
 extern "C" int cg_owner_rank(cg_ctx *c, const double *pos, int64_t n, int32_t *owner_out) {
-    if (c && cgk_substep_flush(c)) return 1;  // (a deferred sub-step pass first)
+    CG_READS_PARTICLES(c);
     CG_CHECK(c && (n == 0 || (pos && owner_out)), "cg_owner_rank: null argument");
     return cgk_owner_rank(c, pos, n, owner_out);
 }

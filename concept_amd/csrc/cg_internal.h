@@ -399,6 +399,33 @@ int cgk_substep_begin(cg_ctx *c, double *pos, const double *mom, double *dmom,
                       const double *integrals_1, double rf_up, double rf_down, int N_rungs,
                       int *any_out, long long *counts_after, int defer);
 int cgk_substep_flush(cg_ctx *c);
+// The gate.  A context remembers two things about particle arrays it does not own: a deferred
+// sub-step pass (sub_pending) and a drift histogram prepared for one pos/mom pair (prep_valid).
+// Every extern "C" entry that takes live particle arrays (pos, mom, Δmom, rungs, ids, rows of
+// particles) begins with exactly one of these lines and holds no flush or invalidation of its own
+// (tests/test_particle_gate_host.py reads the sources for it); a new entry picks its kind:
+//   CG_READS_PARTICLES   launches a pending pass first.  Writing Δmom, rungs or arrays of the
+//                        entry's own leaves the histogram alone: it depends on pos, mom and dt only.
+//   CG_WRITES_PARTICLES  the same, and pos or mom change: the prepared histogram is void.
+//   CG_ADOPTS_PENDING_PASS  cg_shortrange_cells[_rungs] only, and on purpose no flush here:
+//                        cgk_shortrange_cells takes a pending pass over the same pos and n into its
+//                        counting pass and flushes any other itself.
+//   CG_WHOLE_CONTEXT     cg_set_stream, cg_synchronize: what was deferred runs before the stream
+//                        changes or is waited for.  (cg_destroy drops a pending pass.)
+// A null context passes: the entry's own check reports it under the entry's name.
+inline int cg_particle_gate(cg_ctx *c, bool writes) {
+    if (!c) return 0;
+    if (writes) c->prep_valid = false;
+    return cgk_substep_flush(c);
+}
+#define CG_WRITES_PARTICLES_IF(c, writes)                    \
+    do {                                                     \
+        if (cg_particle_gate((c), (writes))) return 1;       \
+    } while (0)
+#define CG_READS_PARTICLES(c) CG_WRITES_PARTICLES_IF(c, false)
+#define CG_WRITES_PARTICLES(c) CG_WRITES_PARTICLES_IF(c, true)
+#define CG_WHOLE_CONTEXT(c) CG_WRITES_PARTICLES_IF(c, false)
+#define CG_ADOPTS_PENDING_PASS(c) ((void)(c))
 int cgk_substep_partial(cg_ctx *c, i64 n, i64 per, int N_rungs, i64 *nwg_out);
 int cgk_substep_populations(cg_ctx *c, i64 nwg, int N_rungs, long long *counts);
 int cgk_substep_end(cg_ctx *c, double *mom, double *dmom, signed char *rung,

@@ -290,6 +290,7 @@ extern "C" int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double 
 
 extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
                                int64_t index_bgn, int dim, double pos_factor, double mom_factor) {
+    CG_WRITES_PARTICLES(psi);
     CG_CHECK(psi, "cg_lpt_displace: null context");
     CG_CHECK(dim >= 0 && dim < 3, "cg_lpt_displace: dim = %d not in {0, 1, 2}", dim);
     if (n == 0) return 0;
@@ -301,7 +302,6 @@ extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
     CG_CHECK((pos || pos_factor == 0) && (mom || mom_factor == 0),
              "cg_lpt_displace: null particle array with a non-zero factor");
     if (pos_factor == 0 && mom_factor == 0) return 0;
-    psi->prep_valid = false;  // (momenta written)
     hipLaunchKernelGGL(k_lpt_displace, dim3(grid_for(n / 2)), dim3(kThreads), 0, psi->stream,
                        (const double *)psi->mesh0, (int)psi->N, psi->ny, psi->pad,
                        pos ? pos + 3 * index_bgn : nullptr, mom ? mom + 3 * index_bgn : nullptr,

@@ -282,6 +282,10 @@ int cgk_substep_begin(cg_ctx *c, double *pos, const double *mom, double *dmom, c
     if (cgk_substep_flush(c)) return 1;
     if (do_flag) CG_HIP(hipMemsetAsync(any_out, 0, sizeof(int), c->stream));
     if (n == 0 || (!do_drift && !do_flag)) return 0;
+    // pos moves: a prepared drift histogram is void from here on, not from the launch — whoever
+    // launches the pass later (the cell list that adopts it, cgk_substep_flush) need not know,
+    // and nothing can prepare one in between (the gate of that entry launches the pass first)
+    if (do_drift) c->prep_valid = false;
     SubstepBegin &B = *c->sub_begin;
     B = SubstepBegin{pos, mom, dmom, rung, rung_jumped, n, do_drift, do_flag, dt_over_mass,
                      c->p.boxsize, lowest_active, RungTable{}, rf_up, rf_down, N_rungs, any_out,
