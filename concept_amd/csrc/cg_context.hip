@@ -120,7 +120,10 @@ static int make_plans(cg_ctx *c) {
 // ---------------------------------------------------------------------------
 #include <map>
 struct DistPlans {
-    std::map<i64, std::pair<rocfft_plan, rocfft_plan>> layers2d;  // by number of layers
+    // by number of layers; a null plan: rocFFT did not make it, the layers take the 1-D plans
+    std::map<i64, std::pair<rocfft_plan, rocfft_plan>> layers2d;
+    // one layer in two steps: z along the rows (r2c / c2r in place), y along the columns kk
+    rocfft_plan z1[2] = {nullptr, nullptr}, y1[2] = {nullptr, nullptr};  // [inverse]
     rocfft_plan x_fwd = nullptr, x_bwd = nullptr;
     rocfft_execution_info info = nullptr;
     cg_buf<void> work;  // (freed after the plans are destroyed: dist_plans_destroy)
@@ -152,20 +155,73 @@ static int dist_plans_2d(cg_ctx *c, i64 nlayers, rocfft_plan *fwd, rocfft_plan *
         CG_FFT(rocfft_plan_description_set_data_layout(
             d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, off, off, 2, rstr,
             P * (size_t)c->ny, 2, cstr, (P / 2) * (size_t)c->ny));
-        CG_FFT(rocfft_plan_create(&pf, rocfft_placement_inplace, rocfft_transform_type_real_forward,
-                                  rocfft_precision_double, 2, lengths, (size_t)nlayers, d));
+        // (rocFFT refuses some of these plans — the inverse one at 16 and 64 points in rows of
+        // N + 16 doubles answers rocfft_status_failure — and such layers are transformed by
+        // the 1-D plans of dist_layers_1d instead)
+        if (rocfft_plan_create(&pf, rocfft_placement_inplace, rocfft_transform_type_real_forward,
+                               rocfft_precision_double, 2, lengths, (size_t)nlayers,
+                               d) != rocfft_status_success)
+            pf = nullptr;
         CG_FFT(rocfft_plan_description_destroy(d));
         CG_FFT(rocfft_plan_description_create(&d));
         CG_FFT(rocfft_plan_description_set_data_layout(
             d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, off, off, 2, cstr,
             (P / 2) * (size_t)c->ny, 2, rstr, P * (size_t)c->ny));
-        CG_FFT(rocfft_plan_create(&pb, rocfft_placement_inplace, rocfft_transform_type_real_inverse,
-                                  rocfft_precision_double, 2, lengths, (size_t)nlayers, d));
+        if (rocfft_plan_create(&pb, rocfft_placement_inplace, rocfft_transform_type_real_inverse,
+                               rocfft_precision_double, 2, lengths, (size_t)nlayers,
+                               d) != rocfft_status_success)
+            pb = nullptr;
         CG_FFT(rocfft_plan_description_destroy(d));
         it = m.emplace(nlayers, std::make_pair(pf, pb)).first;
     }
     *fwd = it->second.first;
     *bwd = it->second.second;
+    return 0;
+}
+
+// The 2-D transform of the layers [layer0, layer0 + nlayers) in two 1-D steps per layer, for
+// the sizes whose 2-D plan rocFFT does not make: z on the N rows of a layer (real <-> hermitian
+// in place, rows pad doubles = cp complex apart), y on its columns kk <= N/2 (complex, stride
+// cp).  Forward z then y, inverse y then z; unnormalised like the 2-D plans.
+static int dist_layers_1d(cg_ctx *c, bool inverse, i64 layer0, i64 nlayers) {
+    DistPlans *dp = c->dist_plans;
+    const size_t N = (size_t)c->N, P = (size_t)c->pad, cp = P / 2;
+    const int inv = inverse ? 1 : 0;
+    if (!dp->z1[inv]) {
+        size_t lengths[1] = {N}, one[1] = {1}, col[1] = {cp}, off[1] = {0};
+        rocfft_plan_description d = nullptr;
+        CG_FFT(rocfft_plan_description_create(&d));
+        if (!inverse)
+            CG_FFT(rocfft_plan_description_set_data_layout(
+                d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, off, off, 1,
+                one, P, 1, one, cp));
+        else
+            CG_FFT(rocfft_plan_description_set_data_layout(
+                d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, off, off, 1,
+                one, cp, 1, one, P));
+        CG_FFT(rocfft_plan_create(&dp->z1[inv], rocfft_placement_inplace,
+                                  inverse ? rocfft_transform_type_real_inverse
+                                          : rocfft_transform_type_real_forward,
+                                  rocfft_precision_double, 1, lengths, N, d));
+        CG_FFT(rocfft_plan_description_destroy(d));
+        CG_FFT(rocfft_plan_description_create(&d));
+        CG_FFT(rocfft_plan_description_set_data_layout(
+            d, rocfft_array_type_complex_interleaved, rocfft_array_type_complex_interleaved, off,
+            off, 1, col, 1, 1, col, 1));
+        CG_FFT(rocfft_plan_create(&dp->y1[inv], rocfft_placement_inplace,
+                                  inverse ? rocfft_transform_type_complex_inverse
+                                          : rocfft_transform_type_complex_forward,
+                                  rocfft_precision_double, 1, lengths, N / 2 + 1, d));
+        CG_FFT(rocfft_plan_description_destroy(d));
+    }
+    for (i64 l = layer0; l < layer0 + nlayers; l++) {
+        void *io[1] = {(void *)(c->mesh0 + l * c->ny * c->pad)};
+        for (int step = 0; step < 2; step++) {
+            rocfft_plan plan = (step == 0) != inverse ? dp->z1[inv] : dp->y1[inv];
+            if (dist_work(c, plan)) return 1;
+            CG_FFT(rocfft_execute(plan, io, nullptr, dp->info));
+        }
+    }
     return 0;
 }
 
@@ -218,15 +274,23 @@ static int dist_generic(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, do
         if (dist_plans_2d(c, nlayers, &pf, &pb)) return 1;
         void *io[1] = {(void *)(m + layer0 * c->ny * cp)};
         if (op == SlabOp::ZYForward) {
-            if (dist_work(c, pf)) return 1;
-            CG_FFT(rocfft_execute(pf, io, nullptr, c->dist_plans->info));
+            if (!pf) {
+                if (dist_layers_1d(c, false, layer0, nlayers)) return 1;
+            } else {
+                if (dist_work(c, pf)) return 1;
+                CG_FFT(rocfft_execute(pf, io, nullptr, c->dist_plans->info));
+            }
             hipLaunchKernelGGL((k_dist_rows<true>), dim3((unsigned)(nlayers * N)), dim3(256), 0,
                                c->stream, m, buf, N, c->ny, cp, nxl, JB, layer0);
         } else {
             hipLaunchKernelGGL((k_dist_rows<false>), dim3((unsigned)(nlayers * N)), dim3(256), 0,
                                c->stream, m, buf, N, c->ny, cp, nxl, JB, layer0);
-            if (dist_work(c, pb)) return 1;
-            CG_FFT(rocfft_execute(pb, io, nullptr, c->dist_plans->info));
+            if (!pb) {
+                if (dist_layers_1d(c, true, layer0, nlayers)) return 1;
+            } else {
+                if (dist_work(c, pb)) return 1;
+                CG_FFT(rocfft_execute(pb, io, nullptr, c->dist_plans->info));
+            }
         }
         hipError_t e_ = hipGetLastError();
         if (e_ != hipSuccess) {
@@ -275,8 +339,12 @@ static void dist_plans_destroy(cg_ctx *c) {
     DistPlans *d = c->dist_plans;
     if (!d) return;
     for (auto &kv : d->layers2d) {
-        rocfft_plan_destroy(kv.second.first);
-        rocfft_plan_destroy(kv.second.second);
+        if (kv.second.first) rocfft_plan_destroy(kv.second.first);
+        if (kv.second.second) rocfft_plan_destroy(kv.second.second);
+    }
+    for (int i = 0; i < 2; i++) {
+        if (d->z1[i]) rocfft_plan_destroy(d->z1[i]);
+        if (d->y1[i]) rocfft_plan_destroy(d->y1[i]);
     }
     if (d->x_fwd) rocfft_plan_destroy(d->x_fwd);
     if (d->x_bwd) rocfft_plan_destroy(d->x_bwd);
