@@ -1,4 +1,5 @@
-// cg_context.hip — context, rocFFT plans, Poisson solve driver, debug fetch.
+// cg_context.hip — the context and the C entry points: argument checks, the choice between the
+// two FFT backends (cg_fft.hip, cg_rocfft.hip), Poisson solve driver, debug fetch.
 // MI355X / gfx950 only.  See include/concept_gpu.h for the reference lines
 // each entry point replaces.
 #include <cmath>
@@ -61,296 +62,16 @@ static CicGeom make_geom_shift(double cellsize, int nghosts, int cell_centered,
     return g;
 }
 
-static int make_plans(cg_ctx *c) {
-    // In-place 3-D R2C / C2R on the padded layout FFTW uses (fft.c:34-73):
-    // real double[N][N][N+2] <-> hermitian complex[N][N][N/2+1], unnormalised
-    // both ways (mesh.py:4015-4022).  rocFFT lengths are fastest-first.
-    const size_t N = (size_t)c->N;
-    size_t lengths[3] = {N, N, N};
-    // row pitch c->pad >= N + 2 doubles (a multiple of 16 doubles when N is, so that
-    // rows and 16-cell tile rows start on 128-byte lines)
-    const size_t P = (size_t)c->pad;
-    size_t rstr[3] = {1, P, P * (size_t)c->ny};
-    size_t cstr[3] = {1, P / 2, (P / 2) * (size_t)c->ny};
-    size_t off[1] = {0};
-    rocfft_plan_description d = nullptr;
-    CG_FFT(rocfft_plan_description_create(&d));
-    CG_FFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_real,
-                                                   rocfft_array_type_hermitian_interleaved, off,
-                                                   off, 3, rstr, P * N * N, 3, cstr,
-                                                   (P / 2) * N * N));
-    CG_FFT(rocfft_plan_create(&c->plan_fwd, rocfft_placement_inplace,
-                              rocfft_transform_type_real_forward, rocfft_precision_double, 3,
-                              lengths, 1, d));
-    CG_FFT(rocfft_plan_description_destroy(d));
-    CG_FFT(rocfft_plan_description_create(&d));
-    CG_FFT(rocfft_plan_description_set_data_layout(d, rocfft_array_type_hermitian_interleaved,
-                                                   rocfft_array_type_real, off, off, 3, cstr,
-                                                   (P / 2) * N * N, 3, rstr, P * N * N));
-    CG_FFT(rocfft_plan_create(&c->plan_bwd, rocfft_placement_inplace,
-                              rocfft_transform_type_real_inverse, rocfft_precision_double, 3,
-                              lengths, 1, d));
-    CG_FFT(rocfft_plan_description_destroy(d));
-    size_t wf = 0, wb = 0;
-    CG_FFT(rocfft_plan_get_work_buffer_size(c->plan_fwd, &wf));
-    CG_FFT(rocfft_plan_get_work_buffer_size(c->plan_bwd, &wb));
-    const size_t work = wf > wb ? wf : wb;
-    if (work) {
-        if (c->fft_work.reserve(c, work)) return 1;
-        c->device_bytes += (i64)work;
-    }
-    CG_FFT(rocfft_execution_info_create(&c->info_fwd));
-    CG_FFT(rocfft_execution_info_create(&c->info_bwd));
-    if (work) {
-        CG_FFT(rocfft_execution_info_set_work_buffer(c->info_fwd, c->fft_work, work));
-        CG_FFT(rocfft_execution_info_set_work_buffer(c->info_bwd, c->fft_work, work));
-    }
-    return 0;
-}
-
-
-// ---------------------------------------------------------------------------
-// x-slab domains on the rocFFT backend: grids that are not a power of two (the reference
-// accepts any size divisible by the decomposition, communication.py:692-741,
-// mesh.py:1898-1905; its own tests use 24 and 36).  Same stages and the same transpose-buffer
-// layout as the hand-written path (cg_fft.hip fft_dist): 2-D real transforms of the owned
-// layers, rows packed by destination domain, all-to-all (the caller's), 1-D transforms along x
-// on complex[N][JB + 1][cp], and back.  The pack / unpack is a pass of its own here (the
-// hand-written y pass writes the blocked layout directly).
-// ---------------------------------------------------------------------------
-#include <map>
-struct DistPlans {
-    // by number of layers; a null plan: rocFFT did not make it, the layers take the 1-D plans
-    std::map<i64, std::pair<rocfft_plan, rocfft_plan>> layers2d;
-    // one layer in two steps: z along the rows (r2c / c2r in place), y along the columns kk
-    rocfft_plan z1[2] = {nullptr, nullptr}, y1[2] = {nullptr, nullptr};  // [inverse]
-    rocfft_plan x_fwd = nullptr, x_bwd = nullptr;
-    rocfft_execution_info info = nullptr;
-    cg_buf<void> work;  // (freed after the plans are destroyed: dist_plans_destroy)
-};
-
-static int dist_work(cg_ctx *c, rocfft_plan plan) {
-    DistPlans *d = c->dist_plans;
-    size_t w = 0;
-    CG_FFT(rocfft_plan_get_work_buffer_size(plan, &w));
-    if (d->work.reserve(c, w)) return 1;
-    if (!d->info) CG_FFT(rocfft_execution_info_create(&d->info));
-    if (d->work.bytes)
-        CG_FFT(rocfft_execution_info_set_work_buffer(d->info, d->work, d->work.bytes));
-    CG_FFT(rocfft_execution_info_set_stream(d->info, c->stream));
-    return 0;
-}
-
-static int dist_plans_2d(cg_ctx *c, i64 nlayers, rocfft_plan *fwd, rocfft_plan *bwd) {
-    if (!c->dist_plans) c->dist_plans = new DistPlans();
-    auto &m = c->dist_plans->layers2d;
-    auto it = m.find(nlayers);
-    if (it == m.end()) {
-        const size_t N = (size_t)c->N, P = (size_t)c->pad;
-        size_t lengths[2] = {N, N};  // fastest first: z, y
-        size_t rstr[2] = {1, P}, cstr[2] = {1, P / 2}, off[1] = {0};
-        rocfft_plan pf = nullptr, pb = nullptr;
-        rocfft_plan_description d = nullptr;
-        CG_FFT(rocfft_plan_description_create(&d));
-        CG_FFT(rocfft_plan_description_set_data_layout(
-            d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, off, off, 2, rstr,
-            P * (size_t)c->ny, 2, cstr, (P / 2) * (size_t)c->ny));
-        // (rocFFT refuses some of these plans — the inverse one at 16 and 64 points in rows of
-        // N + 16 doubles answers rocfft_status_failure — and such layers are transformed by
-        // the 1-D plans of dist_layers_1d instead)
-        if (rocfft_plan_create(&pf, rocfft_placement_inplace, rocfft_transform_type_real_forward,
-                               rocfft_precision_double, 2, lengths, (size_t)nlayers,
-                               d) != rocfft_status_success)
-            pf = nullptr;
-        CG_FFT(rocfft_plan_description_destroy(d));
-        CG_FFT(rocfft_plan_description_create(&d));
-        CG_FFT(rocfft_plan_description_set_data_layout(
-            d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, off, off, 2, cstr,
-            (P / 2) * (size_t)c->ny, 2, rstr, P * (size_t)c->ny));
-        if (rocfft_plan_create(&pb, rocfft_placement_inplace, rocfft_transform_type_real_inverse,
-                               rocfft_precision_double, 2, lengths, (size_t)nlayers,
-                               d) != rocfft_status_success)
-            pb = nullptr;
-        CG_FFT(rocfft_plan_description_destroy(d));
-        it = m.emplace(nlayers, std::make_pair(pf, pb)).first;
-    }
-    *fwd = it->second.first;
-    *bwd = it->second.second;
-    return 0;
-}
-
-// The 2-D transform of the layers [layer0, layer0 + nlayers) in two 1-D steps per layer, for
-// the sizes whose 2-D plan rocFFT does not make: z on the N rows of a layer (real <-> hermitian
-// in place, rows pad doubles = cp complex apart), y on its columns kk <= N/2 (complex, stride
-// cp).  Forward z then y, inverse y then z; unnormalised like the 2-D plans.
-static int dist_layers_1d(cg_ctx *c, bool inverse, i64 layer0, i64 nlayers) {
-    DistPlans *dp = c->dist_plans;
-    const size_t N = (size_t)c->N, P = (size_t)c->pad, cp = P / 2;
-    const int inv = inverse ? 1 : 0;
-    if (!dp->z1[inv]) {
-        size_t lengths[1] = {N}, one[1] = {1}, col[1] = {cp}, off[1] = {0};
-        rocfft_plan_description d = nullptr;
-        CG_FFT(rocfft_plan_description_create(&d));
-        if (!inverse)
-            CG_FFT(rocfft_plan_description_set_data_layout(
-                d, rocfft_array_type_real, rocfft_array_type_hermitian_interleaved, off, off, 1,
-                one, P, 1, one, cp));
-        else
-            CG_FFT(rocfft_plan_description_set_data_layout(
-                d, rocfft_array_type_hermitian_interleaved, rocfft_array_type_real, off, off, 1,
-                one, cp, 1, one, P));
-        CG_FFT(rocfft_plan_create(&dp->z1[inv], rocfft_placement_inplace,
-                                  inverse ? rocfft_transform_type_real_inverse
-                                          : rocfft_transform_type_real_forward,
-                                  rocfft_precision_double, 1, lengths, N, d));
-        CG_FFT(rocfft_plan_description_destroy(d));
-        CG_FFT(rocfft_plan_description_create(&d));
-        CG_FFT(rocfft_plan_description_set_data_layout(
-            d, rocfft_array_type_complex_interleaved, rocfft_array_type_complex_interleaved, off,
-            off, 1, col, 1, 1, col, 1));
-        CG_FFT(rocfft_plan_create(&dp->y1[inv], rocfft_placement_inplace,
-                                  inverse ? rocfft_transform_type_complex_inverse
-                                          : rocfft_transform_type_complex_forward,
-                                  rocfft_precision_double, 1, lengths, N / 2 + 1, d));
-        CG_FFT(rocfft_plan_description_destroy(d));
-    }
-    for (i64 l = layer0; l < layer0 + nlayers; l++) {
-        void *io[1] = {(void *)(c->mesh0 + l * c->ny * c->pad)};
-        for (int step = 0; step < 2; step++) {
-            rocfft_plan plan = (step == 0) != inverse ? dp->z1[inv] : dp->y1[inv];
-            if (dist_work(c, plan)) return 1;
-            CG_FFT(rocfft_execute(plan, io, nullptr, dp->info));
-        }
-    }
-    return 0;
-}
-
-static int dist_plans_x(cg_ctx *c) {
-    if (!c->dist_plans) c->dist_plans = new DistPlans();
-    DistPlans *dp = c->dist_plans;
-    if (dp->x_fwd) return 0;
-    const size_t N = (size_t)c->N, cp = (size_t)c->pad / 2, JB = N / (size_t)c->p.nprocs;
-    size_t lengths[1] = {N}, str[1] = {(JB + 1) * cp}, off[1] = {0};
-    for (int inv = 0; inv < 2; inv++) {
-        rocfft_plan_description d = nullptr;
-        CG_FFT(rocfft_plan_description_create(&d));
-        // one transform per (row of the own block, kk): consecutive complex numbers
-        CG_FFT(rocfft_plan_description_set_data_layout(
-            d, rocfft_array_type_complex_interleaved, rocfft_array_type_complex_interleaved, off,
-            off, 1, str, 1, 1, str, 1));
-        CG_FFT(rocfft_plan_create(inv ? &dp->x_bwd : &dp->x_fwd, rocfft_placement_inplace,
-                                  inv ? rocfft_transform_type_complex_inverse
-                                      : rocfft_transform_type_complex_forward,
-                                  rocfft_precision_double, 1, lengths, JB * cp, d));
-        CG_FFT(rocfft_plan_description_destroy(d));
-    }
-    return 0;
-}
-
-// rows j of the layers [layer0, layer0 + nlayers) between the slab's Fourier layout
-// complex[layer][ny][cp] and the transpose buffer blocked by destination domain
-// buf[q = j / JB][layer][j - q JB][cp] (JB + 1 rows per layer)
-template <bool PACK>
-__global__ __launch_bounds__(256) void k_dist_rows(double2 *__restrict__ slab,
-                                                   double2 *__restrict__ buf, i64 N, i64 ny,
-                                                   i64 cp, i64 nxl, i64 JB, i64 layer0) {
-    const i64 row = blockIdx.x;  // (layer - layer0) * N + j
-    const i64 l = layer0 + row / N, j = row % N, q = j / JB;
-    double2 *a = slab + (l * ny + j) * cp;
-    double2 *b = buf + ((q * nxl + l) * (JB + 1) + (j - q * JB)) * cp;
-    for (i64 kk = threadIdx.x; kk < N / 2 + 1; kk += blockDim.x) {
-        if (PACK) b[kk] = a[kk];
-        else a[kk] = b[kk];
-    }
-}
-
-static int dist_generic(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, double C,
-                        int long_range, double E, i64 layer0, i64 nlayers) {
-    const i64 cp = c->pad / 2, N = c->N, nxl = c->xmap.nxl, JB = N / c->p.nprocs;
-    if (nlayers < 0) nlayers = nxl - layer0;
-    double2 *m = (double2 *)c->mesh0;
-    if (op == SlabOp::ZYForward || op == SlabOp::ZYBackward) {
-        rocfft_plan pf, pb;
-        if (dist_plans_2d(c, nlayers, &pf, &pb)) return 1;
-        void *io[1] = {(void *)(m + layer0 * c->ny * cp)};
-        if (op == SlabOp::ZYForward) {
-            if (!pf) {
-                if (dist_layers_1d(c, false, layer0, nlayers)) return 1;
-            } else {
-                if (dist_work(c, pf)) return 1;
-                CG_FFT(rocfft_execute(pf, io, nullptr, c->dist_plans->info));
-            }
-            hipLaunchKernelGGL((k_dist_rows<true>), dim3((unsigned)(nlayers * N)), dim3(256), 0,
-                               c->stream, m, buf, N, c->ny, cp, nxl, JB, layer0);
-        } else {
-            hipLaunchKernelGGL((k_dist_rows<false>), dim3((unsigned)(nlayers * N)), dim3(256), 0,
-                               c->stream, m, buf, N, c->ny, cp, nxl, JB, layer0);
-            if (!pb) {
-                if (dist_layers_1d(c, true, layer0, nlayers)) return 1;
-            } else {
-                if (dist_work(c, pb)) return 1;
-                CG_FFT(rocfft_execute(pb, io, nullptr, c->dist_plans->info));
-            }
-        }
-        hipError_t e_ = hipGetLastError();
-        if (e_ != hipSuccess) {
-            cg_set_error("cg_dist_fft (rocFFT backend): pack / unpack launch failed: %s",
-                         hipGetErrorString(e_));
-            return 1;
-        }
-        return 0;
-    }
-    if (dist_plans_x(c)) return 1;
-    void *io[1] = {(void *)buf};
-    if (op == SlabOp::XSolve || op == SlabOp::XForward) {
-        if (dist_work(c, c->dist_plans->x_fwd)) return 1;
-        CG_FFT(rocfft_execute(c->dist_plans->x_fwd, io, nullptr, c->dist_plans->info));
-    }
-    if (op == SlabOp::XSolve) {
-        // the Poisson / deconvolution kernel on the rows of this domain (the Fourier view of
-        // cg_dist_bind_fourier, for the duration of the call on `buf`)
-        double2 *four = c->four;
-        const i64 f_si = c->f_si;
-        const int f_j0 = c->f_j0, f_nj = c->f_nj;
-        c->four = buf;
-        c->f_si = (JB + 1) * cp;
-        c->f_j0 = (int)(JB * c->p.rank);
-        c->f_nj = (int)JB;
-        int rc = cgk_kspace(c, deconv_order, C, long_range, E);
-        c->four = four, c->f_si = f_si, c->f_j0 = f_j0, c->f_nj = f_nj;
-        if (rc) return rc;
-    }
-    if (op == SlabOp::XSolve || op == SlabOp::XBackward) {
-        if (dist_work(c, c->dist_plans->x_bwd)) return 1;
-        CG_FFT(rocfft_execute(c->dist_plans->x_bwd, io, nullptr, c->dist_plans->info));
-    }
-    return 0;
-}
-
 // one piece of the slab transform on the context's backend
 static int dist_fft(cg_ctx *c, SlabOp op, const double *buf, int deconv_order, double C,
                     int long_range, double E, i64 layer0, i64 nlayers) {
     double2 *b = (double2 *)const_cast<double *>(buf);
-    return (c->custom_fft ? cgk_fft_dist : dist_generic)(c, op, b, deconv_order, C, long_range, E,
-                                                         layer0, nlayers);
+    return (c->custom_fft ? cgk_fft_dist : cgk_libfft_dist)(c, op, b, deconv_order, C, long_range,
+                                                            E, layer0, nlayers);
 }
-
-static void dist_plans_destroy(cg_ctx *c) {
-    DistPlans *d = c->dist_plans;
-    if (!d) return;
-    for (auto &kv : d->layers2d) {
-        if (kv.second.first) rocfft_plan_destroy(kv.second.first);
-        if (kv.second.second) rocfft_plan_destroy(kv.second.second);
-    }
-    for (int i = 0; i < 2; i++) {
-        if (d->z1[i]) rocfft_plan_destroy(d->z1[i]);
-        if (d->y1[i]) rocfft_plan_destroy(d->y1[i]);
-    }
-    if (d->x_fwd) rocfft_plan_destroy(d->x_fwd);
-    if (d->x_bwd) rocfft_plan_destroy(d->x_bwd);
-    if (d->info) rocfft_execution_info_destroy(d->info);
-    delete d;
-    c->dist_plans = nullptr;
+// the single-domain transform likewise
+static int mesh_fft(cg_ctx *c, FftOp op, int deconv_order, double C, int long_range, double E) {
+    return (c->custom_fft ? cgk_fft : cgk_libfft)(c, op, deconv_order, C, long_range, E);
 }
 
 // a table of the host in a device buffer of its size
@@ -359,8 +80,6 @@ static bool upload(cg_ctx *c, cg_devmem &buf, const std::vector<double> &host) {
     return !buf.reserve(c, bytes) &&
            hipMemcpy(buf.ptr, host.data(), bytes, hipMemcpyHostToDevice) == hipSuccess;
 }
-
-static bool g_rocfft_ready = false;
 
 static int ctx_init(cg_ctx *c);
 
@@ -383,7 +102,7 @@ extern "C" int cg_create(const cg_params *p, cg_ctx **out) {
              "cg_create: gridsize %lld must be divisible by 2*nprocs (mesh.py:1898-1905,3779)",
              (long long)p->gridsize);
     // (x-slab domains: power-of-two grids 16..2048 take the hand-written passes, any other
-    // admissible size rocFFT per slab + a pack pass — dist_generic above)
+    // admissible size rocFFT per slab + a pack pass — cg_rocfft.hip)
     // the potential halo is filled from the neighbour's OWNED layers in one hop
     // (communicate_ghosts(grid,'='), communication.py:563-660): a slab thinner than the G = 3
     // halo layers would hand on its own ghost layers
@@ -392,10 +111,6 @@ extern "C" int cg_create(const cg_params *p, cg_ctx **out) {
              "(use fewer domains or a larger grid)", p->nprocs,
              (long long)(p->gridsize / p->nprocs));
     CG_HIP(hipSetDevice(p->device));
-    if (!g_rocfft_ready) {
-        CG_FFT(rocfft_setup());
-        g_rocfft_ready = true;
-    }
     cg_ctx *c = new cg_ctx();
     c->sub_begin = new SubstepBegin();
     c->p = *p;
@@ -472,8 +187,8 @@ static int ctx_init(cg_ctx *c) {
     // (CONCEPT_GPU_FFT=rocfft forces the library, for A/B measurements)
     {
         const char *env = getenv("CONCEPT_GPU_FFT");
-        bool force_rocfft = env && std::string(env) == "rocfft";
-        c->custom_fft = cgk_fft_supported(c->N) && !force_rocfft;
+        bool force_library = env && std::string(env) == "rocfft";
+        c->custom_fft = cgk_fft_supported(c->N) && !force_library;
         // what the hand-written passes' plans depend on, read once here (cg_fft_plan.h)
         CG_HIP(hipDeviceGetAttribute(&c->ncu, hipDeviceAttributeMultiprocessorCount, p->device));
         CG_CHECK(c->ncu > 0, "cg_create: device %d reports %d compute units", p->device, c->ncu);
@@ -489,21 +204,15 @@ static int ctx_init(cg_ctx *c) {
             tw[2 * k + 1] = (double)sinl(a);
         }
         CG_CHECK(upload(c, c->fft_tw, tw), "cg_create: FFT twiddle upload failed");
-    } else if (p->nprocs == 1 && make_plans(c)) {  // (x-slab domains: plans made on first use)
-        return 1;
     }
-    return 0;
+    return cgk_libfft_init(c);
 }
 
-// (the buffers go with the context, after the plans that use them; a deferred sub-step pass
+// (the buffers go with the context, after rocFFT's plans; a deferred sub-step pass
 // that nothing has launched is dropped: it holds pointers to arrays the caller may have freed)
 extern "C" int cg_destroy(cg_ctx *c) {
     if (!c) return 0;
-    dist_plans_destroy(c);
-    if (c->plan_fwd) rocfft_plan_destroy(c->plan_fwd);
-    if (c->plan_bwd) rocfft_plan_destroy(c->plan_bwd);
-    if (c->info_fwd) rocfft_execution_info_destroy(c->info_fwd);
-    if (c->info_bwd) rocfft_execution_info_destroy(c->info_bwd);
+    cgk_libfft_destroy(c);
     if (c->tile_order_seen) (void)hipHostFree(c->tile_order_seen);
     for (auto &look : c->srd_look)
         if (look.ev) (void)hipEventDestroy(look.ev);
@@ -780,13 +489,7 @@ extern "C" int cg_poisson_forward(cg_ctx *c, int deconv_order, double C, int lon
     CG_CHECK(c->p.nprocs == 1, "cg_poisson_forward: single-domain entry point; x-slab domains use cg_dist_fft_*");
     CG_CHECK(deconv_order >= 0 && deconv_order <= 8, "cg_poisson_forward: deconv_order %d",
              deconv_order);
-    if (c->custom_fft) {
-        if (cgk_fft(c, FftOp::Forward, 0, 0.0, 0, 0.0)) return 1;
-    } else {
-        CG_FFT(rocfft_execution_info_set_stream(c->info_fwd, c->stream));
-        void *buf[1] = {c->mesh};
-        CG_FFT(rocfft_execute(c->plan_fwd, buf, nullptr, c->info_fwd));
-    }
+    if (mesh_fft(c, FftOp::Forward, 0, 0.0, 0, 0.0)) return 1;
     if (apply_kernel) return cgk_kspace(c, deconv_order, C, long_range, E);
     return 0;
 }
@@ -802,11 +505,7 @@ extern "C" int cg_poisson_kernel(cg_ctx *c, int deconv_order, double C, int long
 extern "C" int cg_poisson_backward(cg_ctx *c) {
     CG_CHECK(c, "cg_poisson_backward: null context");
     CG_CHECK(c->p.nprocs == 1, "cg_poisson_backward: single-domain entry point; x-slab domains use cg_dist_fft_*");
-    if (c->custom_fft) return cgk_fft(c, FftOp::Backward, 0, 0.0, 0, 0.0);
-    CG_FFT(rocfft_execution_info_set_stream(c->info_bwd, c->stream));
-    void *buf[1] = {c->mesh};
-    CG_FFT(rocfft_execute(c->plan_bwd, buf, nullptr, c->info_bwd));
-    return 0;
+    return mesh_fft(c, FftOp::Backward, 0, 0.0, 0, 0.0);
 }
 
 extern "C" int cg_poisson_solve(cg_ctx *c, int deconv_order, double C, int long_range, double E) {
@@ -814,10 +513,9 @@ extern "C" int cg_poisson_solve(cg_ctx *c, int deconv_order, double C, int long_
     CG_CHECK(c->p.nprocs == 1, "cg_poisson_solve: single-domain entry point; x-slab domains use cg_dist_fft_*");
     CG_CHECK(deconv_order >= 0 && deconv_order <= 8, "cg_poisson_solve: deconv_order %d",
              deconv_order);
-    // hand-written FFT: the k-space kernel is fused into the x pass (5 passes in all)
-    if (c->custom_fft) return cgk_fft(c, FftOp::Solve, deconv_order, C, long_range, E);
-    if (cg_poisson_forward(c, deconv_order, C, long_range, E, 1)) return 1;
-    return cg_poisson_backward(c);
+    // (hand-written FFT: the k-space kernel is fused into the x pass, 5 passes in all; rocFFT:
+    // forward, the kernel, backward)
+    return mesh_fft(c, FftOp::Solve, deconv_order, C, long_range, E);
 }
 
 extern "C" int cg_poisson_solve_timed(cg_ctx *c, int deconv_order, double C, int long_range,
@@ -825,8 +523,15 @@ extern "C" int cg_poisson_solve_timed(cg_ctx *c, int deconv_order, double C, int
     CG_CHECK(c && pass_ms, "cg_poisson_solve_timed: null argument");
     CG_CHECK(c->custom_fft && c->p.nprocs == 1,
              "cg_poisson_solve_timed: hand-written single-domain FFT only");
-    hipEvent_t ev[6];
-    for (auto &e : ev) CG_HIP(hipEventCreate(&e));
+    struct Events {  // (they leave with the function on every path)
+        hipEvent_t e[6] = {};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } events;
+    hipEvent_t *ev = events.e;
+    for (int i = 0; i < 6; i++) CG_HIP(hipEventCreate(&ev[i]));
     c->pass_events = ev;
     int rc = cg_poisson_solve(c, deconv_order, C, long_range, E);
     c->pass_events = nullptr;
@@ -838,7 +543,6 @@ extern "C" int cg_poisson_solve_timed(cg_ctx *c, int deconv_order, double C, int
             pass_ms[i] = ms;
         }
     }
-    for (auto &e : ev) (void)hipEventDestroy(e);
     return rc;
 }
 

@@ -1,7 +1,6 @@
 // cg_internal.h — shared declarations of libconcept_gpu.so (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
-#include <rocfft/rocfft.h>
 
 #include <cstdarg>
 #include <cstdint>
@@ -31,16 +30,6 @@ void cg_set_error(const char *fmt, ...);
         hipError_t e_ = hipGetLastError();                                                    \
         if (e_ != hipSuccess) {                                                               \
             cg_set_error("kernel launch failed: %s (%s:%d)", hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                           \
-            return 1;                                                                         \
-        }                                                                                     \
-    } while (0)
-
-#define CG_FFT(call)                                                                          \
-    do {                                                                                      \
-        rocfft_status s_ = (call);                                                            \
-        if (s_ != rocfft_status_success) {                                                    \
-            cg_set_error("%s failed: rocfft status %d (%s:%d)", #call, (int)s_, __FILE__,     \
                          __LINE__);                                                           \
             return 1;                                                                         \
         }                                                                                     \
@@ -95,7 +84,7 @@ struct TileGeom {
     int ntx, nty, ntz;  // tiles per dimension
 };
 
-// A device allocation that belongs to its holder (the context, DistPlans) and is freed with it.
+// A device allocation that belongs to its holder (the context, RocfftBackend) and is freed with it.
 // reserve() returns at once when the buffer is large enough; otherwise it drains c->stream (the
 // old buffer may be in use), frees it and allocates the new size: the contents are not kept.
 // On failure the buffer is left empty, the error is set and 1 is returned.
@@ -150,11 +139,9 @@ struct cg_ctx {
     cg_buf<double> ktab_n, ktab_s, ktab_q;
 
     // ---- FFT ----
-    // rocFFT (single domain; the plans are destroyed before fft_work is freed)
-    rocfft_plan plan_fwd = nullptr, plan_bwd = nullptr;
-    rocfft_execution_info info_fwd = nullptr, info_bwd = nullptr;
-    cg_buf<void> fft_work;
-    struct DistPlans *dist_plans = nullptr;  // x-slab domains on the rocFFT backend (cg_context.hip)
+    // the rocFFT backend (cg_rocfft.hip): its plans, execution info and work buffer; null on a
+    // context of the hand-written FFT
+    struct RocfftBackend *libfft = nullptr;
     // hand-written FFT (cg_fft.hip): twiddles exp(-2 pi i k/N) as double2[N]
     bool custom_fft = false;
     cg_buf<double2> fft_tw;
@@ -287,7 +274,7 @@ int cgk_fluid_kick(cg_ctx *c, double *J, const double *rho, const double *P, int
 // the single-domain solve: Solve = forward + Poisson kernel + backward with the x pass fused
 enum class FftOp { Forward, Backward, Solve };
 // its pieces on x-slab domains, around the two transposes (also of the rocFFT backend,
-// cg_context.hip): z and y of owned layers into / out of the transpose buffer, x on that buffer
+// cg_rocfft.hip): z and y of owned layers into / out of the transpose buffer, x on that buffer
 enum class SlabOp { ZYForward, XSolve, XForward, XBackward, ZYBackward };
 bool cgk_fft_supported(i64 N);
 int cgk_fft(cg_ctx *c, FftOp op, int deconv_order, double C, int long_range, double E);
@@ -295,6 +282,15 @@ int cgk_fft(cg_ctx *c, FftOp op, int deconv_order, double C, int long_range, dou
 // pieces; deconv_order, C, long_range, E for XSolve
 int cgk_fft_dist(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, double C, int long_range,
                  double E, i64 layer0, i64 nlayers);
+
+// ---- cg_rocfft.hip: the rocFFT backend ----
+// init: the library's set-up, once, and the backend of a context that is not custom_fft (on a
+// single domain with its 3-D plans); the transforms are those of cgk_fft and cgk_fft_dist
+int cgk_libfft_init(cg_ctx *c);
+void cgk_libfft_destroy(cg_ctx *c);
+int cgk_libfft(cg_ctx *c, FftOp op, int deconv_order, double C, int long_range, double E);
+int cgk_libfft_dist(cg_ctx *c, SlabOp op, double2 *buf, int deconv_order, double C,
+                    int long_range, double E, i64 layer0, i64 nlayers);
 
 // ---- cg_particles.hip: drift, tile sort, regions ----
 // out[i] = in[0] + ... + in[i-1] for i < n, on c->stream (temporary storage: c->scan_tmp)

@@ -1,5 +1,5 @@
 """Plain numpy references for the passes of the x-slab transform (fft_dist in
-concept_amd/csrc/cg_fft.hip, dist_generic and k_dist_rows in cg_context.hip), without a GPU:
+concept_amd/csrc/cg_fft.hip, cgk_libfft_dist and k_dist_rows in cg_rocfft.hip), without a GPU:
 the layouts, the exchange by hand, the expected values, the k-space factor in float64 and in
 numpy.longdouble, and the table of shapes that tests/test_gpu_slab_fft.py runs.
 

@@ -1,5 +1,5 @@
 """The passes of the x-slab transform one by one, in ONE process: fft_dist (cg_fft.hip) and
-dist_generic with k_dist_rows (cg_context.hip) through the raw entries
+cgk_libfft_dist with k_dist_rows (cg_rocfft.hip) through the raw entries
 cg_dist_fft_forward[_layers], cg_dist_fft_x, cg_dist_fft_xsolve, cg_dist_fft_backward[_layers]
 and cg_poisson_kernel on a bound Fourier slab, each against the plain numpy references of
 tests/slab_fft_refs.py.
@@ -41,10 +41,10 @@ Bars (none is made from what the code under test gives):
                    forward bar against the one call and against numpy.
 
 What these tests found: with CONCEPT_GPU_FFT=rocfft the slabs of 16 and 64 points stopped in
-dist_plans_2d — rocfft_plan_create of the in-place 2-D real inverse plan answers
+plans_2d (then dist_plans_2d) — rocfft_plan_create of the in-place 2-D real inverse plan answers
 rocfft_status_failure for 16 x 16 and 64 x 64 in rows of N + 16 doubles (256 and 48 with
-N + 16, 24 and 36 with N + 2 are planned both ways).  dist_generic now transforms such layers
-with two 1-D plans per layer (dist_layers_1d); the rocFFT cases at 16 and 64 run that path.
+N + 16, 24 and 36 with N + 2 are planned both ways).  cgk_libfft_dist now transforms such layers
+with two 1-D plans per layer (layers_1d); the rocFFT cases at 16 and 64 run that path.
 
 Zeros: the planes b == N/2 and kk == N/2 are whole pencils of the x pass and come out of xsolve
 as exact zeros, directly and after a forward pass of the result (`== 0` without a tolerance:
