@@ -10,10 +10,9 @@
 // sums over all its partners itself — twice the arithmetic, but no atomics, no
 // write conflicts (the order of partners inside a cell follows the cell list's
 // atomics, so sums are reproducible to rounding, not bit for bit).  The pair
-// vector and the table index follow the reference's expression and operation order
-// ((xi - xj) + offset; int(r2*scaling)); r2 is one product and two fused multiply-adds
-// (sr_r2), within 1 ulp of the reference's x*x + y*y + z*z, so that a pair at the range or
-// at a table entry's boundary may fall on the other side of it.  Exact negation symmetry
+// vector follows the reference's expression and operation order, (xi - xj) + offset; what
+// happens to it — r2, the range test, the table look-up, the accumulation, the counters — is
+// the same for every form of the sweep and lives in cg_sr_pairs.h.  Exact negation symmetry
 // makes the two directions of a pair bit-consistent.
 // (The tiles of 64 particles and more go to cg_shortrange_dense.hip; earlier forms of the
 // sweep — one wavefront per tile, a single-precision pre-test, a matrix-core range filter —
@@ -22,6 +21,7 @@
 #include <type_traits>
 
 #include "cg_internal.h"
+#include "cg_sr_pairs.h"
 #include "cg_substep.h"
 #include "cg_wave.h"
 
@@ -50,9 +50,6 @@ struct SrParams {
     const unsigned *nact;
     const signed char *rj_sorted;
 };
-struct SrCount {
-    unsigned tests = 0, hits = 0, trips = 0;
-};
 
 // ===========================================================================
 // Sweep over a cell list at HALF-tile granularity (the reference prunes below the tile level
@@ -75,11 +72,7 @@ struct SrCount {
 //  * no self test: a particle paired with itself has x_ji = 0 exactly and contributes
 //    0 * table[0] = 0, as would two distinct particles at one position (the reference skips
 //    i == j by index, interactions.py:1722; the sums are the same);
-//  * the accumulation a += x_ji * f is a fused multiply-add (the order of partners already
-//    differs from the reference's, Δmom is compared to 1e-12); x_ji keeps the reference's
-//    operation order and is bit-identical, r2 is one product and two fused multiply-adds
-//    (sr_r2) and lies within 1 ulp of the reference's sum, so that a pair right at the range
-//    or at a boundary between table entries may fall on the other side of it.
+//  * the order of partners differs from the reference's: Δmom is compared to 1e-12.
 // Periodic images: the tiles on the box faces are swept in blocks that reach across the face,
 // the offset added as the reference does, (xi - xj) + offset (SrWrapSeg below).
 // ===========================================================================
@@ -94,8 +87,7 @@ __device__ __forceinline__ unsigned sr_cell_of(double x0, double x1, double x2, 
 #pragma unroll
     for (int d = 0; d < 3; d++) {
         const double x = xs[d];
-        unsigned t = (unsigned)(i64)((x - 0.0) * inv);
-        t = t >= nt ? nt - 1 : t;
+        const unsigned t = sr_tile1(x, inv, nt);
         const unsigned half = (x - (double)t * ext) >= 0.5 * ext ? 1u : 0u;
         c[d] = 2u * t + half;
     }
@@ -354,11 +346,9 @@ __device__ __forceinline__ double sr_image(int d, double L) {
                             __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
-// pair tests of this lane's receiver against the staged suppliers [a, b), lane group `sub` of S
-// taking every S-th.  Accumulates sum x_ji * table[...] — the receiver's factor is applied once
-// at the end.  NB pairs per trip: their table loads (hits only) are all issued before the first
-// is used (two: 64 VGPRs, 8 wavefronts per SIMD, 8.6 ms at 256^3 / 512^3; four: 80 VGPRs, 9.4 ms;
-// eight: 11.8 ms).
+// pair tests (SrPairs) of this lane's receiver against the staged suppliers [a, b), lane group
+// `sub` of S taking every S-th.  NB pairs per trip (two: 64 VGPRs, 8 wavefronts per SIMD, 8.6 ms
+// at 256^3 / 512^3; four: 80 VGPRs, 9.4 ms; eight: 11.8 ms).
 template <bool WRAP, bool MASK, int NB, bool STATS>
 __device__ __forceinline__ void sr_cell_batch(int k, int S, int b, double xi, double yi, double zi,
                                               const double *sx, const double *sy,
@@ -368,41 +358,21 @@ __device__ __forceinline__ void sr_cell_batch(int k, int S, int b, double xi, do
                                               double &ay, double &az, bool counted, SrCount &cnt,
                                               SrWrapSeg w, double oyA, double oyB,
                                               const double *soz) {
-    // NB pairs of this lane: their table loads (hits only) are all issued before the first use
-    double xj[NB], yj[NB], zj[NB], r2[NB], t[NB];
-    bool hit[NB];
+    SrPairs<NB> P;
 #pragma unroll
     for (int j = 0; j < NB; j++) {
         const int kj = k + j * S;
-        xj[j] = xi - sx[kj];                             // interactions.py:1787-1789
-        yj[j] = yi - sy[kj];
-        zj[j] = zi - sz[kj];
+        const bool valid = !MASK || kj < b;              // (read past the range: staged slack)
+        double x = xi - sx[kj], y = yi - sy[kj], z = zi - sz[kj];  // interactions.py:1787-1789
         if (WRAP) {                                      // gravity.py:299-302
-            xj[j] += w.ox;
-            yj[j] += kj < w.ys ? oyA : oyB;
-            zj[j] += soz[kj];
+            x += w.ox;
+            y += kj < w.ys ? oyA : oyB;
+            z += soz[kj];
         }
-        r2[j] = sr_r2(xj[j], yj[j], zj[j]);  // gravity.py:306
-        hit[j] = r2[j] <= r2_max;                        // gravity.py:311: skip r2 > r2_max
-        if (MASK) hit[j] &= kj < b;                      // (read past the range: staged slack)
-        if (STATS) {
-            const bool valid = counted && (!MASK || kj < b);
-            cnt.tests += (unsigned)__popcll(__ballot(valid));
-            cnt.hits += (unsigned)__popcll(__ballot(valid && hit[j]));
-            cnt.trips++;
-        }
+        P.set(j, x, y, z, valid, r2_max);
+        if (STATS) cnt.add(counted && valid, P.hit[j]), cnt.trips++;
     }
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-        t[j] = 0.0;
-        if (hit[j]) t[j] = table[(unsigned)(int)(r2[j] * r2_index_scaling)];  // gravity.py:316-321
-    }
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-        ax = __builtin_fma(xj[j], t[j], ax);
-        ay = __builtin_fma(yj[j], t[j], ay);
-        az = __builtin_fma(zj[j], t[j], az);
-    }
+    P.accumulate(r2_index_scaling, table, ax, ay, az);
 }
 
 // One trip over the end of a range and the start of the next: the lanes whose turn i = sub + j S
@@ -418,8 +388,7 @@ __device__ __forceinline__ void sr_cell_straddle(int pos, int rem, int na, int n
                                                  double &ay, double &az, bool counted,
                                                  SrCount &cnt, SrWrapSeg w, SrWrapSeg wn,
                                                  double oyA, double oyB, const double *soz) {
-    double xj[2], yj[2], zj[2], r2[2], t[2];
-    bool hit[2];
+    SrPairs<2> P;
     const int nxt = na - rem;
 #pragma unroll
     for (int j = 0; j < 2; j++) {
@@ -427,33 +396,16 @@ __device__ __forceinline__ void sr_cell_straddle(int pos, int rem, int na, int n
         const bool here = i < rem;
         const int kj = (here ? pos : nxt) + i;
         const bool valid = here || kj < nb;
-        xj[j] = xi - sx[kj];
-        yj[j] = yi - sy[kj];
-        zj[j] = zi - sz[kj];
+        double x = xi - sx[kj], y = yi - sy[kj], z = zi - sz[kj];
         if (WRAP) {
-            xj[j] += here ? w.ox : wn.ox;
-            yj[j] += kj < (here ? w.ys : wn.ys) ? oyA : oyB;
-            zj[j] += soz[kj];
+            x += here ? w.ox : wn.ox;
+            y += kj < (here ? w.ys : wn.ys) ? oyA : oyB;
+            z += soz[kj];
         }
-        r2[j] = sr_r2(xj[j], yj[j], zj[j]);
-        hit[j] = r2[j] <= r2_max && valid;
-        if (STATS) {
-            cnt.tests += (unsigned)__popcll(__ballot(counted && valid));
-            cnt.hits += (unsigned)__popcll(__ballot(counted && hit[j]));
-            cnt.trips++;
-        }
+        P.set(j, x, y, z, valid, r2_max);
+        if (STATS) cnt.add(counted && valid, P.hit[j]), cnt.trips++;
     }
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        t[j] = 0.0;
-        if (hit[j]) t[j] = table[(unsigned)(int)(r2[j] * r2_index_scaling)];
-    }
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        ax = __builtin_fma(xj[j], t[j], ax);
-        ay = __builtin_fma(yj[j], t[j], ay);
-        az = __builtin_fma(zj[j], t[j], az);
-    }
+    P.accumulate(r2_index_scaling, table, ax, ay, az);
 }
 
 // The NSEG ranges [sa[s], sb[s]) of the staged window as ONE sequence of suppliers: full trips
@@ -1032,11 +984,7 @@ k_sr_sweep_blocks(const double *__restrict__ pos_r, const unsigned *__restrict__
             }
         }
     }
-    if (STATS && lane == 0) {
-        atomicAdd(&P.stats[0], (unsigned long long)cnt.tests);
-        atomicAdd(&P.stats[1], (unsigned long long)cnt.hits);
-        atomicAdd(&P.stats[2], (unsigned long long)cnt.trips);
-    }
+    if (STATS && lane == 0) cnt.flush(P.stats);
 }
 
 // ===========================================================================
@@ -1045,7 +993,9 @@ k_sr_sweep_blocks(const double *__restrict__ pos_r, const unsigned *__restrict__
 // all.  Every workgroup takes a slice of the suppliers, tests each against the K <= 8 receivers
 // (nearest periodic image: (xi - xj) + offset with offset = -L, 0 or +L, the same operations as
 // the tile offsets of interactions.py:1615-1621 give for a range below a quarter of the box) with
-// the sweep's pair arithmetic, and reduces its sums in a fixed tree; a second kernel adds the
+// the sweep's pair arithmetic (SrPairs<1>, behind a branch: without it every miss would pay the
+// multiply-adds, and the kernel took 174 registers instead of 126), and reduces its sums in a
+// fixed tree; a second kernel adds the
 // slices' partials in order and applies the receiver's rung factor.  Bit-reproducible; equal to
 // the cells sweep up to the order of the additions.
 // The rows come in `slots` slots (at most kSrSparseMax + 1); a slot below 0 is empty (the caller
@@ -1100,13 +1050,9 @@ __global__ __launch_bounds__(256) void k_sr_sparse(const double *__restrict__ po
             x = x + (x > half ? -L : (x < -half ? L : 0.0));       // + the image's offset
             y = y + (y > half ? -L : (y < -half ? L : 0.0));
             z = z + (z > half ? -L : (z < -half ? L : 0.0));
-            const double r2 = sr_r2(x, y, z);               // gravity.py:306
-            if (r2 <= P.r2_max) {                                   // gravity.py:311
-                const double t = table[(unsigned)(int)(r2 * P.r2_index_scaling)];
-                acc[r][0] = __builtin_fma(x, t, acc[r][0]);
-                acc[r][1] = __builtin_fma(y, t, acc[r][1]);
-                acc[r][2] = __builtin_fma(z, t, acc[r][2]);
-            }
+            SrPairs<1> pr;
+            pr.set(0, x, y, z, true, P.r2_max);
+            if (pr.hit[0]) pr.accumulate(P.r2_index_scaling, table, acc[r][0], acc[r][1], acc[r][2]);
         }
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1181,9 +1127,8 @@ int cgk_shortrange_sparse(cg_ctx *c, const double *pos_r, const i64 *active, int
 // every one gets a wavefront of its own — a cell in a clump may hold hundreds of them: the 5 x 5
 // columns x 5 cells around the cell are 25 runs of the suppliers' list (50 where the z range
 // wraps around the box) read where they are — 16 lanes per run, four runs per trip, nothing
-// staged, no barrier.  Same pair arithmetic as the blocks ((xi - xj) + offset bit-identical to
-// the reference's, r2 within 1 ulp of it: sr_r2); a receiver's sum is reduced over the wave in a
-// fixed order.
+// staged, no barrier.  The pair arithmetic is the blocks' (SrPairs); a receiver's sum is reduced
+// over the wave in a fixed order.
 // ===========================================================================
 constexpr int kSaRuns = 52;  // 25 columns x 2 pieces, rounded up to whole trips of 4
 // (one atomic on the list's counter per 4096 cells: an atomic per wavefront — 94,000 of them on
@@ -1359,40 +1304,25 @@ __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
             for (unsigned t0 = 0; t0 < total; t0 += 128) {
                 Row n0, n1;
                 ask(t0 + 128, n0, n1);
-                double x[2], y[2], z[2], r2[2], tv[2];
-                bool hit[2];
+                SrPairs<2> pr;
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     const Row &c = j ? c1 : c0;
-                    x[j] = xi - c.x;                   // interactions.py:1787-1789
-                    y[j] = yi - c.y;
-                    z[j] = zi - c.z;
+                    double x = xi - c.x, y = yi - c.y, z = zi - c.z;  // interactions.py:1787-1789
                     if (faces) {                       // gravity.py:299-302 (elsewhere: + 0)
                         const int img = r_img[wave][c.sl];
-                        x[j] += (double)((img & 3) - 1) * L;
-                        y[j] += (double)((img >> 2 & 3) - 1) * L;
-                        z[j] += (double)((img >> 4 & 3) - 1) * L;
+                        x += sr_image_offset(img, 0, L);
+                        y += sr_image_offset(img, 1, L);
+                        z += sr_image_offset(img, 2, L);
                     }
-                    r2[j] = sr_r2(x[j], y[j], z[j]);       // gravity.py:306
-                    hit[j] = c.valid && r2[j] <= P.r2_max; // gravity.py:311
-                    if (STATS) {
+                    pr.set(j, x, y, z, c.valid, P.r2_max);
+                    if (STATS) {  // (a trip counts where it holds a supplier)
                         const bool any = __builtin_amdgcn_readfirstlane((int)(t0 + 64u * j < total));
-                        cnt.tests += (unsigned)__popcll(__ballot(c.valid));
-                        cnt.hits += (unsigned)__popcll(__ballot(hit[j]));
+                        cnt.add(c.valid, pr.hit[j]);
                         cnt.trips += any ? 1u : 0u;
                     }
                 }
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    tv[j] = 0.0;
-                    if (hit[j]) tv[j] = table[(unsigned)(int)(r2[j] * P.r2_index_scaling)];
-                }
-#pragma unroll
-                for (int j = 0; j < 2; j++) {
-                    ax = __builtin_fma(x[j], tv[j], ax);
-                    ay = __builtin_fma(y[j], tv[j], ay);
-                    az = __builtin_fma(z[j], tv[j], az);
-                }
+                pr.accumulate(P.r2_index_scaling, table, ax, ay, az);
                 c0 = n0, c1 = n1;
             }
         }
@@ -1404,11 +1334,7 @@ __global__ __launch_bounds__(256) void k_sr_sweep_active_cells(
             dmom_r[o + 2] += az * f;
         }
     }
-    if (STATS && lane == 0) {
-        atomicAdd(&P.stats[0], (unsigned long long)cnt.tests);
-        atomicAdd(&P.stats[1], (unsigned long long)cnt.hits);
-        atomicAdd(&P.stats[2], (unsigned long long)cnt.trips);
-    }
+    if (STATS && lane == 0) cnt.flush(P.stats);
 }
 
 // the instantiation for (shape, rungs mode, statistics, table in LDS, across the faces)

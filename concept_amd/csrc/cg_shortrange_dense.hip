@@ -18,12 +18,10 @@
 //  * a wavefront takes 16 consecutive receivers (four lanes each) and the suppliers come as
 //    "quads" of 4 consecutive rows: a quad whose bounding box is further than the range from
 //    the bounding box of the 16 receivers is skipped (one lane per quad, 64 quads per look);
-//  * the quads that are left are evaluated exactly as the cells sweep evaluates a row of
-//    suppliers — 16 receivers x 4 suppliers per trip, (xi - xj) + offset, r2, the range test,
-//    table[int(r2*scaling)], three multiply-adds in FP64 — every contribution bit-identical to the
-//    cells sweep's (r2 by the same sr_r2, within 1 ulp of the reference's: a table index may
-//    differ from the reference's at a boundary), only the order of the additions differs.  All 64 lanes work in every trip:
-//    no per-lane candidate lists.
+//  * the quads that are left go through the pair test of the cells sweep (cg_sr_pairs.h), 16
+//    receivers x 4 suppliers per trip: every contribution is bit-identical to the cells
+//    sweep's, only the order of the additions differs.  All 64 lanes work in every trip: no
+//    per-lane candidate lists.
 // Measured on a Gaussian blob of the bench's clustered box (profiles/HISTORY_design_r1_r5.md §16b): 2.1-2.6 pair
 // tests per pair in range in tiles of 256 particles and more, 3.2 at 128-256, 4.1 at 64-128
 // (the cells sweep: 4.1-4.7), worse below — so cg_shortrange_sweep_cells hands the tiles above a
@@ -32,6 +30,7 @@
 #include <cstring>
 
 #include "cg_internal.h"
+#include "cg_sr_pairs.h"
 #include "cg_tiles.h"
 
 namespace {
@@ -70,12 +69,6 @@ struct SrdShared {
 // Lists by tile (Tiling.sort, species.py:775-780; z fastest): a counting sort — histogram,
 // scan, scatter — with the positions copied in list order.
 // ---------------------------------------------------------------------------
-// Tiling.sort (species.py:775-780) with tiling location 0
-__device__ __forceinline__ unsigned srd_tile1(double x, double inv, unsigned nt) {
-    unsigned t = (unsigned)(i64)((x - 0.0) * inv);
-    return t >= nt ? nt - 1 : t;
-}
-
 constexpr unsigned kdNoKey = 0xffffffffu;
 
 struct SrdKey {
@@ -92,8 +85,7 @@ __device__ __forceinline__ SrdKey srd_key(const double *__restrict__ pos, i64 p,
     k.x = k.y = k.z = 0;
     if (p < n && !(rung && rung[p] < lowest_active)) {
         k.x = pos[3 * p], k.y = pos[3 * p + 1], k.z = pos[3 * p + 2];
-        k.key = (srd_tile1(k.x, inv, nt) * nt + srd_tile1(k.y, inv, nt)) * nt +
-                srd_tile1(k.z, inv, nt);
+        k.key = (sr_tile1(k.x, inv, nt) * nt + sr_tile1(k.y, inv, nt)) * nt + sr_tile1(k.z, inv, nt);
     }
     return k;
 }
@@ -371,49 +363,30 @@ __global__ __launch_bounds__(256) void k_srd_gate(const unsigned *__restrict__ o
 }
 
 // NB quads of 4 supplier rows against the wave's 16 receivers: lane (j, g) pairs receiver j
-// with row g of every quad.  Same arithmetic, in the same order, as sr_cell_batch
-// (cg_shortrange.hip): the table loads of the hits are all issued before the first is used.
+// with row g of every quad (SrPairs: the arithmetic of sr_cell_batch, cg_shortrange.hip).
 template <bool FACE, int NB, bool STATS>
 __device__ __forceinline__ void srd_quads(const SrdShared &S, const int (&q)[NB], int g, double xi,
                                           double yi, double zi, double boxsize, double r2_max,
                                           double r2_index_scaling,
                                           const double *__restrict__ table, double &ax, double &ay,
-                                          double &az, bool counted, unsigned *cnt) {
-    double xj[NB], yj[NB], zj[NB], r2[NB], t[NB];
-    bool hit[NB];
+                                          double &az, bool counted, SrCount &cnt) {
+    SrPairs<NB> P;
 #pragma unroll
     for (int k = 0; k < NB; k++) {
         const int row = 4 * q[k] + g;
-        xj[k] = xi - S.sx[row];                          // interactions.py:1787-1789
-        yj[k] = yi - S.sy[row];
-        zj[k] = zi - S.sz[row];
-        if (FACE) {                                      // gravity.py:299-302: + the image's
-            const unsigned im = S.simg[row];             // offset -L, 0 or +L (exact products)
-            xj[k] += (double)((int)(im & 3) - 1) * boxsize;
-            yj[k] += (double)((int)((im >> 2) & 3) - 1) * boxsize;
-            zj[k] += (double)((int)((im >> 4) & 3) - 1) * boxsize;
+        double x = xi - S.sx[row], y = yi - S.sy[row], z = zi - S.sz[row];  // interactions.py:1787-1789
+        if (FACE) {                                      // gravity.py:299-302
+            const int im = S.simg[row];
+            x += sr_image_offset(im, 0, boxsize);
+            y += sr_image_offset(im, 1, boxsize);
+            z += sr_image_offset(im, 2, boxsize);
         }
-        r2[k] = sr_r2(xj[k], yj[k], zj[k]);  // gravity.py:306
-        hit[k] = r2[k] <= r2_max;                        // gravity.py:311
-        if (STATS) {
-            // a row of padding (the rest of a last quad, the far quad) sits at 1e300
-            const bool valid = counted && S.sx[4 * q[k] + g] < 1e299;
-            cnt[0] += (unsigned)__popcll(__ballot(valid));
-            cnt[1] += (unsigned)__popcll(__ballot(valid && hit[k]));
-            cnt[2]++;
-        }
+        // (a row of padding — the rest of a last quad, the far quad — sits at 1e300: out of
+        // everybody's range, and not counted as a test)
+        P.set(k, x, y, z, true, r2_max);
+        if (STATS) cnt.add(counted && S.sx[row] < 1e299, P.hit[k]), cnt.trips++;
     }
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-        t[k] = 0.0;
-        if (hit[k]) t[k] = table[(unsigned)(int)(r2[k] * r2_index_scaling)];  // gravity.py:316-321
-    }
-#pragma unroll
-    for (int k = 0; k < NB; k++) {
-        ax = __builtin_fma(xj[k], t[k], ax);
-        ay = __builtin_fma(yj[k], t[k], ay);
-        az = __builtin_fma(zj[k], t[k], az);
-    }
+    P.accumulate(r2_index_scaling, table, ax, ay, az);
 }
 
 // the quads of one look (bits of `m`: quad 64 look + bit), four at a time
@@ -422,7 +395,7 @@ __device__ __forceinline__ void srd_look(const SrdShared &S, unsigned long long 
                                          double xi, double yi, double zi, double boxsize,
                                          double r2_max, double r2_index_scaling,
                                          const double *__restrict__ table, double &ax, double &ay,
-                                         double &az, bool counted, unsigned *cnt) {
+                                         double &az, bool counted, SrCount &cnt) {
     while (m) {
         int q[kdNB];
 #pragma unroll
@@ -536,7 +509,7 @@ __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sr_sweep_dense(
     __syncthreads();
     const unsigned total = S.ppre[kdPieces];
     double ax = 0, ay = 0, az = 0;
-    unsigned cnt[3] = {0, 0, 0};
+    SrCount cnt;
     for (unsigned r0 = 0; r0 < total; r0 += kdCap) {
         const int nrows = (int)(min(total, r0 + (unsigned)kdCap) - r0);
         const int nq = (nrows + 3) >> 2;
@@ -565,12 +538,12 @@ __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sr_sweep_dense(
             for (int i = 0; i < 4; i++) {
                 const int w = 4 * q + i;
                 if (w < nrows) {
-                    const unsigned im = S.simg[w];
                     // x_ji = (xi - xj) + offset: the supplier's image sits at xj - offset
+                    const int im = S.simg[w];
                     const double v[3] = {
-                        ((S.sx[w] - (double)((int)(im & 3) - 1) * P.boxsize) - cx) * P.inv_ext,
-                        ((S.sy[w] - (double)((int)((im >> 2) & 3) - 1) * P.boxsize) - cy) * P.inv_ext,
-                        ((S.sz[w] - (double)((int)((im >> 4) & 3) - 1) * P.boxsize) - cz) * P.inv_ext};
+                        ((S.sx[w] - sr_image_offset(im, 0, P.boxsize)) - cx) * P.inv_ext,
+                        ((S.sy[w] - sr_image_offset(im, 1, P.boxsize)) - cy) * P.inv_ext,
+                        ((S.sz[w] - sr_image_offset(im, 2, P.boxsize)) - cz) * P.inv_ext};
 #pragma unroll
                     for (int d = 0; d < 3; d++) {
                         lo[d] = fminf(lo[d], (float)v[d]);
@@ -624,11 +597,7 @@ __attribute__((amdgpu_waves_per_eu(8, 8))) void k_sr_sweep_dense(
         dmom_r[3 * pi + 1] += ay * f;
         dmom_r[3 * pi + 2] += az * f;
     }
-    if (STATS && lane == 0) {
-        atomicAdd(&P.stats[3], (unsigned long long)cnt[0]);
-        atomicAdd(&P.stats[4], (unsigned long long)cnt[1]);
-        atomicAdd(&P.stats[5], (unsigned long long)cnt[2]);
-    }
+    if (STATS && lane == 0) cnt.flush(P.stats + 3);
     }
 }
 

@@ -6,6 +6,8 @@ factors by the JUMPED rung index, pinned to the reference by test_oracle_golden.
     (mode 1), the active-first list in blocks (mode 2: 2 x 2 blocks below 6 tiles a side, 4 x 2
     with the table in LDS or read from memory), by active receiver, without a cell list, and the
     dense tiles' form taking the tiles dense with active receivers;
+  * the sweeps' counters against counts made on the host: the pairs in range for every form,
+    the pair tests of the two cells forms from the cell histogram;
   * the dispatch of interactions.gravity() at the thresholds of the rung populations, with one
     and with two receiver components, the form taken recorded by a spy;
   * rung populations that disagree with the rung array: the oracle's answer or an error,
@@ -317,6 +319,117 @@ def test_dense_form_by_default_on_a_clustered_box(monkeypatch):
                 mesh.close()
             ref, s = _check(case, lowest, outs[0], base, f'{form}, dense by default')
             case.check_distinct(lowest, ref, TOL*s)
+
+
+# ----------------------------------------------------------------------------------------------
+# 1b. the sweeps' counters (cg_sr_pairs.h: one pair test, one SrCount for every form)
+# ----------------------------------------------------------------------------------------------
+def _cell_coords(pos, nt, L):
+    """the half-tile cell (X, Y, Z) of every particle, as sr_cell_of bins it"""
+    ext = L/nt
+    inv = (1/ext)*(1 - 2*2.220446049250313e-16)
+    t = np.minimum((pos*inv).astype(np.int64), nt - 1)
+    return 2*t + ((pos - t*ext) >= 0.5*ext)
+
+
+def _box_sum(a, axis, lo, hi):
+    """periodic sum of a[i + lo .. i + hi] along axis"""
+    return sum(np.roll(a, -d, axis) for d in range(lo, hi + 1))
+
+
+def _counter_truth(case):
+    """What the counters must show, from the host alone (cached on the case):
+    hits[i]: the suppliers within the range of receiver i — minimum image, r2 <= r2_max, the
+        receiver itself included where the two sets are one (the kernels skip no pair: it adds
+        0 * table[0]); no pair may sit at the cut, where sr_r2's ulp would decide;
+    by_cell[i]: the suppliers in the 5 x 5 x 5 cells around i's cell — what the sweep by active
+        receiver tests;
+    blocks[i]: the suppliers in the 5 x 5 columns around i's column over the 6 cells in z of its
+        tile's window (2 tc - 2 .. 2 tc + 3) — what the block sweep tests;
+    pop: the suppliers per cell."""
+    if hasattr(case, '_counters'):
+        return case._counters
+    nt, L, nc, r2_max = case.nt, case.L, 2*case.nt, RANGE**2
+    sup = case.pos_s if case.two else case.pos
+    hits = np.zeros(len(case.pos), np.int64)
+    for a in range(0, len(case.pos), 256):
+        r2 = 0
+        for d in range(3):
+            x = case.pos[a:a + 256, d, None] - sup[None, :, d]
+            x -= L*np.rint(x/L)
+            r2 = r2 + x*x
+        assert not (np.abs(r2 - r2_max) <= 1e-12*r2_max).any(), \
+            'a pair at the cut: choose another seed'
+        hits[a:a + 256] = (r2 <= r2_max).sum(1)
+    pop = np.zeros((nc, nc, nc), np.int64)
+    np.add.at(pop, tuple(_cell_coords(sup, nt, L).T), 1)
+    X, Y, Z = _cell_coords(case.pos, nt, L).T
+    columns = _box_sum(_box_sum(pop, 0, -2, 2), 1, -2, 2)
+    window = _box_sum(columns, 2, -2, 3)     # (at an even cell 2 tc: 2 tc - 2 .. 2 tc + 3)
+    case._counters = (hits, _box_sum(columns, 2, -2, 2)[X, Y, Z], window[X, Y, Z - Z % 2], pop)
+    return case._counters
+
+
+COUNTED = [CASES[0], CASES[2], CASES[3]]
+
+
+@pytest.mark.parametrize('dense', ['0', '3'])
+@pytest.mark.parametrize('spec', COUNTED, ids=[_ids(c) for c in COUNTED])
+def test_sweep_counters_against_host_counts(spec, dense, monkeypatch):
+    """cg_shortrange_stats of every form of the sweep — the plain list with every rung active
+    (lowest 0) and with the inactive receivers of lowest 1, the active-first list in blocks, by
+    active receiver — against counts made on the host: the pairs in range exactly
+    (cells + dense: the dense tiles' form, forced with a threshold of 3, must find the same
+    pairs), and with the dense form off the pair tests of the two cells forms from the cell
+    histogram.  The STATS instantiations are code of their own: their Δmom meets the oracle's
+    bar too.  (The formulas for the pair tests were read off the kernels; the counters of the
+    five hand-written copies of the pair test that cg_sr_pairs.h replaced agreed with them on all
+    three boxes: profiles/sr_pairs_refactor.json.)"""
+    import torch
+    from concept_amd.mesh import PotentialMesh
+    monkeypatch.setenv('CONCEPT_GPU_SR_DENSE_MIN', dense)
+    case = get_case(*spec)
+    nt, L = case.nt, case.L
+    hits, by_cell, blocks, pop = _counter_truth(case)
+    mesh = PotentialMesh(32, L)
+    dev = 'cuda'
+    pos = torch.as_tensor(case.pos, device=dev)
+    rung = torch.as_tensor(case.rung, device=dev)
+    jumped = torch.as_tensor(case.jumped, device=dev)
+    factors = torch.as_tensor(case.factors, device=dev)
+    table = torch.as_tensor(case.table, device=dev)
+    base = torch.as_tensor(np.random.default_rng(11).normal(0, 1e-3*case.s_pair, case.pos.shape),
+                           device=dev)
+    ext = L/nt
+    plain = mesh.shortrange_cells(pos, nt, ext)
+    cs = mesh.shortrange_cells(torch.as_tensor(case.pos_s, device=dev), nt, ext) if case.two else None
+    assert np.array_equal(np.diff((cs or plain).offset.cpu().numpy()), pop.ravel()), 'cell histogram'
+    assert 0 < (case.rung >= 1).sum() < len(case.rung)   # (lowest 1 has inactive receivers)
+    in_blocks = mesh.shortrange_cells(pos, nt, ext, (rung, jumped, 1), True)
+    runs = [(0, 'plain list', plain, None, blocks),
+            (1, 'plain list', plain, None, blocks),
+            (1, 'active-first in blocks', in_blocks, None, blocks),
+            (1, 'by active receiver', in_blocks, 'n_active', by_cell)]
+    for lowest, what, cells, bound, tests in runs:
+        active = case.rung >= lowest
+        got = base.clone()
+        mesh.shortrange_stats(True)
+        mesh.shortrange_sweep_cells(cells, got, cs if case.two else cells, nt, table, case.scaling,
+                                    RANGE**2, 0.0, (factors, rung, jumped, lowest),
+                                    int(active.sum()) if bound else None)
+        stats = mesh.shortrange_stats(False)
+        what = f'{what}, lowest active rung {lowest}, dense from {dense}: {stats}'
+        print(what, int(hits[active].sum()), int(tests[active].sum()))
+        assert stats['cells'][1] + stats['dense'][1] == hits[active].sum(), what
+        if dense == '0':
+            assert stats['dense'] == (0, 0, 0), what
+            assert stats['cells'][0] == tests[active].sum(), what
+            assert stats['cells'][2] > 0, what
+        else:
+            assert stats['dense'][0] > 0, f'dense form not taken: {what}'
+        _check(case, lowest, got, base, what)
+    assert mesh.error_flags() == 0
+    mesh.close()
 
 
 # ----------------------------------------------------------------------------------------------
