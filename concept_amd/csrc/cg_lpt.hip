@@ -8,7 +8,10 @@
 //   k_realize_grid   realize_grid (scalar and vector)   ic.py:708-764
 //   k_fluid_from_mesh  domain_decompose and the move to ϱ or Jⁱ of realize_fluid
 //                                                       ic.py:418-456
-// All six are streaming maps: one grid-stride loop, a thread per complex mode or per pair of
+//   k_lpt_diff_enlarge       fourier_diff + resize_grid up, of diff_ifft   ic.py:2093-2101
+//   k_lpt_dealias_cube       nullify_modes('beyond cube of |k| < …')       ic.py:2025
+//   k_lpt_shrink_accumulate  resize_grid down + the move to the output     ic.py:2029-2057
+// All of them are streaming maps: one grid-stride loop, a thread per complex mode or per pair of
 // neighbouring real cells (16-byte loads and stores), no LDS, no atomics, nothing wave-level.
 // The k-space kernels walk the Fourier view of the contexts (cg_ctx::four, the view
 // k_fourier_operate walks) over the N/2 + 1 modes of every row, the real-space kernels the N
@@ -103,7 +106,10 @@ __global__ __launch_bounds__(kThreads) void k_lpt_diff(double2 *dst, const doubl
     }
 }
 
-// out (= | += | -=) factor * a * b over the real cells; the three grids may be one another
+// out (= | += | -=) factor * a * b over the real cells; the three grids may be one another:
+// a thread reads its pair of cells of a, b and (for '+=', '-=') out before it writes that same
+// pair of out, and no other thread touches the pair, so the in-place product base *= tmp of
+// handle_lpt_term (ic.py:2020-2021) is cg_lpt_product(out = a = base, b = tmp, '=')
 template <int kOp>
 __global__ __launch_bounds__(kThreads) void k_lpt_product(double *out, const double *a,
                                                           const double *b, int N, i64 nrows, i64 ny,
@@ -208,6 +214,101 @@ __global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh
     }
 }
 
+// ---- 3LPT and Orszag dealiasing: the passes between the realisation size N and the dealiasing
+// size M = 3N/2 (+1 when odd).  The size-change phase of copy_modes (mesh.py:1302) is
+// theta = (pi/N_onto - pi/N_from)*((ki + kj) + kk), applied on the way up and on the way down.
+
+// `small` is the cube of |k| < n/2 of a grid of size n inside a larger one
+__device__ __forceinline__ bool in_cube(const KspaceMode &m, int n) {
+    const int h = n / 2;
+    return m.ki > -h && m.ki < h && m.kj > -h && m.kj < h && m.kk < h;
+}
+// array index of signed wave number k in a grid of size n
+__device__ __forceinline__ i64 wrap_index(i64 k, int n) { return k + (k < 0 ? n : 0); }
+
+// fourier_diff at N (k_lpt_diff's rounding) + resize_grid to M (mesh.py:916-922) in one pass over
+// dst: inside the cube the rotated derivative, everywhere else (src's Nyquist planes and all of
+// dst's included) zero without a read.  Every mode of dst is written exactly once.
+__global__ __launch_bounds__(kThreads) void k_lpt_diff_enlarge(double2 *dst, const double2 *src,
+                                                               int M, int N, i64 dst_si, i64 dst_cp,
+                                                               i64 src_si, i64 src_cp, int dim0,
+                                                               int dim1, double scale,
+                                                               double dtheta) {
+#pragma clang fp contract(off)
+    const i64 total = (i64)M * M * (M / 2 + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const KspaceMode m = kspace_mode(e, M, 0, M);
+        double2 out = make_double2(0.0, 0.0);
+        if (m.k2 != 0 && in_cube(m, N)) {
+            const double2 z =
+                src[wrap_index(m.ki, N) * src_si + wrap_index(m.kj, N) * src_cp + m.kk];
+            const i64 kl0 = dim0 == 0 ? m.ki : (dim0 == 1 ? m.kj : m.kk);
+            double re, im;
+            if (dim1 < 0) {
+                const double amplitude = scale * (double)kl0;  // mesh.py:3496
+                re = amplitude * -z.y;
+                im = amplitude * z.x;
+            } else {
+                const i64 kl1 = dim1 == 0 ? m.ki : (dim1 == 1 ? m.kj : m.kk);
+                const double amplitude = scale * (double)kl0 * (double)kl1;  // mesh.py:3506
+                re = amplitude * -z.x;
+                im = amplitude * -z.y;
+            }
+            const double theta = dtheta * (double)((m.ki + m.kj) + m.kk);  // mesh.py:1302
+            const double c = cos(theta), s = sin(theta);
+            out = make_double2(re * c - im * s, re * s + im * c);  // mesh.py:1310-1313
+        }
+        dst[(i64)m.a * dst_si + (i64)m.bl * dst_cp + m.kk] = out;
+    }
+}
+
+// nullify_modes(slab, 'beyond cube of |k| < n/2') (ic.py:2025): zeros outside the cube, nothing
+// read, nothing written inside
+__global__ __launch_bounds__(kThreads) void k_lpt_dealias_cube(double2 *mesh, int M, int n, i64 si,
+                                                               i64 cp) {
+    const i64 total = (i64)M * M * (M / 2 + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const KspaceMode m = kspace_mode(e, M, 0, M);
+        if (!in_cube(m, n)) mesh[(i64)m.a * si + (i64)m.bl * cp + m.kk] = make_double2(0.0, 0.0);
+    }
+}
+
+// resize_grid down to N (nullify 'nyquist', copy_modes; mesh.py:912-922) + the move to the output
+// grid (ic.py:2038-2057) in one pass over out: rotation, factor and sum rounded in turn.  On
+// out's Nyquist planes the shrunk grid is zero: '=' writes it, '+=' and '-=' leave out as it is.
+template <int kOp>
+__global__ __launch_bounds__(kThreads) void k_lpt_shrink_accumulate(double2 *out,
+                                                                    const double2 *src, int N,
+                                                                    int M, i64 out_si, i64 out_cp,
+                                                                    i64 src_si, i64 src_cp,
+                                                                    double factor, double dtheta) {
+#pragma clang fp contract(off)
+    const int nyq = N / 2;
+    const i64 total = (i64)N * N * (nyq + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const KspaceMode m = kspace_mode(e, N, 0, N);
+        double2 *o = out + (i64)m.a * out_si + (i64)m.bl * out_cp + m.kk;
+        if (m.a == nyq || m.bl == nyq || m.kk == nyq) {
+            if (kOp == 0) *o = make_double2(0.0, 0.0);
+            continue;
+        }
+        const double2 z = src[wrap_index(m.ki, M) * src_si + wrap_index(m.kj, M) * src_cp + m.kk];
+        const double theta = dtheta * (double)((m.ki + m.kj) + m.kk);  // mesh.py:1302
+        const double c = cos(theta), s = sin(theta);
+        double2 v = make_double2(z.x * c - z.y * s, z.x * s + z.y * c);
+        if (factor != 1) v = make_double2(factor * v.x, factor * v.y);  // ic.py:2042-2057
+        if (kOp == 0) {
+            *o = v;
+        } else {
+            const double2 w = *o;
+            *o = kOp == 1 ? make_double2(w.x + v.x, w.y + v.y) : make_double2(w.x - v.x, w.y - v.y);
+        }
+    }
+}
+
 int fourier_pair_checks(const char *name, cg_ctx *dst, cg_ctx *src) {
     CG_CHECK(dst && src, "%s: null context", name);
     CG_CHECK(dst->four != nullptr && src->four != nullptr,
@@ -217,6 +318,24 @@ int fourier_pair_checks(const char *name, cg_ctx *dst, cg_ctx *src) {
     CG_CHECK(same_geometry(dst, src), "%s: the two meshes differ in grid size or domain", name);
     CG_CHECK(dst->N * (i64)dst->f_nj < ((i64)1 << 31), "%s: %lld rows", name,
              (long long)(dst->N * (i64)dst->f_nj));
+    return 0;
+}
+
+// two single-domain contexts of different grid size in Fourier space: `large` of size M, `small`
+// of size N < M
+int resize_pair_checks(const char *name, cg_ctx *large, cg_ctx *small) {
+    CG_CHECK(large && small, "%s: null context", name);
+    CG_CHECK(large->four != nullptr && small->four != nullptr,
+             "%s: no Fourier buffer bound (cg_dist_bind_fourier)", name);
+    CG_CHECK(large->p.nprocs == 1 && small->p.nprocs == 1, "%s: single-domain entry point", name);
+    CG_CHECK(small->N >= 2 && small->N % 2 == 0 && large->N % 2 == 0,
+             "%s: grid sizes %lld and %lld are not both even", name, (long long)small->N,
+             (long long)large->N);
+    CG_CHECK(large->N > small->N, "%s: grid size %lld is not larger than %lld", name,
+             (long long)large->N, (long long)small->N);
+    CG_CHECK(large->p.boxsize == small->p.boxsize, "%s: the two meshes span different boxes", name);
+    CG_CHECK(large->N * large->N < ((i64)1 << 31), "%s: %lld rows", name,
+             (long long)(large->N * large->N));
     return 0;
 }
 
@@ -284,6 +403,61 @@ extern "C" int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double 
     else if (op == 1) CG_LPT_PRODUCT(1);
     else CG_LPT_PRODUCT(2);
 #undef CG_LPT_PRODUCT
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_lpt_diff_enlarge(cg_ctx *dst, cg_ctx *src, int dim0, int dim1, double factor) {
+    if (resize_pair_checks("cg_lpt_diff_enlarge", dst, src)) return 1;
+    CG_CHECK(dim0 >= 0 && dim0 < 3 && dim1 >= -1 && dim1 < 3,
+             "cg_lpt_diff_enlarge: dimensions (%d, %d) outside 0..2 (the second may be -1)", dim0,
+             dim1);
+    const double k_fundamental = 2 * kPi / src->p.boxsize;
+    const double scale = dim1 < 0 ? factor * k_fundamental
+                                  : factor * (k_fundamental * k_fundamental);
+    const double dtheta = kPi / (double)dst->N - kPi / (double)src->N;  // mesh.py:1302
+    const i64 total = dst->N * dst->N * (dst->N / 2 + 1);
+    hipLaunchKernelGGL(k_lpt_diff_enlarge, dim3(grid_for(total)), dim3(kThreads), 0, dst->stream,
+                       dst->four, (const double2 *)src->four, (int)dst->N, (int)src->N, dst->f_si,
+                       dst->pad / 2, src->f_si, src->pad / 2, dim0, dim1, scale, dtheta);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_lpt_dealias_cube(cg_ctx *mesh, int64_t n_small) {
+    CG_CHECK(mesh, "cg_lpt_dealias_cube: null context");
+    CG_CHECK(mesh->four != nullptr,
+             "cg_lpt_dealias_cube: no Fourier buffer bound (cg_dist_bind_fourier)");
+    CG_CHECK(mesh->p.nprocs == 1, "cg_lpt_dealias_cube: single-domain entry point");
+    CG_CHECK(n_small >= 2 && n_small % 2 == 0 && mesh->N % 2 == 0,
+             "cg_lpt_dealias_cube: grid sizes %lld and %lld are not both even", (long long)n_small,
+             (long long)mesh->N);
+    CG_CHECK(n_small < mesh->N, "cg_lpt_dealias_cube: grid size %lld is not larger than %lld",
+             (long long)mesh->N, (long long)n_small);
+    CG_CHECK(mesh->N * mesh->N < ((i64)1 << 31), "cg_lpt_dealias_cube: %lld rows",
+             (long long)(mesh->N * mesh->N));
+    const i64 total = mesh->N * mesh->N * (mesh->N / 2 + 1);
+    hipLaunchKernelGGL(k_lpt_dealias_cube, dim3(grid_for(total)), dim3(kThreads), 0, mesh->stream,
+                       mesh->four, (int)mesh->N, (int)n_small, mesh->f_si, mesh->pad / 2);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_lpt_shrink_accumulate(cg_ctx *out, cg_ctx *src, int op, double factor) {
+    if (resize_pair_checks("cg_lpt_shrink_accumulate", src, out)) return 1;
+    CG_CHECK(op >= 0 && op <= 2,
+             "cg_lpt_shrink_accumulate: operation %d not in {0 '=', 1 '+=', 2 '-='}", op);
+    const double dtheta = kPi / (double)out->N - kPi / (double)src->N;  // mesh.py:1302
+    const i64 total = out->N * out->N * (out->N / 2 + 1);
+#define CG_LPT_SHRINK(OP)                                                                        \
+    hipLaunchKernelGGL(k_lpt_shrink_accumulate<OP>, dim3(grid_for(total)), dim3(kThreads), 0,    \
+                       out->stream, out->four, (const double2 *)src->four, (int)out->N,          \
+                       (int)src->N, out->f_si, out->pad / 2, src->f_si, src->pad / 2, factor,    \
+                       dtheta)
+    if (op == 0) CG_LPT_SHRINK(0);
+    else if (op == 1) CG_LPT_SHRINK(1);
+    else CG_LPT_SHRINK(2);
+#undef CG_LPT_SHRINK
     CG_LAUNCH_CHECK();
     return 0;
 }

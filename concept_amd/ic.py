@@ -1,6 +1,5 @@
-"""Initial conditions: 1LPT / 2LPT particle realisation and the realisation of the fluid
-variables ϱ and J (ic.py:67-232, 297-477, 599-627, 708-764, 928-1589, 1895-2280 of the
-reference).
+"""Initial conditions: 1LPT / 2LPT / 3LPT particle realisation and the realisation of the fluid
+variables ϱ and J (ic.py:67-232, 297-477, 599-627, 708-764, 928-2280 of the reference).
 
 The reference gets two things from CLASS — a table of amplitudes T(k)·ζ(k) indexed by k² and a
 handful of growth factors — and does everything after that on meshes.  Here both are inputs
@@ -13,14 +12,18 @@ GPU (csrc/cg_lpt.hip through PotentialMesh.lpt_*):
       -> positions += Ψ, momenta += factor·Ψ    lpt_displace
     2LPT: the six products of second derivatives of Φ⁽¹⁾ (lpt_diff, lpt_product) summed into
     the source of Φ⁽²⁾, transformed, ∇⁻², and displaced the same way.
+    3LPT (extended=True): Φ⁽³ᵃ⁾, Φ⁽³ᵇ⁾ and the three A⁽³ᶜ⁾ᵢ from tables of terms (LptTerms), the
+    last displaced by its curl.  Dealiasing (extended=True): every derivative is enlarged to
+    M = 3N/2 (lpt_diff_enlarge), every product made there, nullified beyond the cube |k| < N/2
+    (lpt_dealias_cube) and the last one shrunk into the potential (lpt_shrink_accumulate).
 
     fluids (realize_fluid, realize): the same noise
       -> amplitude·noise (ϱ) or amplitude·(-i kⁱ/k²)·noise (Jⁱ)   realize_grid
       -> back to real space                                       the mesh's inverse transform
       -> ϱ = ϱ_bar(1 + δ) or Jⁱ = a**(1 - 3w_eff)ϱ_bar(1 + w)uⁱ    fluid_from_mesh
 
-Out of scope, refused by name.  Particles: 3LPT, Orszag dealiasing, non-Gaussianity, non-primordial
-structure, N without a cubic lattice.  Fluids: the variables above J (ς, δP), closure 'class'.
+Out of scope, refused by name.  Particles: 3LPT and Orszag dealiasing unless extended=True,
+non-Gaussianity, non-primordial structure, N without a cubic lattice.  Fluids: the variables above J (ς, δP), closure 'class'.
 Both: several domains."""
 import contextlib
 import math
@@ -313,18 +316,23 @@ def realization_options(component):
     return {key: is_selected(component, d) for key, d in p.realization_options.items()}
 
 
-def _check_scope(component, options):
+def _check_scope(component, options, extended=False):
     name = component.name
     lpt = options['lpt']
-    if lpt == 3:
-        raise ConceptGPUError(f'{name}: realization_options["lpt"] = 3: 3LPT is not '
-                              'implemented (1LPT and 2LPT are)')
-    if lpt not in {1, 2}:
-        raise ConceptGPUError(f'{name}: realize_particles() called with attempted {lpt}LPT, '
-                              'though only 1LPT and 2LPT are implemented')
-    if options['dealias']:
-        raise ConceptGPUError(f'{name}: realization_options["dealias"]: Orszag dealiasing of '
-                              'the LPT products is not implemented')
+    if extended:
+        if lpt not in {1, 2, 3}:
+            raise ConceptGPUError(f'{name}: realize_particles() called with attempted {lpt}LPT, '
+                                  'though only 1LPT, 2LPT and 3LPT are implemented')
+    else:
+        if lpt == 3:
+            raise ConceptGPUError(f'{name}: realization_options["lpt"] = 3: 3LPT is not '
+                                  'implemented (1LPT and 2LPT are)')
+        if lpt not in {1, 2}:
+            raise ConceptGPUError(f'{name}: realize_particles() called with attempted {lpt}LPT, '
+                                  'though only 1LPT and 2LPT are implemented')
+        if options['dealias']:
+            raise ConceptGPUError(f'{name}: realization_options["dealias"]: Orszag dealiasing of '
+                                  'the LPT products is not implemented')
     if options['nongaussianity'] != 0:
         raise ConceptGPUError(f'{name}: realization_options["nongaussianity"] = '
                               f'{options["nongaussianity"]}: non-Gaussian initial conditions are '
@@ -369,30 +377,272 @@ class _Stopwatch:
             self.timings[kind + ' passes'] = self.timings.get(kind + ' passes', 0) + 1
 
 
+# ---- the potentials above the first (ic.py:1539-2103) ---------------------------------------------
+def dealias_gridsize(gridsize):
+    """the size of the enlarged grids of Orszag's 3/2 rule, made even (ic.py:1322-1323)"""
+    gridsize_dealias = (gridsize*3)//2
+    return gridsize_dealias + (gridsize_dealias & 1)
+
+
+def _term(output, operation, factor, *potentials):
+    """(output, operation, factor, ((potential, dim0, dim1), ...)): one term of the source of
+    an LPT potential, the dimensions of a derivative sorted as handle_lpt_term sorts them"""
+    return (output, operation, float(factor),
+            tuple((name,) + tuple(sorted(dims)) for name, *dims in potentials))
+
+
+# ∇²Φ⁽²⁾ = D⁽²⁾/(D⁽¹⁾)² (-Φ,₀₀Φ,₁₁ - Φ,₁₁Φ,₂₂ - Φ,₂₂Φ,₀₀ + Φ,₀₁² + Φ,₁₂² + Φ,₂₀²), Φ = Φ⁽¹⁾
+# (ic.py:1554-1575)
+LPT_TERMS_2 = (
+    _term('Φ2', '=', -1, ('Φ1', 0, 0), ('Φ1', 1, 1)),
+    _term('Φ2', '-=', 1, ('Φ1', 1, 1), ('Φ1', 2, 2)),
+    _term('Φ2', '-=', 1, ('Φ1', 2, 2), ('Φ1', 0, 0)),
+    _term('Φ2', '+=', 1, ('Φ1', 0, 1), ('Φ1', 0, 1)),
+    _term('Φ2', '+=', 1, ('Φ1', 1, 2), ('Φ1', 1, 2)),
+    _term('Φ2', '+=', 1, ('Φ1', 2, 0), ('Φ1', 2, 0)),
+)
+# ∇²Φ⁽³ᵃ⁾ = D⁽³ᵃ⁾/(D⁽¹⁾)³ (Φ,₂₀²Φ,₁₁ - Φ,₁₁Φ,₂₂Φ,₀₀ + Φ,₀₀Φ,₁₂² - 2Φ,₁₂Φ,₂₀Φ,₀₁ + Φ,₀₁²Φ,₂₂)
+# (ic.py:1633-1652)
+LPT_TERMS_3A = (
+    _term('Φ3', '=', 1, ('Φ1', 2, 0), ('Φ1', 2, 0), ('Φ1', 1, 1)),
+    _term('Φ3', '-=', 1, ('Φ1', 1, 1), ('Φ1', 2, 2), ('Φ1', 0, 0)),
+    _term('Φ3', '+=', 1, ('Φ1', 0, 0), ('Φ1', 1, 2), ('Φ1', 1, 2)),
+    _term('Φ3', '-=', 2, ('Φ1', 1, 2), ('Φ1', 2, 0), ('Φ1', 0, 1)),
+    _term('Φ3', '+=', 1, ('Φ1', 0, 1), ('Φ1', 0, 1), ('Φ1', 2, 2)),
+)
+# ∇²Φ⁽³ᵇ⁾ = D⁽³ᵇ⁾/(D⁽¹⁾D⁽²⁾) (-½Φ⁽¹⁾,₂₂Φ⁽²⁾,₀₀ - ½Φ⁽²⁾,₀₀Φ⁽¹⁾,₁₁ - ½Φ⁽¹⁾,₁₁Φ⁽²⁾,₂₂ - ½Φ⁽²⁾,₂₂Φ⁽¹⁾,₀₀
+#   - ½Φ⁽¹⁾,₀₀Φ⁽²⁾,₁₁ - ½Φ⁽²⁾,₁₁Φ⁽¹⁾,₂₂ + Φ⁽²⁾,₂₀Φ⁽¹⁾,₂₀ + Φ⁽²⁾,₀₁Φ⁽¹⁾,₀₁ + Φ⁽²⁾,₁₂Φ⁽¹⁾,₁₂)  (ic.py:1711-1739)
+LPT_TERMS_3B = (
+    _term('Φ3', '=', -0.5, ('Φ1', 2, 2), ('Φ2', 0, 0)),
+    _term('Φ3', '-=', 0.5, ('Φ2', 0, 0), ('Φ1', 1, 1)),
+    _term('Φ3', '-=', 0.5, ('Φ1', 1, 1), ('Φ2', 2, 2)),
+    _term('Φ3', '-=', 0.5, ('Φ2', 2, 2), ('Φ1', 0, 0)),
+    _term('Φ3', '-=', 0.5, ('Φ1', 0, 0), ('Φ2', 1, 1)),
+    _term('Φ3', '-=', 0.5, ('Φ2', 1, 1), ('Φ1', 2, 2)),
+    _term('Φ3', '+=', 1, ('Φ2', 2, 0), ('Φ1', 2, 0)),
+    _term('Φ3', '+=', 1, ('Φ2', 0, 1), ('Φ1', 0, 1)),
+    _term('Φ3', '+=', 1, ('Φ2', 1, 2), ('Φ1', 1, 2)),
+)
+
+
+def lpt_terms_3c(i):
+    """∇²Aᵢ⁽³ᶜ⁾ = D⁽³ᶜ⁾/(D⁽¹⁾D⁽²⁾) (Φ⁽²⁾,ⱼⱼΦ⁽¹⁾,ⱼₖ - Φ⁽¹⁾,ⱼₖΦ⁽²⁾,ₖₖ - Φ⁽¹⁾,ᵢⱼΦ⁽²⁾,ᵢₖ - Φ⁽¹⁾,ⱼⱼΦ⁽²⁾,ⱼₖ
+    + Φ⁽²⁾,ⱼₖΦ⁽¹⁾,ₖₖ + Φ⁽²⁾,ᵢⱼΦ⁽¹⁾,ᵢₖ) with (i, j, k) cyclic (ic.py:1801-1830)"""
+    j, k = (i + 1) % 3, (i + 2) % 3
+    return (
+        _term('Φ3', '=', 1, ('Φ2', j, j), ('Φ1', j, k)),
+        _term('Φ3', '-=', 1, ('Φ1', j, k), ('Φ2', k, k)),
+        _term('Φ3', '-=', 1, ('Φ1', i, j), ('Φ2', i, k)),
+        _term('Φ3', '-=', 1, ('Φ1', j, j), ('Φ2', j, k)),
+        _term('Φ3', '+=', 1, ('Φ2', j, k), ('Φ1', k, k)),
+        _term('Φ3', '+=', 1, ('Φ2', i, j), ('Φ1', i, k)),
+    )
+
+
+def _gradient():
+    """Ψᵢ = ∂ᵢΦ: (dimension of the derivative, its factor, dimension displaced)"""
+    return tuple((i, 1.0, i) for i in range(3))
+
+
+def _curl(i):
+    """the part of Ψ⁽³ᶜ⁾ⱼ = ±∂ₖAᵢ that Aᵢ carries, with the sign of ic.py:1840-1847"""
+    passes = []
+    for j in range(3):
+        if j == i:
+            continue
+        k = 3 - i - j
+        passes.append((k, float(2*(k == (j + 1) % 3) - 1), j))
+    return tuple(passes)
+
+
+def lpt_orders(lpt):
+    """What follows 1LPT, potential by potential in the reference's order (carryout_2lpt,
+    carryout_3lpt_a, _b and three times _c): (name, terms, growth factor D, the potentials whose
+    D⁽ⁿ⁾ divide it, growth rate f, displacement passes)."""
+    orders = []
+    if lpt >= 2:
+        orders.append(('Φ2', LPT_TERMS_2, 'D2', lambda g: g['D1']**2, 'f2', _gradient()))
+    if lpt >= 3:
+        orders.append(('Φ3a', LPT_TERMS_3A, 'D3a', lambda g: g['D1']**3, 'f3a', _gradient()))
+        orders.append(('Φ3b', LPT_TERMS_3B, 'D3b', lambda g: g['D1']*g['D2'], 'f3b',
+                       _gradient()))
+        for i in range(3):
+            orders.append((f'A3c{i}', lpt_terms_3c(i), 'D3c', lambda g: g['D1']*g['D2'], 'f3c',
+                           _curl(i)))
+    return orders
+
+
+class LptTerms:
+    """handle_lpt_term (ic.py:1895-2057) driven by data, with the reference's book-keeping of
+    what the temporary grids hold (`notes`), so that a derivative the next term needs is not made
+    again.  One object per lattice; begin() at the start of every potential, as the reference
+    makes its dict of grids anew there.
+
+    potentials: name -> mesh in Fourier space.  tmps: the two temporary meshes of the
+    realisation size; tmps_dealias: the two of the dealiasing size, or None.  A mesh is anything
+    with the lpt_* and transform methods of PotentialMesh: the host tests pass recorders.
+
+    Where the reference copies a derivative into the second temporary grid to square it
+    (ic.py:2005-2009), the two names swap their grids instead and the product reads one grid
+    twice: the names hold what the reference's hold, and no copy is made."""
+
+    def __init__(self, potentials, tmps, tmps_dealias=None, watch=None):
+        self.potentials = potentials
+        self.dealias = tmps_dealias is not None
+        self.grids = {f'tmp{n}': (tmp, tmps_dealias[n] if self.dealias else tmp)
+                      for n, tmp in enumerate(tmps)}
+        self.gridsize = tmps[0].gridsize
+        self.gridsize_dealias = self.grids['tmp0'][1].gridsize
+        self.fft_factor = float(self.gridsize_dealias)**(-3)
+        self.watch = watch or _Stopwatch(None)
+        self.notes = {}
+        self.begin()
+
+    def begin(self):
+        self.order = sorted(self.grids)
+
+    def take_tmp(self):
+        """get_tmpgrid (ic.py:2063-2074): the first temporary grid, which then goes last"""
+        name = self.order.pop(0)
+        self.order.append(name)
+        return name
+
+    def release_tmp(self):
+        """the realisation-size grid the displacement uses after a potential is built
+        (ic.py:1583-1584): whatever it held is gone"""
+        name = self.take_tmp()
+        self.notes.pop(name, None)
+        return self.grids[name][0]
+
+    def diff_ifft(self, pot, name):
+        """diff_ifft (ic.py:2093-2103) of a potential's derivative into the named grid"""
+        Φ, (dim0, dim1) = self.potentials[pot[0]], (pot[1:] + (-1,))[:2]
+        work = self.grids[name][1]
+        with self.watch('k-space'):
+            if self.dealias:
+                work.lpt_diff_enlarge(Φ, dim0, dim1)
+            else:
+                work.lpt_diff(Φ, dim0, dim1)
+        with self.watch('transforms'):
+            work.poisson_backward()
+
+    def __call__(self, term):
+        output, operation, factor, pots = term
+        n_pot = len(pots)
+        if self.dealias:  # every dealiasing step but the last brings its own M⁻³ (ic.py:1956-1958)
+            factor *= self.fft_factor**(n_pot - 2)
+        notes = self.notes
+        # reuse what the temporary grids hold (ic.py:1962-1984): the first potential in front
+        # (it becomes the base grid), else the second at the back (the temporary grid)
+        unique = list(dict.fromkeys(pots))
+        for n, pot in enumerate(unique[:2]):
+            if pot not in notes.values():
+                continue
+            name_reuse = next(name for name in notes if notes[name] == pot)
+            others = [name for name in self.order if name != name_reuse]
+            self.order = [name_reuse] + others if n == 0 else others + [name_reuse]
+            break
+        base = self.take_tmp()
+        if notes.get(base) != pots[0]:
+            self.diff_ifft(pots[0], base)
+        notes.pop(base, None)
+        tmp = self.take_tmp()
+        Φ_out = self.potentials[output]
+        for n, pot in enumerate(pots[1:], 1):
+            factors = (base, tmp)
+            if n == 1 and pot == pots[0]:
+                self.grids[base], self.grids[tmp] = self.grids[tmp], self.grids[base]
+                factors = (tmp, tmp)
+            elif notes.get(tmp) != pot:
+                self.diff_ifft(pot, tmp)
+            notes[tmp] = pot
+            x, y = (self.grids[name][1] for name in factors)
+            work = self.grids[base][1]
+            last = (n == n_pot - 1)
+            with self.watch('products'):
+                if last and not self.dealias:
+                    # the last product and the move to the output grid (ic.py:2020-2057)
+                    Φ_out.lpt_product(x, y, operation, factor)
+                else:
+                    work.lpt_product(x, y, '=')
+            if self.dealias:
+                with self.watch('transforms'):
+                    work.fft_forward()
+                if not last:  # ic.py:2023-2026
+                    with self.watch('k-space'):
+                        work.lpt_dealias_cube(self.gridsize)
+                    with self.watch('transforms'):
+                        work.poisson_backward()
+        if self.dealias:  # shrink, staying in Fourier space, and move (ic.py:2029-2057)
+            with self.watch('k-space'):
+                Φ_out.lpt_shrink_accumulate(self.grids[base][1], operation, factor)
+
+
+def carryout_lpt(orders, terms, growth_factors, a, H, mass, particles=(None, None, 0),
+                 on_potential=None):
+    """The potentials above the first for one lattice and their displacements (carryout_2lpt
+    ... carryout_3lpt_c, ic.py:1539-1848).  orders: lpt_orders(lpt); terms: an LptTerms, which
+    holds the meshes; particles: (pos, mom, index_bgn) for lpt_displace."""
+    pos, mom, index_bgn = particles
+    watch = terms.watch
+    for name, term_list, D, denominator, f, passes in orders:
+        Φ = terms.potentials[term_list[0][0]]
+        potential_factor = terms.fft_factor*growth_factors[D]/denominator(growth_factors)
+        velocity_factor = a*H*growth_factors[f]
+        terms.begin()
+        for term in term_list:
+            terms(term)
+        if not terms.dealias:
+            with watch('transforms'):
+                Φ.fft_forward()
+        with watch('k-space'):
+            Φ.lpt_potential(Φ, None, factor=potential_factor)
+        if on_potential is not None:
+            on_potential(name, Φ, potential_factor)
+        tmp = terms.release_tmp()
+        for dim_diff, factor, dim in passes:
+            with watch('k-space'):
+                tmp.lpt_diff(Φ, dim_diff, -1, factor)
+            with watch('transforms'):
+                tmp.poisson_backward()
+            with watch('particles'):
+                tmp.lpt_displace(pos, mom, dim, 1.0, velocity_factor*(a*mass), index_bgn)
+
+
 def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_factors=None,
-                      cosmology=None, components_all=None, timings=None):
+                      cosmology=None, components_all=None, timings=None, extended=False,
+                      on_potential=None):
     """Realise a particle component at scale factor a (realize_particles, ic.py:1199-1400):
     particles on their lattice, displaced and boosted by 1LPT and, with
     realization_options['lpt'] = 2, 2LPT; positions wrapped into [0, boxsize).
 
+    extended: carry out realization_options['lpt'] = 3 and ['dealias'] = True (Orszag's 3/2 rule
+      on every product of grids) as well.  Without it both are refused by name, as they have
+      been since the realisation was built and as the tests of that scope pin word for word; the
+      wider scope is opted into, as the fluid solvers are.  ic.realize forwards the keyword.
+    on_potential: called as on_potential(name, mesh, factor) after every potential above the
+      first is built ('Φ2', 'Φ3a', 'Φ3b', 'A3c0', 'A3c1', 'A3c2': the last five share a mesh).
+
     amplitudes: the k²-indexed table of δ (amplitudes_from_power, or the caller's own transfer
       functions, signed as they wish); amplitudes_θ: that of θ, needed without back-scaling.
     growth_factors: dict with the reference's keys ('D1', 'f1', 'D2', 'f2', ...) at a; needed
-      with back-scaling or 2LPT.
+      with back-scaling or 2LPT ('D3a', 'f3a', 'D3b', 'f3b', 'D3c', 'f3c' too with 3LPT).
     cosmology: an integration.Cosmology (H(a)); default: one of the component's parameters.
     components_all: every component of the run; those that are particles with mass -1 are the
       ones to be realised and decide the lattice of each (1: sc, 2: bcc, 4: fcc by tally).
     timings: a dict that receives milliseconds by kind of pass (synchronises)."""
     options = realization_options(component)
-    _check_scope(component, options)
+    _check_scope(component, options, extended)
     p = component.params
     backscale, lpt = bool(options['backscale']), int(options['lpt'])
+    dealias = bool(options['dealias']) and lpt >= 2  # 1LPT has no product to dealias
     if not backscale and amplitudes_θ is None:
         raise ConceptGPUError(f'{component.name}: without back-scaling the momenta come from '
                               'the amplitudes of θ: pass amplitudes_θ')
     growth_factors = dict(growth_factors or {})
     if backscale or lpt > 1:
-        need = ('D1', 'f1') + (('D2', 'f2') if lpt > 1 else ())
+        need = ('D1', 'f1') + (('D2', 'f2') if lpt > 1 else ()) + (
+            ('D3a', 'f3a', 'D3b', 'f3b', 'D3c', 'f3c') if lpt > 2 else ())
         missing = [key for key in need if key not in growth_factors]
         if missing:
             raise ConceptGPUError(f'{component.name}: growth factors {missing} are needed')
@@ -425,13 +675,22 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
     if not backscale:
         amplitudes_dev[1] = _amplitudes_dev(component, amplitudes_θ, gridsize)
     watch = _Stopwatch(timings)
-    # Φ⁽¹⁾ and one temporary grid; 2LPT: Φ⁽²⁾ and a second temporary grid (ic.py:1304-1312)
+    # Φ⁽¹⁾ and one temporary grid; 2LPT: Φ⁽²⁾ and a second temporary grid; 3LPT: Φ⁽³⁾, which
+    # holds Φ⁽³ᵃ⁾, Φ⁽³ᵇ⁾ and the three A⁽³ᶜ⁾ᵢ in turn; dealiasing: two enlarged temporary grids
+    # (ic.py:1304-1325)
     from .mesh import get_mesh
-    def grid(role):
-        return get_mesh(gridsize, p.boxsize, p.nghosts, p.cell_centered, role=role,
+    def grid(role, size=gridsize):
+        return get_mesh(size, p.boxsize, p.nghosts, p.cell_centered, role=role,
                         device=component.device)
     Φ1, tmp0 = grid('lpt Φ1'), grid('lpt tmp0')
     Φ2, tmp1 = (grid('lpt Φ2'), grid('lpt tmp1')) if lpt >= 2 else (None, tmp0)
+    Φ3 = grid('lpt Φ3') if lpt >= 3 else None
+    potentials = {'Φ1': Φ1, 'Φ2': Φ2, 'Φ3': Φ3}
+    gridsize_dealias = dealias_gridsize(gridsize) if dealias else gridsize
+    tmps_dealias = None
+    if dealias:
+        tmps_dealias = (grid('lpt tmp0 dealias', gridsize_dealias),
+                        grid('lpt tmp1 dealias', gridsize_dealias))
     with _host_timer(timings, 'noise (host)'):
         noise = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
                                           p.primordial_phase_shift, p)
@@ -471,38 +730,10 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
             else:
                 displace(Φ1, tmp1, 0.0, 1*(a*mass))
         if lpt >= 2:
-            # 2LPT (carryout_2lpt, ic.py:1539-1589):
-            #   ∇²Φ⁽²⁾ = D⁽²⁾/(D⁽¹⁾)² (-Φ,₀₀Φ,₁₁ - Φ,₁₁Φ,₂₂ - Φ,₂₂Φ,₀₀ + Φ,₀₁² + Φ,₁₂² + Φ,₂₀²)
-            # with a derivative grid kept where the next term needs it, as the reference's
-            # notes do: seven inverse transforms for the six terms
-            potential_factor = (float(gridsize)**(-3)*growth_factors['D2']
-                                / growth_factors['D1']**2)
-            velocity_factor = a*H*growth_factors['f2']
-
-            def derivative(tmp, i, j):
-                with watch('k-space'):
-                    tmp.lpt_diff(Φ1, i, j)
-                with watch('transforms'):
-                    tmp.poisson_backward()
-
-            def term(operation, x, y, factor=1.0):
-                with watch('products'):
-                    Φ2.lpt_product(x, y, operation, factor)
-            derivative(tmp0, 0, 0)
-            derivative(tmp1, 1, 1)
-            term('=', tmp0, tmp1, -1.0)
-            derivative(tmp0, 2, 2)
-            term('-=', tmp1, tmp0)
-            derivative(tmp1, 0, 0)
-            term('-=', tmp0, tmp1)
-            for i, j in ((0, 1), (1, 2), (0, 2)):
-                derivative(tmp0, i, j)
-                term('+=', tmp0, tmp0)
-            with watch('transforms'):
-                Φ2.fft_forward()
-            with watch('k-space'):
-                Φ2.lpt_potential(Φ2, None, factor=potential_factor)
-            displace(Φ2, tmp0, 1.0, velocity_factor*(a*mass))
+            # 2LPT and 3LPT (ic.py:1352-1380): the notes start empty on every lattice
+            terms = LptTerms(potentials, (tmp0, tmp1), tmps_dealias, watch)
+            carryout_lpt(lpt_orders(lpt), terms, growth_factors, a, H, mass,
+                         (pos, mom, index_bgn), on_potential)
         id_bgn += n_particles
         index_bgn += n_particles
     tally['particles_tally'] = id_bgn
@@ -516,7 +747,8 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
     component.tiles_exact = False
     component._store.touch_mom()
     watch.finish()
-    return {'Φ1': Φ1, 'Φ2': Φ2, 'gridsize': gridsize}
+    return {'Φ1': Φ1, 'Φ2': Φ2, 'Φ3': Φ3, 'gridsize': gridsize,
+            'gridsize_dealias': gridsize_dealias}
 
 
 # ---- fluids (ic.py:297-511, 708-764) ---------------------------------------------------------------

@@ -162,6 +162,9 @@ SYMBOLS = {
     'cg_lpt_diff': (_int, [_vp, _vp, _int, _int, _dbl]),
     'cg_lpt_product': (_int, [_vp, _vp, _vp, _int, _dbl]),
     'cg_lpt_displace': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _dbl, _dbl]),
+    'cg_lpt_diff_enlarge': (_int, [_vp, _vp, _int, _int, _dbl]),
+    'cg_lpt_dealias_cube': (_int, [_vp, _i64]),
+    'cg_lpt_shrink_accumulate': (_int, [_vp, _vp, _int, _dbl]),
     'cg_realize_grid': (_int, [_vp, _vp, _vp, _i64, _int, _int]),
     'cg_fluid_from_mesh': (_int, [_vp, _vp, _int, _dbl, _dbl]),
     'cg_fluid_kt_step': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _dbl, _dbl,

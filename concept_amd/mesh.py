@@ -549,6 +549,24 @@ class PotentialMesh:
                                 float(factor)))
         return self
 
+    def lpt_diff_enlarge(self, source, dim0, dim1=-1, factor=1.0):
+        """fourier_diff of the smaller `source` and its enlargement into this mesh in one pass
+        (diff_ifft before its transform, ic.py:2093-2101): zero beyond the cube |k| < N/2"""
+        check(_L.cg_lpt_diff_enlarge(self._ctx, source._ctx, int(dim0), int(dim1), float(factor)))
+        return self
+
+    def lpt_dealias_cube(self, gridsize_small):
+        """nullify_modes(slab, 'beyond cube of |k| < gridsize_small/2') in place (ic.py:2025)"""
+        check(_L.cg_lpt_dealias_cube(self._ctx, int(gridsize_small)))
+        return self
+
+    def lpt_shrink_accumulate(self, source, operation='=', factor=1.0):
+        """this mesh (= | += | -=) factor*(the larger `source` shrunk to this size), in Fourier
+        space (resize_grid and the move to the output grid, ic.py:2029-2057)"""
+        check(_L.cg_lpt_shrink_accumulate(self._ctx, source._ctx,
+                                          ('=', '+=', '-=').index(operation), float(factor)))
+        return self
+
     def lpt_displace(self, pos, mom, dim, pos_factor, mom_factor, index_bgn=0):
         """displace_particles (ic.py:2249-2280) from this mesh's real-space content: the
         gridsize**3 rows of pos / mom from index_bgn on, row (i*g + j)*g + k from cell (i, j, k).

@@ -863,6 +863,27 @@ int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double factor);
 int cg_lpt_displace(cg_ctx *psi, double *pos /*DEV or NULL*/, double *mom /*DEV or NULL*/,
                     int64_t n, int64_t index_bgn, int dim, double pos_factor, double mom_factor);
 
+/* --- initial conditions: 3LPT and Orszag dealiasing (ic.py:1304-1380, 1895-2103) -----------
+ * The passes that move a grid between the realisation size N and the dealiasing size
+ * M = 3N/2 (+1 when that is odd), each one trip over its output.  Both contexts are single
+ * domains of one box with even grid sizes, M > N, in Fourier space.  The size-change phase is
+ * copy_modes' (mesh.py:1302): theta = (pi/N_onto - pi/N_from)*((ki + kj) + kk).
+ * cg_lpt_diff_enlarge: diff_ifft before its transform (ic.py:2093-2101): fourier_diff
+ *   (mesh.py:3466-3510) of src (size N) and resize_grid to dst (size M; mesh.py:916-922) at once.
+ *   Every mode of dst is written exactly once: inside the cube |k| < N/2 the derivative of src's
+ *   mode, rounded as cg_lpt_diff rounds it, then rotated by theta; everywhere else (src's Nyquist
+ *   planes, the origin and all of dst's Nyquist planes included) zero, with no read.
+ * cg_lpt_dealias_cube: nullify_modes(slab, 'beyond cube of |k| < n_small/2') (ic.py:2025,
+ *   mesh.py:3585-3622) in place: zeros where they belong, nothing read, the cube keeps its bits.
+ * cg_lpt_shrink_accumulate: resize_grid down to out's size (nullify 'nyquist' + copy_modes,
+ *   mesh.py:912-922) and the move to the output grid of handle_lpt_term (ic.py:2038-2057) at
+ *   once, in Fourier space: out (op 0 '=', 1 '+=', 2 '-=') factor*(src's mode rotated by theta),
+ *   rotation, factor and sum rounded in turn, the multiplication by a factor of 1 left out.  On
+ *   out's Nyquist planes '=' writes zero and '+=' / '-=' leave the value unchanged. */
+int cg_lpt_diff_enlarge(cg_ctx *dst, cg_ctx *src, int dim0, int dim1, double factor);
+int cg_lpt_dealias_cube(cg_ctx *mesh, int64_t n_small);
+int cg_lpt_shrink_accumulate(cg_ctx *out, cg_ctx *src, int op, double factor);
+
 /* --- initial conditions: fluid realisation (ic.py:400-477, 708-764) -----------------------
  * cg_realize_grid: realize_grid (ic.py:708-764) without a lattice shift, for the scalar
  *   (tensor_rank 0) and the vector (tensor_rank 1, component index0) structure, from the

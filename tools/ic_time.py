@@ -3,7 +3,15 @@ noise (host, wall clock), upload of the noise slab, k-space passes (lpt_potentia
 transforms, grid products and particle passes (lattice, displacement, wrap), hipEvents around
 every pass.
 
-  python tools/ic_time.py [--gridsize 512] [--lpt 2] [--runs 2] [--out profiles/ic_512.json]
+  python tools/ic_time.py [--gridsize 512] [--lpt 2] [--dealias] [--runs 2] [--fused]
+                          [--out profiles/ic_512.json]
+
+--lpt 3 and --dealias go through realize_particles(extended=True).  --fused also times, on the
+realisation's own meshes in this process, each of the three passes between the realisation size N
+and the dealiasing size M against the unfused passes it replaces: lpt_diff + zero_fourier +
+copy_modes_from for lpt_diff_enlarge, copy_modes_from into a nullified slab + an accumulation
+for lpt_shrink_accumulate, nothing shorter than itself for lpt_dealias_cube (listed with the
+whole-slab zeroing for scale); median of 5 after a warm-up, hipEvents.
 
 A made-up power spectrum, back-scaling on, fixed growth factors: the passes do not depend on
 the numbers.  The first run warms up (plans, allocations); the last one is reported.  A record,
@@ -20,10 +28,60 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def fused_vs_unfused(grids, p, device):
+    from concept_amd.mesh import get_mesh
+    n, m = grids['gridsize'], grids['gridsize_dealias']
+    if m == n:
+        raise SystemExit('--fused needs --dealias')
+
+    def mesh(role, size):
+        return get_mesh(size, p.boxsize, p.nghosts, p.cell_centered, role=role, device=device)
+    Φ, tmp, out = grids['Φ1'], mesh('lpt tmp0', n), mesh('lpt tmp1', n)
+    big = mesh('lpt tmp0 dealias', m)
+
+    def median_ms(f):
+        f()
+        times = []
+        for _ in range(5):
+            e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+            e0.record()
+            f()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1))
+        return sorted(times)[2]
+
+    def enlarge_unfused():
+        tmp.lpt_diff(Φ, 0, 1)
+        big.copy_modes_from(tmp)  # zero_fourier, then the copy with the phase
+
+    def shrink_unfused():
+        tmp.copy_modes_from(big)  # the same into a slab of size N
+        out.fourier_operate(source=tmp, operation='+=')
+
+    slab_bytes = {'N': 8*n*n*(n + 2), 'M': 8*m*m*(m + 2)}
+    ms = {'diff_enlarge fused': median_ms(lambda: big.lpt_diff_enlarge(Φ, 0, 1)),
+          'diff_enlarge unfused': median_ms(enlarge_unfused),
+          'shrink_accumulate fused': median_ms(lambda: out.lpt_shrink_accumulate(big, '+=', 0.5)),
+          'shrink_accumulate unfused': median_ms(shrink_unfused),
+          'dealias_cube': median_ms(lambda: big.lpt_dealias_cube(n)),
+          'zero_fourier (M)': median_ms(big.zero_fourier)}
+    # what the expectation prices: one write of the M slab (enlarge), one read of the cube's
+    # part of it plus read and write of the N slab (shrink), the write of M less the cube (cube)
+    ms['slab bytes'] = slab_bytes
+    ms['TB/s'] = {
+        'diff_enlarge fused': (slab_bytes['N'] + slab_bytes['M'])/ms['diff_enlarge fused']/1e9,
+        'shrink_accumulate fused': 3*slab_bytes['N']/ms['shrink_accumulate fused']/1e9,
+        'dealias_cube': (slab_bytes['M'] - slab_bytes['N'])/ms['dealias_cube']/1e9}
+    return ms
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gridsize', type=int, default=512)
     ap.add_argument('--lpt', type=int, default=2)
+    ap.add_argument('--dealias', action='store_true')
+    ap.add_argument('--fused', action='store_true')
     ap.add_argument('--runs', type=int, default=2)
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
@@ -34,10 +92,14 @@ def main():
         'boxsize': L, 'H0': 0.07, 'Ωb': 0.05, 'Ωcdm': 0.25, 'a_begin': 0.02,
         'potential_options': {'gridsize': {'gravity': {'pm': g}}},
         'select_forces': {'all': {'gravity': 'pm'}},
-        'realization_options': {'lpt': args.lpt, 'backscale': True}})
+        'realization_options': {'lpt': args.lpt, 'backscale': True, 'dealias': args.dealias}})
+    extended = args.lpt > 2 or args.dealias
     k = np.geomspace(1e-4, 100, 400)
     amplitudes = ic.amplitudes_from_power(k, 2e3*k/(1 + (k/0.1)**2)**1.5, g, L)
     growth = {'D1': 0.02, 'f1': 1.0, 'D2': -3/7*0.02**2, 'f2': 2.0}
+    if args.lpt > 2:
+        growth.update({'D3a': -1/3*0.02**3, 'f3a': 3.0, 'D3b': 10/21*0.02**3, 'f3b': 3.0,
+                       'D3c': -1/7*0.02**3, 'f3c': 3.0})
     c = Component('matter', 'matter', N=g**3, mass=-1)
     c.keep_order = False
     record = None
@@ -46,15 +108,19 @@ def main():
         timings = {}
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        ic.realize_particles(c, p.a_begin, amplitudes, growth_factors=growth, timings=timings)
+        grids = ic.realize_particles(c, p.a_begin, amplitudes, growth_factors=growth,
+                                     timings=timings, **({'extended': True} if extended else {}))
         torch.cuda.synchronize()
         record = {'device': torch.cuda.get_device_name(), 'gridsize': g, 'particles': g**3,
-                  'lpt': args.lpt, 'backscale': True,
+                  'lpt': args.lpt, 'backscale': True, 'dealias': args.dealias,
+                  'gridsize_dealias': grids.get('gridsize_dealias', g),
                   'wall_ms': (time.perf_counter() - t0)*1e3,
                   'ms': {k_: v for k_, v in timings.items() if not k_.endswith(' passes')},
                   'passes': {k_[:-7]: v for k_, v in timings.items() if k_.endswith(' passes')}}
         record['gpu_ms'] = sum(v for k_, v in record['ms'].items() if k_ != 'noise (host)')
     assert bool(((c.pos >= 0) & (c.pos < L)).all())
+    if args.fused:
+        record['fused_vs_unfused_ms'] = fused_vs_unfused(grids, p, c.device)
     text = json.dumps(record, indent=1)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
