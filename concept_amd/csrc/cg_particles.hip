@@ -216,23 +216,14 @@ __global__ __launch_bounds__(256) void k_tile_scatter(
         }
         int rs, rl;
         wave_runs(key, lane, rs, rl);
-        unsigned first = 0;
-        if (lane == rs && key != kNoTile) {
-            // A run that does not fit its bucket means the histogram was not made from these
-            // positions and momenta (a prepared histogram gone stale: something changed mom
-            // between cg_gather_kick_tiled_prepare and this sort).  Equal totals with unequal
-            // buckets always overflow one of them, so this check is complete; the run is
-            // dropped (never stored outside its bucket) and the context's error word is set
-            // (cg_error_flags).
-            const unsigned o0 = offset[key], room = offset[key + 1] - o0;
-            const unsigned local = atomicAdd(&cursor[key], (unsigned)rl);
-            first = o0 + local;
-            if (local + (unsigned)rl > room) {
-                atomicOr(err_flags, (unsigned)CG_ERR_STALE_HISTOGRAM);
-                first = kNoTile;
-            }
-        }
-        first = __shfl(first, rs);
+        // A run that does not fit its bucket means the histogram was not made from these
+        // positions and momenta (a prepared histogram gone stale: something changed mom
+        // between cg_gather_kick_tiled_prepare and this sort).  Equal totals with unequal
+        // buckets always overflow one of them, so this check is complete; the run is
+        // dropped (never stored outside its bucket) and the context's error word is set
+        // (cg_error_flags).
+        const unsigned first = reserve_run(offset, cursor, key, lane, rs, rl, kNoCapacity,
+                                           err_flags, (unsigned)CG_ERR_STALE_HISTOGRAM);
         // particles of other domains (kNoTile) are dropped: the host exchanges them before
         // sorting; table[last] = number kept
         const bool valid = p < n && key != kNoTile && first != kNoTile;

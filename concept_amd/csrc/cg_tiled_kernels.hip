@@ -15,6 +15,7 @@
 #include "cg_chunk_box.h"  // the CIC index and weights (cic1, in 32-bit cell arithmetic), wrap
 #include "cg_internal.h"
 #include "cg_tiles.h"
+#include <type_traits>
 
 // two doubles at 8-byte alignment (the xy of an xyz record)
 typedef double d2u8 __attribute__((ext_vector_type(2), aligned(8)));
@@ -263,6 +264,48 @@ static TileOrder tile_order_args(const cg_ctx *c) {
     return o;
 }
 
+// The walk behind the list: the tile of the walk's block b, and whether the order knows that tile
+// (has a place for it in ord.rank).
+struct PlainWalk {
+    // (the order knows the first `nranked` tiles — those that hold particles; a slab domain's
+    // ghost row behind them is walked as ever)
+    unsigned ntiles, nranked;
+    __device__ __forceinline__ unsigned operator()(unsigned b) const { return tile_for_block(b, ntiles); }
+    __device__ __forceinline__ bool ranked(unsigned tile) const { return tile < nranked; }
+};
+struct GroupedWalk {
+    unsigned ntiles, nt;
+    __device__ __forceinline__ unsigned operator()(unsigned b) const {
+        return tile_for_block_grouped(b, ntiles, nt, nt);
+    }
+    __device__ __forceinline__ bool ranked(unsigned) const { return true; }
+};
+// workgroup -> tile (see "heavy tiles first" above).  tile == kNoTile: a block in front that the
+// list does not reach — it ends at once.  place: of the WALK's tile on the list (all ones: none);
+// a tile with a place among the blocks in front (place < ord.cap; uniform) was theirs, and the
+// walk's workgroup ends.  WHEN it ends is the kernel's: the place is loaded here and not waited
+// for, so a kernel that looks at it after its next loads (the gather-kick: behind the tile's
+// offsets) pays no dependent load in front of its first loads — that was the 8.45 -> 8.78 ms
+// of a table read by every workgroup.
+struct TileTake {
+    unsigned tile, place;
+    bool none;
+};
+template <class Walk>
+__device__ __forceinline__ TileTake take_tile(const TileOrder &ord, const Walk &walk) {
+    TileTake t{kNoTile, ~0u, false};
+    if (ord.list && blockIdx.x < ord.cap) {
+        if (blockIdx.x < (unsigned)__builtin_amdgcn_readfirstlane((int)*ord.n))
+            t.tile = (unsigned)__builtin_amdgcn_readfirstlane((int)ord.list[blockIdx.x]);
+        else
+            t.none = true;
+    } else {
+        t.tile = walk(blockIdx.x - (ord.list ? ord.cap : 0u));
+        if (ord.list && walk.ranked(t.tile)) t.place = ord.rank[t.tile];
+    }
+    return t;
+}
+
 // ---------------------------------------------------------------------------
 // tiled deposit, owner-computes ("pull") form
 //
@@ -289,17 +332,10 @@ __global__ __launch_bounds__(512) void k_deposit_cic_pull(
     __shared__ unsigned seg_beg[64], seg_end_prefix[65];
     // (ord: heavy tiles first, see cgk_tile_order; it knows the first `nordered` tiles — those
     // that hold particles; a slab domain's ghost row behind them is walked as ever)
-    unsigned tile;
-    if (ord.list && blockIdx.x < ord.cap) {
-        if (blockIdx.x >= (unsigned)__builtin_amdgcn_readfirstlane((int)*ord.n)) return;
-        tile = (unsigned)__builtin_amdgcn_readfirstlane((int)ord.list[blockIdx.x]);
-    } else {
-        const unsigned b = blockIdx.x - (ord.list ? ord.cap : 0u);
-        tile = tile_for_block(b, nblocks);
-        if (ord.list && tile < nordered &&
-            (unsigned)__builtin_amdgcn_readfirstlane((int)ord.rank[tile]) < ord.cap)
-            return;
-    }
+    const TileTake take = take_tile(ord, PlainWalk{nblocks, nordered});
+    const unsigned tile = take.tile;
+    if (take.none || (unsigned)__builtin_amdgcn_readfirstlane((int)take.place) < ord.cap)
+        return;
     const int tc = tile % nt, tb = (tile / nt) % nt, ta = tile / (nt * nt);
     const int Ni = (int)N;
     const int T0a = (int)xm.x0 + ta * T, T0b = tb * T, T0c = tc * T;
@@ -373,6 +409,18 @@ __global__ __launch_bounds__(512) void k_deposit_cic_pull(
     }
 }
 
+// the one dispatch over the tile extent: f(std::integral_constant<int, T>) for the context's T
+template <class F>
+static int with_tile_extent(const cg_ctx *c, const char *who, F f) {
+    switch (c->tiles.tx) {
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        default: cg_set_error("%s: tile extent %d", who, c->tiles.tx); return 1;
+    }
+}
+
 template <int T>
 static int launch_deposit(cg_ctx *c, const double *pos, const unsigned *table,
                           const unsigned *count, double contribution, int accumulate) {
@@ -384,34 +432,33 @@ static int launch_deposit(cg_ctx *c, const double *pos, const unsigned *table,
     if (cgk_tile_order(c, table, count)) return 1;
     const TileOrder order = tile_order_args(c);
     const unsigned nordered = (unsigned)c->ntiles;
-    if (accumulate)
-        hipLaunchKernelGGL((k_deposit_cic_pull<T, true>), dim3(nb + order.cap), dim3(512), 0, c->stream, pos,
-                           table, count, c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.ntx, c->tiles.nty,
-                           nb, c->xmap, c->geom_deposit, contribution, order, nordered);
-    else
-        hipLaunchKernelGGL((k_deposit_cic_pull<T, false>), dim3(nb + order.cap), dim3(512), 0, c->stream, pos,
-                           table, count, c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.ntx, c->tiles.nty,
-                           nb, c->xmap, c->geom_deposit, contribution, order, nordered);
+    const auto kern = accumulate ? k_deposit_cic_pull<T, true> : k_deposit_cic_pull<T, false>;
+    hipLaunchKernelGGL(kern, dim3(nb + order.cap), dim3(512), 0, c->stream, pos, table, count,
+                       c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.ntx, c->tiles.nty, nb,
+                       c->xmap, c->geom_deposit, contribution, order, nordered);
     return 0;
 }
 
 int cgk_deposit_cic_tiled(cg_ctx *c, const double *pos, i64 n, const unsigned *tile_offset,
                           const unsigned *count, double contribution, int accumulate) {
     (void)n;
-    const int T = c->tiles.tx;
-    switch (T) {
-        case 16: if (launch_deposit<16>(c, pos, tile_offset, count, contribution, accumulate)) return 1; break;
-        case 8: if (launch_deposit<8>(c, pos, tile_offset, count, contribution, accumulate)) return 1; break;
-        case 4: if (launch_deposit<4>(c, pos, tile_offset, count, contribution, accumulate)) return 1; break;
-        case 2: if (launch_deposit<2>(c, pos, tile_offset, count, contribution, accumulate)) return 1; break;
-        default: cg_set_error("cgk_deposit_cic_tiled: tile extent %d", T); return 1;
-    }
+    if (with_tile_extent(c, "cgk_deposit_cic_tiled", [&](auto t) {
+            return launch_deposit<decltype(t)::value>(c, pos, tile_offset, count, contribution,
+                                                      accumulate);
+        }))
+        return 1;
     CG_LAUNCH_CHECK();
     return 0;
 }
 
 // ---------------------------------------------------------------------------
 // tiled gather + finite difference + kick
+//
+// k_gather_kick_tiled reads top to bottom as: take the tile (take_tile above); find the
+// particle range (GatherLds::load_segments for a gapped input); stage the block (stage_block);
+// per batch of 512 particles load (GatherLds::region_slot), gather (two stencil loops over
+// add_cell), kick, drift, and run the mode's epilogue (prep_epilogue, fused_epilogue with
+// reserve_run of cg_tiles.h, the |mom|^2 sum).
 // ---------------------------------------------------------------------------
 // One force-cell value per dimension exactly as diff_domaingrid forms it
 // (mesh.py:4966-4981); P(da, db, dc) reads the potential at an offset from
@@ -430,6 +477,20 @@ __device__ __forceinline__ void force_cell(const P &phi, double c1, double c2, d
     }
 }
 
+// one cell of a particle's cloud: its force, weighted by wij * wk, added to the particle's —
+// the accumulation of the staged and of the direct stencil.  (The product stands behind the
+// force on purpose: in front of it the fused pass spills, see DESIGN.md.)
+template <int ORDER, class P>
+__device__ __forceinline__ void add_cell(const P &phi, double c1, double c2, double wij,
+                                         double wk, double (&val)[3]) {
+    double fx, fy, fz;
+    force_cell<ORDER>(phi, c1, c2, fx, fy, fz);
+    const double w = wij * wk;
+    val[0] += fx * w;
+    val[1] += fy * w;
+    val[2] += fz * w;
+}
+
 // PREP: additionally histogram where every particle will be after the NEXT drift
 // (pos + mom_new*next_dtm, the arithmetic of k_tile_histogram<true>) into `count`, so
 // that cg_drift_sort can skip its own histogram pass over pos and mom.
@@ -445,21 +506,15 @@ struct PrepArgs {
     unsigned *emig_count;
     i64 emig_cap;
     // MODE 2 (fused kick + drift + scatter): the drifted particles with their kicked momenta go
-    // straight to their place in the next tile order.  start_out[k] = first slot of the region
+    // straight to their place in the next tile order.  fs.start_out[k] = first slot of the region
     // reserved for (tile, bucket) k (capacities predicted from the present populations,
-    // cg_predict_regions), count_out[k] = slots taken so far (zeroed before the launch; it ends
-    // as the new population).  A run that does not fit sets CG_ERR_BUCKET_OVERFLOW.
-    const unsigned *start_out;
-    unsigned *count_out;
-    double *pos_out, *mom_out;
-    const i64 *ids_in;
-    i64 *ids_out;
-    const i64 *aux_in;  // a second 64-bit column travelling with the particles (or null)
-    i64 *aux_out;
-    i64 out_capacity;   // rows of pos_out / mom_out (/ ids_out, aux_out)
+    // cg_predict_regions), fs.count_out[k] = slots taken so far (zeroed before the launch; it
+    // ends as the new population).  A run that does not fit sets CG_ERR_BUCKET_OVERFLOW.
+    // fs.aux_in: a second 64-bit column travelling with the particles (or null);
+    // fs.out_capacity: rows of pos_out / mom_out (/ ids_out, aux_out); fs.count_in: the input
+    // populations when the input itself is in regions with gaps (null: dense tile order).
+    FusedScatter fs;
     unsigned *err_flags;
-    // input populations when the input itself is in regions with gaps (null: dense tile order)
-    const unsigned *count_in;
     // x-slab domains: particles leaving the slab go to this row buffer (8 doubles each)
     double *emig_rows;
     unsigned *emig_rows_count;
@@ -482,7 +537,7 @@ struct PrepArgs {
 // plain block (they fit two workgroups either way).
 template <int ORDER, int T>
 struct GatherLds {
-    static constexpr int H = ORDER / 2, E = T + 1 + 2 * H, PL = E * E;
+    static constexpr int H = ORDER / 2, E = T + 1 + 2 * H, PL = E * E;  // cells [T0-H, T0+T+H]
     static constexpr bool compact = (ORDER == 2 && T == 16);
     static constexpr int main_planes = compact ? E - 2 : E;       // planes kept as E x E
     static constexpr int IN = E - 2;                                // interior of a compact plane
@@ -490,8 +545,100 @@ struct GatherLds {
     static constexpr int P_HI = P_LO + IN * IN;                     // compact plane a = E - 1
     static constexpr int doubles = compact ? P_HI + IN * IN : E * E * E;
     // index of block entry (a, b, c) for a in the main planes (compact: a = 1 .. E - 2)
-    __device__ static constexpr int main(int a, int b, int c) {
+    __host__ __device__ static constexpr int main(int a, int b, int c) {
         return ((a - (compact ? 1 : 0)) * E + b) * E + c;
+    }
+
+    // The segment tables of a gapped input (MODE 2; regions with gaps, PrepArgs::fs.count_in):
+    // the tile's 8 buckets' first slots, seg_beg(f), f = 0 .. 7, and the running sums of their
+    // populations, seg_pre(f), f = 0 .. 8, walked as one flat index.
+    // (MODE 2 only: the plain kernel's LDS block is sized so that three workgroups fit a CU
+    // to the byte — nothing may be added to it)
+    // They live in entries of the staged block that no stencil reads and the staging leaves
+    // alone (holds_seg): compact layout — the corners (a, 0, 0) of the planes a = 1 .. 4
+    // (seg_beg) and 5 .. 9 (seg_pre), two words each; plain layout — rows b = E - 1 (8 words)
+    // and b = 0 (9 words) of plane a = 0 (a particle's stencil reaches plane 0 only at rows
+    // H .. E-1-H; E >= 5 doubles per row).  seg_claims_hold() is these claims, asserted where
+    // the tables are used.
+    static constexpr int SEG_AT = (E - 1) * E;   // plain layout: block index of row (0, E - 1)
+    // the 32-bit word of the block (two per entry) that holds seg_beg(f) / seg_pre(f)
+    __host__ __device__ static constexpr int beg_word(int f) {
+        return compact ? 2 * main(1 + (f >> 1), 0, 0) + (f & 1) : 2 * SEG_AT + f;
+    }
+    __host__ __device__ static constexpr int pre_word(int f) {
+        return compact ? 2 * main(5 + (f >> 1), 0, 0) + (f & 1) : f;
+    }
+    __device__ __forceinline__ static unsigned &seg_beg(double *lds, int f) {
+        return ((unsigned *)lds)[beg_word(f)];
+    }
+    __device__ __forceinline__ static unsigned &seg_pre(double *lds, int f) {
+        return ((unsigned *)lds)[pre_word(f)];
+    }
+    // does the entry i2 = b * E + c of main plane a hold a segment table?  (whole rows in the
+    // plain layout: the staging tests a range)
+    __host__ __device__ static constexpr bool holds_seg(int a, int i2) {
+        return compact ? (i2 == 0 && a >= 1 && a <= 9) : (a == 0 && (i2 >= SEG_AT || i2 < E));
+    }
+    // Is block entry (a, b, c) read by the stencil of some particle of the tile?  A cloud's cells
+    // lie in [H, E - 1 - H]^3 and a difference leaves that range along one axis only.
+    __host__ __device__ static constexpr bool stencil_reads(int a, int b, int c) {
+        return (a >= H && a <= E - 1 - H) + (b >= H && b <= E - 1 - H) +
+                   (c >= H && c <= E - 1 - H) >= 2;
+    }
+    // every table word lies in a main-plane entry that no stencil reads and the staging leaves
+    // alone, and no two tables share an entry
+    __host__ __device__ static constexpr bool seg_claims_hold() {
+        for (int t = 0; t < 17; t++) {
+            const int e = (t < 8 ? beg_word(t) : pre_word(t - 8)) / 2;  // entry of the main planes
+            const int a = e / PL + (compact ? 1 : 0), i2 = e % PL;
+            if (e < 0 || e >= main_planes * PL) return false;
+            if (stencil_reads(a, i2 / E, i2 % E) || !holds_seg(a, i2)) return false;
+            for (int u = 8; t < 8 && u < 17; u++)
+                if (pre_word(u - 8) / 2 == e) return false;
+        }
+        return true;
+    }
+
+    // Fill the tables from the tile's 8 (start, population) pairs; -> the tile's population, by
+    // scalar loads (the tile is uniform): the tables are published by the barrier that ends the
+    // staging, which starts without waiting for them (a barrier here cost the pass from regions
+    // with gaps 0.2 ms against the dense order).
+    __device__ __forceinline__ static unsigned load_segments(double *lds,
+                                                             const unsigned *tile_offset,
+                                                             const unsigned *count_in,
+                                                             unsigned tile) {
+        static_assert(seg_claims_hold(), "a segment table lies in a block entry that is in use");
+        if (threadIdx.x < 64) {
+            const int f = threadIdx.x & 7;
+            unsigned cnt = count_in[8 * tile + f];
+            unsigned incl = cnt;
+#pragma unroll
+            for (int o = 1; o < 8; o <<= 1) {
+                unsigned v = __shfl_up(incl, o);
+                if (f >= o) incl += v;
+            }
+            if (threadIdx.x < 8) {
+                seg_beg(lds, f) = tile_offset[8 * tile + f];
+                seg_pre(lds, f + 1) = incl;
+                if (f == 0) seg_pre(lds, 0) = 0;
+            }
+        }
+        unsigned total = 0;
+#pragma unroll
+        for (int f = 0; f < 8; f++)
+            total += (unsigned)__builtin_amdgcn_readfirstlane((int)count_in[8 * tile + f]);
+        return total;
+    }
+    // flat index of a particle of the tile -> slot of its bucket's region
+    __device__ __forceinline__ static unsigned region_slot(double *lds, unsigned p) {
+        // bucket 0 (the tile's interior, (15/16)^3 of its particles) first: a wave that
+        // lies in it entirely — most do — skips the search (uniform branch)
+        if (p < seg_pre(lds, 1)) return seg_beg(lds, 0) + p;
+        int f = 0;
+#pragma unroll
+        for (int step = 4; step > 0; step >>= 1)
+            if (seg_pre(lds, f + step) <= p) f += step;
+        return seg_beg(lds, f) + (p - seg_pre(lds, f));
     }
 };
 // Wavefronts per SIMD the register allocation aims at (T = 16, order 2; 512-lane workgroups: 6
@@ -507,6 +654,138 @@ constexpr int gk_waves() {
     return MODE == 1 ? 4 : 6;
 }
 
+// Stage the potential tile + stencil halo.  Wave w takes the planes a = w, w+8, ...
+// of the E^3 block: the layer index and its 64-bit row base are wave-uniform
+// (scalar unit), a lane's (row, column) offsets inside a plane are 32-bit and the
+// same for every plane, so a load costs one instruction (scalar base + lane
+// offset) instead of the ~80 of per-element 64-bit index arithmetic this loop
+// used to spend — that arithmetic, not the stencil, was two thirds of the kernel's
+// VALU work (rocprofv3: 1060 VALU instructions per particle, VALUBusy 78 %).
+// All loads of a lane are issued before its first LDS store.
+// SEG: the entries that hold the segment tables are left alone.
+template <int ORDER, int T, bool SEG>
+__device__ __forceinline__ void stage_block(double *lds, const double *__restrict__ mesh,
+                                            const XMap &xm, i64 N, i64 ny, i64 pad, int T0a,
+                                            int T0b, int T0c) {
+    using BL = GatherLds<ORDER, T>;
+    constexpr int H = BL::H, E = BL::E;
+    constexpr bool COMPACT = BL::compact;
+    constexpr int PL = BL::PL;               // points per plane
+    constexpr int NP = (PL + 63) / 64;       // 64-lane passes per plane
+    constexpr int NA = (E + 7) / 8;          // planes per wave
+    const int Ni = (int)N;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int b0 = T0b - H, c0 = T0c - H;
+    const bool seam = b0 < 0 || c0 < 0 || b0 + E > Ni || c0 + E > Ni;
+    unsigned off[NP];  // gj*pad + gk
+    int cmp[COMPACT ? NP : 1];  // compact planes: (b-1)*IN + (c-1) of the interior, else -1
+#pragma unroll
+    for (int q = 0; q < NP; q++) {
+        int i2 = lane + 64 * q;
+        int b = i2 / E, c = i2 - b * E;
+        int gj = b0 + b, gk = c0 + c;
+        if (seam) {  // (tile-uniform) the block reaches across the periodic seam in y or z
+            gj += (gj < 0 ? Ni : 0) - (gj >= Ni ? Ni : 0);
+            gk += (gk < 0 ? Ni : 0) - (gk >= Ni ? Ni : 0);
+        }
+        off[q] = (unsigned)gj * (unsigned)pad + (unsigned)gk;
+        if (COMPACT)
+            cmp[q] = (b >= 1 && b <= E - 2 && c >= 1 && c <= E - 2)
+                         ? (b - 1) * BL::IN + (c - 1) : -1;
+    }
+    double v[NA][NP];
+#pragma unroll
+    for (int s = 0; s < NA; s++) {
+        const int a = __builtin_amdgcn_readfirstlane(wave) + 8 * s;  // wave-uniform
+        if (a < E) {
+            const double *plane = mesh + cg_xlayer(xm, (i64)(T0a - H + a), N) * ny * pad;
+            const bool edge = COMPACT && (a == 0 || a == E - 1);  // (uniform)
+#pragma unroll
+            for (int q = 0; q < NP; q++) {
+                const bool want = (PL % 64 == 0 || lane + 64 * q < PL) &&
+                                  (!edge || cmp[COMPACT ? q : 0] >= 0);
+                if (want) v[s][q] = plane[off[q]];
+            }
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < NA; s++) {
+        const int a = __builtin_amdgcn_readfirstlane(wave) + 8 * s;
+        if (a >= E) continue;
+        if (COMPACT && (a == 0 || a == E - 1)) {
+            // a compact boundary plane: its interior only (the branch is wave-uniform)
+            const int base = a == 0 ? BL::P_LO : BL::P_HI;
+#pragma unroll
+            for (int q = 0; q < NP; q++)
+                if ((PL % 64 == 0 || lane + 64 * q < PL) && cmp[COMPACT ? q : 0] >= 0)
+                    lds[base + cmp[COMPACT ? q : 0]] = v[s][q];
+        } else {
+            const int base = BL::main(a, 0, 0);
+#pragma unroll
+            for (int q = 0; q < NP; q++) {
+                const int i2 = lane + 64 * q;
+                if ((PL % 64 == 0 || i2 < PL) && !(SEG && BL::holds_seg(a, i2)))
+                    lds[base + i2] = v[s][q];
+            }
+        }
+    }
+}
+
+// MODE 1: the histogram of the keys after the next drift, and the list of those that leave
+__device__ __forceinline__ void prep_epilogue(const PrepArgs &prep, unsigned next_key,
+                                              bool pvalid, unsigned p) {
+    int rs, rl;
+    wave_runs(next_key, threadIdx.x & 63, rs, rl);
+    if ((int)(threadIdx.x & 63) == rs && next_key != kNoTile)
+        atomicAdd(&prep.count[next_key], (unsigned)rl);
+    if (prep.emig_idx && pvalid && next_key == kNoTile) {
+        const unsigned slot = atomicAdd(prep.emig_count, 1u);
+        if ((i64)slot < prep.emig_cap) prep.emig_idx[slot] = p;
+    }
+}
+// MODE 2: the scatter of cg_particles.hip k_tile_scatter — one atomic per run of equal keys among
+// consecutive lanes (reserve_run) — with its own stores
+__device__ __forceinline__ void fused_epilogue(const PrepArgs &prep, double x, double y, double z,
+                                               double m0, double m1, double m2, unsigned key,
+                                               bool pvalid, unsigned p) {
+    const FusedScatter &fs = prep.fs;
+    const int lane = threadIdx.x & 63;
+    int rs, rl;
+    wave_runs(key, lane, rs, rl);
+    const unsigned first = reserve_run(fs.start_out, fs.count_out, key, lane, rs, rl,
+                                       fs.out_capacity, prep.err_flags,
+                                       (unsigned)CG_ERR_BUCKET_OVERFLOW);
+    const bool valid = pvalid && key != kNoTile && first != kNoTile;
+    // every lane stores its own record (24-byte stride; the runs of a wave are
+    // consecutive records, L2 merges the partial lines).  The cooperative run store of
+    // the stand-alone scatter (store_run there: contiguous stores through 36 lane
+    // permutes per particle) is slower HERE — 10.4 vs 9.9 ms — because the permutes go
+    // through the LDS crossbar, which the stencil reads already keep busy.
+    if (valid) {
+        const i64 q = 3 * ((i64)first + (lane - rs));
+        d2u8 a, b;
+        a.x = x, a.y = y, b.x = m0, b.y = m1;
+        *(d2u8 *)(fs.pos_out + q) = a;
+        fs.pos_out[q + 2] = z;
+        *(d2u8 *)(fs.mom_out + q) = b;
+        fs.mom_out[q + 2] = m2;
+    }
+    if (valid && fs.ids_in) fs.ids_out[(i64)first + (lane - rs)] = fs.ids_in[p];
+    if (valid && fs.aux_in) fs.aux_out[(i64)first + (lane - rs)] = fs.aux_in[p];
+    if (prep.emig_rows && pvalid && key == kNoTile) {
+        // leaves this domain's slab: exchange() (communication.py:135-517) takes it
+        // from here, already kicked and drifted
+        const unsigned slot = atomicAdd(prep.emig_rows_count, 1u);
+        if ((i64)slot < prep.emig_rows_cap) {
+            double *row = prep.emig_rows + 8 * (i64)slot;
+            row[0] = x, row[1] = y, row[2] = z, row[3] = m0, row[4] = m1, row[5] = m2;
+            row[6] = fs.ids_in ? __longlong_as_double(fs.ids_in[p]) : 0.0;
+            row[7] = fs.aux_in ? __longlong_as_double(fs.aux_in[p]) : 0.0;
+        } else {  // more leavers than the row buffer holds: the pass must be repeated
+            atomicOr(prep.err_flags, (unsigned)CG_ERR_BUCKET_OVERFLOW);
+        }
+    }
+}
 // MODE 0: gather + kick in place.  1: also histogram the tile keys after the next drift (PREP).
 // 2: kick, drift and scatter into the next tile order in one pass (nothing written in place).
 // MOM2 (MODE 2 only): the pass also leaves the sum of |mom|^2 (prep.mom2_out) — its own
@@ -524,187 +803,45 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(
     constexpr bool COMPACT = BL::compact;
     extern __shared__ double lds[];
     constexpr bool PREP = MODE == 1, FUSED = MODE == 2;
-    unsigned tile;
-    unsigned place = ~0u;  // of the walk's tile on the list of heavy tiles
-    if (prep.order.list && blockIdx.x < prep.order.cap) {
-        if (blockIdx.x >= (unsigned)__builtin_amdgcn_readfirstlane((int)*prep.order.n)) return;
-        tile = (unsigned)__builtin_amdgcn_readfirstlane((int)prep.order.list[blockIdx.x]);
-    } else {
-        tile = tile_for_block_grouped(blockIdx.x - (prep.order.list ? prep.order.cap : 0u),
-                                      ntiles, (unsigned)nt, (unsigned)nt);
-        // (no wait here: the byte arrives with the tile's offsets)
-        if (prep.order.list) place = prep.order.rank[tile];
-    }
-    // the tile's particles: dense tile order -> one range; regions with gaps (prep.count_in)
+    const TileTake take = take_tile(prep.order, GroupedWalk{ntiles, (unsigned)nt});
+    const unsigned tile = take.tile;
+    if (take.none) return;
+    // the tile's particles: dense tile order -> one range; regions with gaps (prep.fs.count_in)
     // -> its 8 buckets' (start, population), walked as one flat index
-    // (FUSED only: the plain kernel's LDS block is sized so that three workgroups fit a CU
-    // to the byte — nothing may be added to it)
-    // They live in entries of the staged block that no stencil reads and the staging leaves
-    // alone: compact layout — the corners (a, 0, 0) of the planes a = 1 .. 9, two words each;
-    // plain layout — rows b = E - 1 (8 words) and b = 0 (9 words) of plane a = 0 (a particle's
-    // stencil reaches plane 0 only at rows H .. E-1-H; E >= 5 doubles per row).
-    constexpr int SEG_AT = (E - 1) * E;   // plain layout: block index of row (0, E - 1)
-    static_assert(E * 8 >= 9 * 4, "segment tables do not fit");
-    auto seg_beg = [&](int f) -> unsigned & {
-        return COMPACT ? ((unsigned *)(lds + BL::main(1 + (f >> 1), 0, 0)))[f & 1]
-                       : ((unsigned *)(lds + SEG_AT))[f];
-    };
-    auto seg_pre = [&](int f) -> unsigned & {
-        return COMPACT ? ((unsigned *)(lds + BL::main(5 + (f >> 1), 0, 0)))[f & 1]
-                       : ((unsigned *)lds)[f];
-    };
-    const bool gapped = FUSED && prep.count_in != nullptr;
+    const bool gapped = FUSED && prep.fs.count_in != nullptr;
     // (particle indices fit 32 bits: the tile tables are uint32)
     typedef unsigned pidx;
     pidx beg = tile_offset[8 * tile], end = tile_offset[8 * tile + 8];
     if (gapped) {
-        if (threadIdx.x < 64) {
-            const int f = threadIdx.x & 7;
-            unsigned cnt = prep.count_in[8 * tile + f];
-            unsigned incl = cnt;
-#pragma unroll
-            for (int o = 1; o < 8; o <<= 1) {
-                unsigned v = __shfl_up(incl, o);
-                if (f >= o) incl += v;
-            }
-            if (threadIdx.x < 8) {
-                seg_beg(f) = tile_offset[8 * tile + f];
-                seg_pre(f + 1) = incl;
-                if (f == 0) seg_pre(0) = 0;
-            }
-        }
-        // the total by scalar loads (the tile is uniform): the table above is published by the
-        // barrier that ends the staging, which starts without waiting for it (a barrier here
-        // cost the pass from regions with gaps 0.2 ms against the dense order)
-        unsigned total = 0;
-#pragma unroll
-        for (int f = 0; f < 8; f++)
-            total += (unsigned)__builtin_amdgcn_readfirstlane((int)prep.count_in[8 * tile + f]);
         beg = 0;
-        end = total;
+        end = BL::load_segments(lds, tile_offset, prep.fs.count_in, tile);
     }
-    // (uniform; a tile with a place among the blocks in front was theirs)
-    if (beg == end || (unsigned)__builtin_amdgcn_readfirstlane((int)place) < prep.order.cap) return;
-    // FUSED: a workgroup is a chain of dependent round trips (stage the block, load a batch of
-    // particles, gather, reserve places, store) and only two fit a CU: the particle loads of a
-    // batch are issued one stage ahead — the first batch's under the staging of the block,
-    // the next one's under the arithmetic of the present one
-    pidx pre_p = 0;
-    bool pre_valid = false;
-    double pre_x = 0, pre_y = 0, pre_z = 0, pre_mx = 0, pre_my = 0, pre_mz = 0;
-    auto fetch = [&](pidx pbase) {
+    // (uniform; a tile with a place among the blocks in front was theirs.  The exit waits until
+    // here: the place arrives with the tile's offsets instead of in front of them)
+    if (beg == end || (unsigned)__builtin_amdgcn_readfirstlane((int)take.place) < prep.order.cap) return;
+    const int tc = tile % nt, tb = (tile / nt) % nt, ta = tile / (nt * nt);
+    const int Ni = (int)N;
+    const int T0a = (int)xm.x0 + ta * T, T0b = tb * T, T0c = tc * T;
+    stage_block<ORDER, T, FUSED>(lds, mesh, xm, N, ny, pad, T0a, T0b, T0c);
+    __syncthreads();
+    int m2_lo = 0, m2_hi = 0;  // (FUSED, prep.mom2_out: this wave's sum of |mom|^2, wave-uniform)
+    // A batch's particles are loaded at the top of the trip that uses them.  (A workgroup is a
+    // chain of dependent round trips — stage the block, load a batch, gather, reserve places,
+    // store — but issuing a batch's loads one stage ahead, the first batch's under the staging
+    // of the block, the next one's under the arithmetic of the present one, costs 4 spilled
+    // registers at the 80 that three workgroups per CU allow: 9.4 against 8.4 ms.)
+    for (pidx pbase = beg; pbase < end; pbase += 512) {
         pidx p = pbase + threadIdx.x;
-        pre_valid = p < end;
-        if (gapped && pre_valid) {  // flat index -> slot of its bucket's region
-            // bucket 0 (the tile's interior, (15/16)^3 of its particles) first: a wave that
-            // lies in it entirely — most do — skips the search (uniform branch)
-            if (p < seg_pre(1)) {
-                p = seg_beg(0) + p;
-            } else {
-                int f = 0;
-#pragma unroll
-                for (int step = 4; step > 0; step >>= 1)
-                    if (seg_pre(f + step) <= (unsigned)p) f += step;
-                p = seg_beg(f) + (p - seg_pre(f));
-            }
-        }
-        pre_p = p;
-        if (pre_valid) {
+        const bool pvalid = p < end;
+        if (gapped && pvalid) p = BL::region_slot(lds, p);
+        double px = 0, py = 0, pz = 0, qx = 0, qy = 0, qz = 0;
+        if (FUSED && pvalid) {
             // a record is 24 B at an 8-byte boundary: one 16-byte and one 8-byte access (global
             // memory takes vector accesses at their element's alignment) — 4 requests per
             // particle instead of 6
             const d2u8 a = *(const d2u8 *)(pos + 3 * (i64)p), b = *(const d2u8 *)(mom + 3 * (i64)p);
-            pre_x = a.x, pre_y = a.y, pre_z = pos[3 * (i64)p + 2];
-            pre_mx = b.x, pre_my = b.y, pre_mz = mom[3 * (i64)p + 2];
-        }
-    };
-    // (Issuing a batch's particle loads one stage ahead — the first batch's under the staging of
-    // the block, the next one's under the arithmetic of the present one — costs 4 spilled
-    // registers at the 80 that three workgroups per CU allow: 9.4 against 8.4 ms.)
-    const int tc = tile % nt, tb = (tile / nt) % nt, ta = tile / (nt * nt);
-    const int Ni = (int)N;
-    const int T0a = (int)xm.x0 + ta * T, T0b = tb * T, T0c = tc * T;
-    {
-        // Stage the potential tile + stencil halo.  Wave w takes the planes a = w, w+8, ...
-        // of the E^3 block: the layer index and its 64-bit row base are wave-uniform
-        // (scalar unit), a lane's (row, column) offsets inside a plane are 32-bit and the
-        // same for every plane, so a load costs one instruction (scalar base + lane
-        // offset) instead of the ~80 of per-element 64-bit index arithmetic this loop
-        // used to spend — that arithmetic, not the stencil, was two thirds of the kernel's
-        // VALU work (rocprofv3: 1060 VALU instructions per particle, VALUBusy 78 %).
-        // All loads of a lane are issued before its first LDS store.
-        constexpr int PL = E * E;                // points per plane
-        constexpr int NP = (PL + 63) / 64;       // 64-lane passes per plane
-        constexpr int NA = (E + 7) / 8;          // planes per wave
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int b0 = T0b - H, c0 = T0c - H;
-        const bool seam = b0 < 0 || c0 < 0 || b0 + E > Ni || c0 + E > Ni;
-        unsigned off[NP];  // gj*pad + gk
-        int cmp[COMPACT ? NP : 1];  // compact planes: (b-1)*IN + (c-1) of the interior, else -1
-#pragma unroll
-        for (int q = 0; q < NP; q++) {
-            int i2 = lane + 64 * q;
-            int b = i2 / E, c = i2 - b * E;
-            int gj = b0 + b, gk = c0 + c;
-            if (seam) {  // (tile-uniform) the block reaches across the periodic seam in y or z
-                gj += (gj < 0 ? Ni : 0) - (gj >= Ni ? Ni : 0);
-                gk += (gk < 0 ? Ni : 0) - (gk >= Ni ? Ni : 0);
-            }
-            off[q] = (unsigned)gj * (unsigned)pad + (unsigned)gk;
-            if (COMPACT)
-                cmp[q] = (b >= 1 && b <= E - 2 && c >= 1 && c <= E - 2)
-                             ? (b - 1) * BL::IN + (c - 1) : -1;
-        }
-        double v[NA][NP];
-#pragma unroll
-        for (int s = 0; s < NA; s++) {
-            const int a = __builtin_amdgcn_readfirstlane(wave) + 8 * s;  // wave-uniform
-            if (a < E) {
-                const double *plane = mesh + cg_xlayer(xm, (i64)(T0a - H + a), N) * ny * pad;
-                const bool edge = COMPACT && (a == 0 || a == E - 1);  // (uniform)
-#pragma unroll
-                for (int q = 0; q < NP; q++) {
-                    const bool want = (PL % 64 == 0 || lane + 64 * q < PL) &&
-                                      (!edge || cmp[COMPACT ? q : 0] >= 0);
-                    if (want) v[s][q] = plane[off[q]];
-                }
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < NA; s++) {
-            const int a = __builtin_amdgcn_readfirstlane(wave) + 8 * s;
-            if (a >= E) continue;
-            if (COMPACT && (a == 0 || a == E - 1)) {
-                // a compact boundary plane: its interior only (the branch is wave-uniform)
-                const int base = a == 0 ? BL::P_LO : BL::P_HI;
-#pragma unroll
-                for (int q = 0; q < NP; q++)
-                    if ((PL % 64 == 0 || lane + 64 * q < PL) && cmp[COMPACT ? q : 0] >= 0)
-                        lds[base + cmp[COMPACT ? q : 0]] = v[s][q];
-            } else {
-                const int base = COMPACT ? BL::main(a, 0, 0) : a * PL;
-#pragma unroll
-                for (int q = 0; q < NP; q++) {
-                    const int i2 = lane + 64 * q;
-                    // the entries that hold the segment tables (FUSED) are left alone
-                    const bool seg = FUSED && (COMPACT ? (i2 == 0 && a <= 9)
-                                                       : (a == 0 && (i2 >= SEG_AT || i2 < E)));
-                    if ((PL % 64 == 0 || i2 < PL) && !seg) lds[base + i2] = v[s][q];
-                }
-            }
-        }
-    }
-    __syncthreads();
-    int m2_lo = 0, m2_hi = 0;  // (FUSED, prep.mom2_out: this wave's sum of |mom|^2, wave-uniform)
-    for (pidx pbase = beg; pbase < end; pbase += 512) {
-        pidx p = pbase + threadIdx.x;
-        bool pvalid = p < end;
-        double px = 0, py = 0, pz = 0, qx = 0, qy = 0, qz = 0;
-        if (FUSED) {
-            fetch(pbase);
-            p = pre_p;
-            pvalid = pre_valid;
-            px = pre_x, py = pre_y, pz = pre_z, qx = pre_mx, qy = pre_my, qz = pre_mz;
+            px = a.x, py = a.y, pz = pos[3 * (i64)p + 2];
+            qx = b.x, qy = b.y, qz = mom[3 * (i64)p + 2];
         } else if (pvalid) {
             px = pos[3 * (i64)p + 0], py = pos[3 * (i64)p + 1], pz = pos[3 * (i64)p + 2];
         }
@@ -746,12 +883,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(
                             if (COMPACT && da != 0) return cell[da < 0 ? xm : xp];
                             return cell[(da * E + db) * E + dc];
                         };
-                        double fx, fy, fz;
-                        force_cell<ORDER>(phi, c1, c2, fx, fy, fz);
-                        double w = wij * wz[k];
-                        val[0] += fx * w;
-                        val[1] += fy * w;
-                        val[2] += fz * w;
+                        add_cell<ORDER>(phi, c1, c2, wij, wz[k], val);
                     }
                 }
         } else if (FUSED) {
@@ -777,12 +909,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(
                             return mesh[cg_xlayer(xm, (i64)(ga + i + da), N) * ny * pad +
                                         (i64)wrap(gb + j + db, Ni) * pad + wrap(gc + k + dc, Ni)];
                         };
-                        double fx, fy, fz;
-                        force_cell<ORDER>(phi, c1, c2, fx, fy, fz);
-                        double w = wij * wz[k];
-                        val[0] += fx * w;
-                        val[1] += fy * w;
-                        val[2] += fz * w;
+                        add_cell<ORDER>(phi, c1, c2, wij, wz[k], val);
                     }
                 }
         }
@@ -809,63 +936,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(
             next_key = tile_of(nx, ny_, nz, prep.geo_sort, g, N, prep.tiles, xm.x0);
         }
         }
-        if (PREP) {
-            int rs, rl;
-            wave_runs(next_key, threadIdx.x & 63, rs, rl);
-            if ((int)(threadIdx.x & 63) == rs && next_key != kNoTile)
-                atomicAdd(&prep.count[next_key], (unsigned)rl);
-            if (prep.emig_idx && pvalid && next_key == kNoTile) {
-                const unsigned slot = atomicAdd(prep.emig_count, 1u);
-                if ((i64)slot < prep.emig_cap) prep.emig_idx[slot] = p;
-            }
-        }
+        if (PREP) prep_epilogue(prep, next_key, pvalid, p);
         if (FUSED) {
-            // the scatter of cg_particles.hip k_tile_scatter: one atomic per run of equal keys
-            // among consecutive lanes, runs stored cooperatively
-            const int lane = threadIdx.x & 63;
-            int rs, rl;
-            wave_runs(next_key, lane, rs, rl);
-            unsigned first = kNoTile;
-            if (lane == rs && next_key != kNoTile) {
-                // (a region that reaches beyond the output arrays has no room at all: the
-                // populations outgrew what the arrays were sized for)
-                const unsigned o0 = prep.start_out[next_key], o1 = prep.start_out[next_key + 1],
-                               room = (i64)o1 <= prep.out_capacity ? o1 - o0 : 0u;
-                const unsigned local = atomicAdd(&prep.count_out[next_key], (unsigned)rl);
-                if (local + (unsigned)rl > room) atomicOr(prep.err_flags, 2u);  // overflow
-                else first = o0 + local;
-            }
-            first = __shfl(first, rs);
-            const bool valid = pvalid && next_key != kNoTile && first != kNoTile;
-            // every lane stores its own record (24-byte stride; the runs of a wave are
-            // consecutive records, L2 merges the partial lines).  The cooperative run store of
-            // the stand-alone scatter (store_run there: contiguous stores through 36 lane
-            // permutes per particle) is slower HERE — 10.4 vs 9.9 ms — because the permutes go
-            // through the LDS crossbar, which the stencil reads already keep busy.
-            if (valid) {
-                const i64 q = 3 * ((i64)first + (lane - rs));
-                d2u8 a, b;
-                a.x = nx, a.y = ny_, b.x = n0, b.y = n1;
-                *(d2u8 *)(prep.pos_out + q) = a;
-                prep.pos_out[q + 2] = nz;
-                *(d2u8 *)(prep.mom_out + q) = b;
-                prep.mom_out[q + 2] = n2;
-            }
-            if (valid && prep.ids_in) prep.ids_out[(i64)first + (lane - rs)] = prep.ids_in[p];
-            if (valid && prep.aux_in) prep.aux_out[(i64)first + (lane - rs)] = prep.aux_in[p];
-            if (prep.emig_rows && pvalid && next_key == kNoTile) {
-                // leaves this domain's slab: exchange() (communication.py:135-517) takes it
-                // from here, already kicked and drifted
-                const unsigned slot = atomicAdd(prep.emig_rows_count, 1u);
-                if ((i64)slot < prep.emig_rows_cap) {
-                    double *row = prep.emig_rows + 8 * (i64)slot;
-                    row[0] = nx, row[1] = ny_, row[2] = nz, row[3] = n0, row[4] = n1, row[5] = n2;
-                    row[6] = prep.ids_in ? __longlong_as_double(prep.ids_in[p]) : 0.0;
-                    row[7] = prep.aux_in ? __longlong_as_double(prep.aux_in[p]) : 0.0;
-                } else {  // more leavers than the row buffer holds: the pass must be repeated
-                    atomicOr(prep.err_flags, (unsigned)CG_ERR_BUCKET_OVERFLOW);
-                }
-            }
+            fused_epilogue(prep, nx, ny_, nz, n0, n1, n2, next_key, pvalid, p);
             if (MOM2) {
                 // analysis.measure(component, 'v_rms') (analysis.py:3902-3910) of the momenta
                 // this pass leaves: the sum of a batch's |mom|^2 over the wave's lanes, carried
@@ -902,44 +975,28 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double *__restrict__
     if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
+// mode: 0 in place, 1 prepared, 2 fused (with the sum of |mom|^2 when args.mom2_out is set)
 template <int ORDER, int T>
 static int launch_gather(cg_ctx *c, const double *pos, double *mom, const unsigned *tile_offset,
-                         double c1, double c2, double factor, const PrepArgs *prep) {
+                         double c1, double c2, double factor, int mode, const PrepArgs &args) {
     const size_t lds = sizeof(double) * GatherLds<ORDER, T>::doubles;
-    auto kern = k_gather_kick_tiled<ORDER, T, 0>;
-    auto kern_prep = k_gather_kick_tiled<ORDER, T, 1>;
-    auto kern_fused = k_gather_kick_tiled<ORDER, T, 2>;
-    auto kern_fused_m2 = k_gather_kick_tiled<ORDER, T, 2, true>;
-    // the attribute belongs to the function ON A DEVICE: once per device of this process
-    static bool attr_set[64] = {};
+    const int which = mode + (mode == 2 && args.mom2_out ? 1 : 0);
+    decltype(&k_gather_kick_tiled<ORDER, T, 0>) const kerns[4] = {
+        k_gather_kick_tiled<ORDER, T, 0>, k_gather_kick_tiled<ORDER, T, 1>,
+        k_gather_kick_tiled<ORDER, T, 2>, k_gather_kick_tiled<ORDER, T, 2, true>};
+    const auto kern = kerns[which];
+    // the attribute belongs to the function ON A DEVICE: once per kernel and device of this process
+    static bool attr_set[4][64] = {};
     const int dev = c->p.device & 63;
-    if (!attr_set[dev] && lds > 64 * 1024) {
+    if (!attr_set[which][dev] && lds > 64 * 1024) {
         CG_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
                                    (int)lds));
-        CG_HIP(hipFuncSetAttribute((const void *)kern_prep,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CG_HIP(hipFuncSetAttribute((const void *)kern_fused,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        CG_HIP(hipFuncSetAttribute((const void *)kern_fused_m2,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set[dev] = true;
+        attr_set[which][dev] = true;
     }
-    unsigned nt = (unsigned)c->ntiles;
-    PrepArgs plain{};
-    plain.order = prep ? prep->order : tile_order_args(c);
-    const unsigned nblocks = nt + plain.order.cap;
-    if (prep && prep->start_out)
-        hipLaunchKernelGGL(prep->mom2_out ? kern_fused_m2 : kern_fused, dim3(nblocks), dim3(512), lds, c->stream, pos, mom, tile_offset,
-                           c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.nty, nt, c->xmap,
-                           c->geom_gather, c1, c2, factor, *prep);
-    else if (prep)
-        hipLaunchKernelGGL(kern_prep, dim3(nblocks), dim3(512), lds, c->stream, pos, mom, tile_offset,
-                           c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.nty, nt, c->xmap,
-                           c->geom_gather, c1, c2, factor, *prep);
-    else
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(512), lds, c->stream, pos, mom, tile_offset,
-                           c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.nty, nt, c->xmap,
-                           c->geom_gather, c1, c2, factor, plain);
+    const unsigned nt = (unsigned)c->ntiles;
+    hipLaunchKernelGGL(kern, dim3(nt + args.order.cap), dim3(512), lds, c->stream, pos, mom,
+                       tile_offset, c->mesh, c->N, c->ny, c->pad, c->p.nghosts, c->tiles.nty, nt,
+                       c->xmap, c->geom_gather, c1, c2, factor, args);
     return 0;
 }
 
@@ -949,17 +1006,8 @@ int cgk_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i64 n,
     PrepArgs prep_args{next_dtm, c->p.boxsize, c->geom_deposit, c->tiles, c->tile_count,
                        c->emig_idx, c->emig_count, c->emig_cap};
     if (fs) {
-        prep_args.start_out = fs->start_out;
-        prep_args.count_out = fs->count_out;
-        prep_args.pos_out = fs->pos_out;
-        prep_args.mom_out = fs->mom_out;
-        prep_args.ids_in = fs->ids_in;
-        prep_args.ids_out = fs->ids_out;
-        prep_args.aux_in = fs->aux_in;
-        prep_args.aux_out = fs->aux_out;
-        prep_args.out_capacity = fs->out_capacity;
+        prep_args.fs = *fs;
         prep_args.err_flags = c->err_flags;
-        prep_args.count_in = fs->count_in;
         prep_args.emig_rows = c->emig_rows;
         prep_args.emig_rows_count = c->emig_rows_count;
         prep_args.emig_rows_cap = c->emig_rows_cap;
@@ -977,10 +1025,8 @@ int cgk_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i64 n,
         CG_HIP(hipMemsetAsync(c->emig_count, 0, sizeof(unsigned), c->stream));
     if (cgk_tile_order(c, tile_offset, fs ? fs->count_in : nullptr)) return 1;
     prep_args.order = tile_order_args(c);
-    const PrepArgs *prep = (prepare || fs) ? &prep_args : nullptr;
     if (prepare)
         CG_HIP(hipMemsetAsync(c->tile_count, 0, 4 * (8 * c->ntiles + 1), c->stream));
-    const int T = c->tiles.tx;
     double dx = c->p.boxsize / (double)c->N;  // interactions.py:2133
     double c1, c2 = 0;
     if (diff_order == 2) c1 = (1.0 / 2) / dx;  // mesh.py:4967
@@ -988,21 +1034,15 @@ int cgk_gather_kick_tiled(cg_ctx *c, const double *pos, double *mom, i64 n,
         c1 = (2.0 / 3) / dx;  // mesh.py:4973
         c2 = (1.0 / 12) / dx;  // mesh.py:4977
     }
-    int rc = 1;
-#define CG_GATHER_CASE(TT)                                                                       \
-    case TT:                                                                                     \
-        rc = diff_order == 2                                                                     \
-                 ? launch_gather<2, TT>(c, pos, mom, tile_offset, c1, c2, factor, prep)          \
-                 : launch_gather<4, TT>(c, pos, mom, tile_offset, c1, c2, factor, prep);         \
-        break;
-    switch (T) {
-        CG_GATHER_CASE(16)
-        CG_GATHER_CASE(8)
-        CG_GATHER_CASE(4)
-        CG_GATHER_CASE(2)
-        default: cg_set_error("cgk_gather_kick_tiled: tile extent %d", T); return 1;
-    }
-#undef CG_GATHER_CASE
+    // (in place, mode 0: of prep_args the kernel reads the order alone)
+    const int mode = fs ? 2 : (prepare ? 1 : 0);
+    const int rc = with_tile_extent(c, "cgk_gather_kick_tiled", [&](auto t) {
+        constexpr int T = decltype(t)::value;
+        return diff_order == 2
+                   ? launch_gather<2, T>(c, pos, mom, tile_offset, c1, c2, factor, mode, prep_args)
+                   : launch_gather<4, T>(c, pos, mom, tile_offset, c1, c2, factor, mode,
+                                         prep_args);
+    });
     if (rc) return rc;
     CG_LAUNCH_CHECK();
     if (fs && c->mom2_sum_out) {

@@ -1,6 +1,6 @@
 // cg_tiles.h — device helpers shared by the particle kernels: the reference's mod(),
 // the tile / bucket key of a particle; with it come the wave primitives of cg_wave.h (wave_runs
-// turns runs of equal keys into one atomic each).
+// turns runs of equal keys into one atomic each, reserve_run below gives such a run its slots).
 #pragma once
 #include "cg_internal.h"
 #include "cg_wave.h"
@@ -55,4 +55,27 @@ __device__ __forceinline__ unsigned tile_of(double x, double y, double z, const 
     unsigned f = (((ca & last) == last) ? 4u : 0u) | (((cb & last) == last) ? 2u : 0u) |
                  (((cc & last) == last) ? 1u : 0u);
     return ((a * t.nty + b) * t.ntz + c) * 8u + f;
+}
+
+// A run of `rl` consecutive lanes with the same key (wave_runs: the run starts at lane rs) takes
+// `rl` slots of the key's region [start[key], start[key + 1]) with ONE atomic on taken[key],
+// issued by its first lane; every lane of the run gets the run's first slot.  A run that does not
+// fit is dropped — kNoTile, never a slot outside its region — and raises `err_bit` in err_flags.
+// `capacity`: rows of the arrays behind the regions — a region that reaches beyond them has no
+// room at all — or kNoCapacity (more than any table can hold: the test folds away) where the
+// regions are known to lie inside.
+constexpr i64 kNoCapacity = INT64_MAX;
+__device__ __forceinline__ unsigned reserve_run(const unsigned *start, unsigned *taken,
+                                                unsigned key, int lane, int rs, int rl,
+                                                i64 capacity, unsigned *err_flags,
+                                                unsigned err_bit) {
+    unsigned first = kNoTile;
+    if (lane == rs && key != kNoTile) {
+        const unsigned o0 = start[key], o1 = start[key + 1];
+        const unsigned room = (i64)o1 <= capacity ? o1 - o0 : 0u;
+        const unsigned local = atomicAdd(&taken[key], (unsigned)rl);
+        if (local + (unsigned)rl > room) atomicOr(err_flags, err_bit);
+        else first = o0 + local;
+    }
+    return __shfl(first, rs);
 }
