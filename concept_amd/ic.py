@@ -6,7 +6,8 @@ handful of growth factors — and does everything after that on meshes.  Here bo
 (`amplitudes_from_power` makes the table from a tabulated P(k)) and the mesh work runs on the
 GPU (csrc/cg_lpt.hip through PotentialMesh.lpt_*):
 
-    noise (host, numpy's own generators: the reference's random streams, number for number)
+    noise (host, numpy's own generators: the reference's random streams, number for number;
+           or with noise_on='device' the same streams drawn on the GPU, csrc/cg_noise.hip)
       -> Φ⁽¹⁾ = ∇⁻²(amplitude·noise)            lpt_potential
       -> Ψ⁽¹⁾ᵢ = ∂ᵢΦ⁽¹⁾, back to real space      lpt_diff + the mesh's inverse transform
       -> positions += Ψ, momenta += factor·Ψ    lpt_displace
@@ -213,6 +214,126 @@ def generate_primordial_noise(gridsize, fixed_amplitude=False, phase_shift=0, pa
         raise ConceptGPUError(f'primordial_noise_imprinting = "{scheme}" not implemented')
     slab[0, 0, 0] = slab[0, 0, 1] = 0  # nullify_modes(slab, 'origin')
     return slab
+
+
+# ---- primordial noise on the device (csrc/cg_noise.hip) ------------------------------------------
+PCG_CHEAP_MULTIPLIER = 0xda942042e4dd58b5  # PCG64DXSM: state' = a·state + inc mod 2¹²⁸
+_MASK64, _MASK128 = 2**64 - 1, 2**128 - 1
+_noise_tables = {}  # (device, 'jump' | gridsize) -> device tensor
+
+
+def _words128(*values):
+    """128-bit integers as pairs of 64-bit words, low word first"""
+    return [w for v in values for w in (v & _MASK64, v >> 64)]
+
+
+def pcg64dxsm_jump_table(n):
+    """uint64[n + 1][4]: row k holds (aᵏ, Sₖ = 1 + a + … + aᵏ⁻¹) mod 2¹²⁸, low words first.
+    k steps of PCG64DXSM take `state` to aᵏ·state + Sₖ·inc, whatever the stream and the seed."""
+    rows, power, series = [], 1, 0
+    for _ in range(n + 1):
+        rows.append(_words128(power, series))
+        series = (series*PCG_CHEAP_MULTIPLIER + 1) & _MASK128
+        power = (power*PCG_CHEAP_MULTIPLIER) & _MASK128
+    return np.array(rows, dtype=np.uint64)
+
+
+def noise_order_table(gridsize):
+    """int32[(g - 1)·g/2][2]: the point (ki, kk) the t-th draw of a j-slice belongs to"""
+    ki, kk = _curve_order_slice(gridsize)
+    return np.ascontiguousarray(np.stack([ki, kk], axis=1).astype(np.int32))
+
+
+def noise_stream_table(gridsize, fixed_amplitude=False, params=None):
+    """uint64[g - 1][8]: for every spawn key κ = -nyquist + 1 … nyquist - 1 of the 'distributed'
+    scheme the 128-bit state and increment of the amplitude stream and of the phase stream
+    (low words first), as numpy seeds them.  Every stream appears once: the slice kj = κ draws
+    it for itself and the slice kj = -κ as its conjugate stream.  With fixed amplitudes the
+    amplitude streams are not made (polar() does not draw them either): their words are 0."""
+    p = params or commons.params
+    if p is None:
+        raise ConceptGPUError('no parameters loaded: call concept_amd.commons.load_params()')
+    _check_noise_device_scope(p)
+    nyquist = int(gridsize)//2
+    spawn_key_offset = 2**32
+    commons_ = [None if fixed_amplitude else PseudoRandomNumberGenerator(
+                    p.random_seeds['primordial amplitudes'], p.random_generator),
+                PseudoRandomNumberGenerator(p.random_seeds['primordial phases'],
+                                            p.random_generator)]
+    table = np.zeros((2*nyquist - 1, 8), dtype=np.uint64)
+    for row, κ in enumerate(range(-nyquist + 1, nyquist)):
+        for n, common in enumerate(commons_):
+            if common is None:
+                continue
+            state = common.spawn(spawn_key_offset + κ).generator.bit_generator.state['state']
+            table[row, 4*n:4*n + 4] = _words128(state['state'], state['inc'])
+    return table
+
+
+def _check_noise_device_scope(p):
+    scheme = p.primordial_noise_imprinting
+    if scheme == 'simple':
+        raise ConceptGPUError(
+            'primordial noise on the device: primordial_noise_imprinting = "simple" is not '
+            'implemented (its two streams run along the whole curve; "distributed" is)')
+    if scheme != 'distributed':
+        raise ConceptGPUError(f'primordial_noise_imprinting = "{scheme}" not implemented')
+    if p.random_generator != 'PCG64DXSM':
+        raise ConceptGPUError(
+            f'primordial noise on the device: random_generator = "{p.random_generator}" is not '
+            'implemented (the bit generator "PCG64DXSM" is)')
+
+
+def _check_noise_on(component, noise_on):
+    """what noise_on='device' needs beyond the scope of the realisation itself"""
+    if noise_on == 'host':
+        return
+    if noise_on != 'device':
+        raise ConceptGPUError(f"{component.name}: noise_on = {noise_on!r} is neither 'host' nor "
+                              "'device'")
+    if _comm.active() is not None or getattr(component, 'nprocs', 1) > 1:
+        raise ConceptGPUError(
+            f"{component.name}: noise_on='device' with an active comm process group: the "
+            'primordial noise of several domains is not generated on the device')
+    _check_noise_device_scope(component.params)
+
+
+def _noise_table_dev(device, key, make):
+    table = _noise_tables.get((device, key))
+    if table is None:
+        array = make()
+        if array.dtype == np.uint64:
+            array = array.view(np.int64)
+        table = _noise_tables[device, key] = torch.from_numpy(array).to(device)
+    return table
+
+
+def generate_primordial_noise_device(mesh, fixed_amplitude=False, phase_shift=0, params=None):
+    """The slab generate_primordial_noise(mesh.gridsize, ...) returns, as upload_fourier would
+    leave it in the Fourier view of `mesh`, drawn on the device from the same random streams
+    (csrc/cg_noise.hip): the same modes, zeros on the Nyquist planes and at the origin, the
+    kk = 0 plane Hermitian.  The amplitudes and the uniform numbers are numpy's to the bit; cos,
+    sin and the ziggurat's rare log1p and exp are the device library's.  The 'distributed'
+    scheme on PCG64DXSM (the defaults) and one domain; anything else is refused.  Returns the
+    mesh."""
+    from .lib import raw
+    p = params or commons.params
+    if p is None:
+        raise ConceptGPUError('no parameters loaded: call concept_amd.commons.load_params()')
+    g = int(mesh.gridsize)
+    if g < 2 or g % 2:
+        raise ConceptGPUError(f'generate_primordial_noise_device(): grid size {g} must be even '
+                              'and ≥ 2')
+    if mesh.dist or _comm.active() is not None:
+        raise ConceptGPUError('generate_primordial_noise_device() with an active comm process '
+                              'group: the primordial noise of several domains is not generated '
+                              'on the device')
+    streams = noise_stream_table(g, fixed_amplitude, p)
+    trip = int(raw().cg_noise_trip())
+    jump = _noise_table_dev(mesh.device, 'jump', lambda: pcg64dxsm_jump_table(trip))
+    order = _noise_table_dev(mesh.device, g, lambda: noise_order_table(g))
+    streams = torch.from_numpy(streams.view(np.int64)).to(mesh.device)
+    return mesh.noise_generate(streams, order, jump, fixed_amplitude, phase_shift)
 
 
 # ---- amplitudes (ic.py:599-627) ------------------------------------------------------------------
@@ -611,7 +732,7 @@ def carryout_lpt(orders, terms, growth_factors, a, H, mass, particles=(None, Non
 
 def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_factors=None,
                       cosmology=None, components_all=None, timings=None, extended=False,
-                      on_potential=None):
+                      on_potential=None, noise_on='host'):
     """Realise a particle component at scale factor a (realize_particles, ic.py:1199-1400):
     particles on their lattice, displaced and boosted by 1LPT and, with
     realization_options['lpt'] = 2, 2LPT; positions wrapped into [0, boxsize).
@@ -630,7 +751,12 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
     cosmology: an integration.Cosmology (H(a)); default: one of the component's parameters.
     components_all: every component of the run; those that are particles with mass -1 are the
       ones to be realised and decide the lattice of each (1: sc, 2: bcc, 4: fcc by tally).
-    timings: a dict that receives milliseconds by kind of pass (synchronises)."""
+    timings: a dict that receives milliseconds by kind of pass (synchronises).
+    noise_on: 'host' draws the primordial noise with numpy and uploads the slab ('noise (host)'
+      and 'upload' in timings); 'device' draws the same streams on the GPU into the mesh
+      (generate_primordial_noise_device; 'noise (device)' in timings) — the 'distributed'
+      scheme on PCG64DXSM and one domain, anything else is refused."""
+    _check_noise_on(component, noise_on)
     options = realization_options(component)
     _check_scope(component, options, extended)
     p = component.params
@@ -691,9 +817,11 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
     if dealias:
         tmps_dealias = (grid('lpt tmp0 dealias', gridsize_dealias),
                         grid('lpt tmp1 dealias', gridsize_dealias))
-    with _host_timer(timings, 'noise (host)'):
-        noise = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
-                                          p.primordial_phase_shift, p)
+    noise = None
+    if noise_on == 'host':
+        with _host_timer(timings, 'noise (host)'):
+            noise = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
+                                              p.primordial_phase_shift, p)
     mass = a**(-3*component.w_eff(a=a))*component.mass  # ic.py:2267
     H = cosmology.hubble(a)
     pos, mom = component.pos, component.mom
@@ -718,8 +846,13 @@ def realize_particles(component, a, amplitudes, amplitudes_θ=None, growth_facto
         uploaded = False
         for variable in range(1 - backscale, -1, -1):
             if not uploaded or tmp1 is tmp0:
-                with watch('upload'):
-                    tmp0.upload_fourier(noise)
+                if noise is None:
+                    with watch('noise (device)'):
+                        generate_primordial_noise_device(tmp0, p.primordial_amplitude_fixed,
+                                                         p.primordial_phase_shift, p)
+                else:
+                    with watch('upload'):
+                        tmp0.upload_fourier(noise)
                 uploaded = True
             with watch('k-space'):
                 Φ1.lpt_potential(tmp0, amplitudes_dev[variable], shift, factor=2*variable - 1)
@@ -778,16 +911,19 @@ def _realization_mesh(component, role):
                     device=component.device)
 
 
-def realize_fluid(component, a, amplitudes, variable=0, multi_index=0, noise=None, timings=None):
+def realize_fluid(component, a, amplitudes, variable=0, multi_index=0, noise=None, timings=None,
+                  noise_on='host'):
     """Realise one fluid scalar of a fluid component at scale factor a (realize_fluid,
     ic.py:400-477): ϱ (variable 0) or J[multi_index] (variable 1) from the primordial noise.
 
     amplitudes: the k²-indexed table (amplitudes_from_power) of δ for ϱ, of θ for J.
     noise: a mesh that holds the primordial noise in Fourier space (what an earlier call
-      returned); without it the noise is generated on the host and uploaded.
+      returned); without it the noise is generated on the host and uploaded, or with
+      noise_on='device' on the GPU (as in realize_particles).
     timings: a dict that receives milliseconds by kind of pass (synchronises).
     Returns the noise mesh.  realization_options['structure'] plays no part: a variable within
     the Boltzmann order is realised from the primordial structure (ic.py:819-823)."""
+    _check_noise_on(component, noise_on)
     _check_fluid_scope(component, variable, multi_index)
     p = component.params
     gridsize = component.gridsize
@@ -795,11 +931,16 @@ def realize_fluid(component, a, amplitudes, variable=0, multi_index=0, noise=Non
     watch = _Stopwatch(timings)
     if noise is None:
         noise = _realization_mesh(component, 'realize noise')
-        with _host_timer(timings, 'noise (host)'):
-            slab = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
-                                             p.primordial_phase_shift, p)
-        with watch('upload'):
-            noise.upload_fourier(slab)
+        if noise_on == 'device':
+            with watch('noise (device)'):
+                generate_primordial_noise_device(noise, p.primordial_amplitude_fixed,
+                                                 p.primordial_phase_shift, p)
+        else:
+            with _host_timer(timings, 'noise (host)'):
+                slab = generate_primordial_noise(gridsize, p.primordial_amplitude_fixed,
+                                                 p.primordial_phase_shift, p)
+            with watch('upload'):
+                noise.upload_fourier(slab)
     elif noise.gridsize != gridsize:
         raise ConceptGPUError(f'{component.name}: a noise mesh of grid size {noise.gridsize} for '
                               f'a fluid of grid size {gridsize}')
@@ -827,10 +968,11 @@ def realize(component, a, amplitudes, amplitudes_θ=None, **kw):
     realize_particles(component, a, amplitudes, amplitudes_θ, **kw).  A fluid gets ϱ and, with
     a Boltzmann order of 1 or more, J[0..2] (amplitudes_θ is then needed), all from one noise
     slab generated and uploaded once; 𝒫 = c²wϱ follows (realize_approximative,
-    ic.py:495-511; w is constant here).  kw for a fluid: timings."""
+    ic.py:495-511; w is constant here).  kw for a fluid: timings, noise_on."""
     if component.representation == 'particles':
         return realize_particles(component, a, amplitudes, amplitudes_θ, **kw)
     timings = kw.pop('timings', None)
+    noise_on = kw.pop('noise_on', 'host')
     if kw:
         raise ConceptGPUError(f'{component.name}: realize() of a fluid component takes no '
                               f'{sorted(kw)}')
@@ -838,7 +980,7 @@ def realize(component, a, amplitudes, amplitudes_θ=None, **kw):
     if with_J and amplitudes_θ is None:
         raise ConceptGPUError(f'{component.name}: J comes from the amplitudes of θ: pass '
                               'amplitudes_θ')
-    noise = realize_fluid(component, a, amplitudes, 0, timings=timings)
+    noise = realize_fluid(component, a, amplitudes, 0, timings=timings, noise_on=noise_on)
     if with_J:
         for multi_index in range(3):
             realize_fluid(component, a, amplitudes_θ, 1, multi_index, noise=noise, timings=timings)

@@ -521,6 +521,29 @@ class PotentialMesh:
         self.layers_write(0, N, torch.from_numpy(native).to(self.device))
         return self
 
+    def noise_generate(self, streams, order, jump, fixed_amplitude=False, phase_shift=0.0):
+        """The primordial noise of the 'distributed' scheme (ic.py:928-1163) as this mesh's
+        Fourier content, drawn on the device from the reference's streams (cg_noise_generate;
+        one domain).  Device tensors, contiguous: streams uint64-as-int64 (gridsize - 1, 8), the
+        state and increment of the amplitude and of the phase stream of every spawn key; order
+        int32 ((gridsize - 1)*gridsize/2, 2), (ki, kk) of a slice in visiting order; jump
+        uint64-as-int64 (cg_noise_trip() + 1, 4), the jump-ahead table of PCG64DXSM.  Every
+        element of the view is written: the mesh need not be zeroed."""
+        if self.dist:
+            raise lib.ConceptGPUError('noise_generate(): single-domain entry')
+        for name, t, dtype, cols in (('streams', streams, torch.int64, 8),
+                                     ('order', order, torch.int32, 2),
+                                     ('jump', jump, torch.int64, 4)):
+            if (t.dtype != dtype or t.device != self.device or not t.is_contiguous()
+                    or t.dim() != 2 or t.shape[1] != cols):
+                raise lib.ConceptGPUError(
+                    f'noise_generate(): {name} must be a contiguous {dtype} tensor of {cols} '
+                    f'columns on {self.device}')
+        check(_L.cg_noise_generate(self._ctx, _ptr(streams), streams.shape[0], _ptr(order),
+                                   order.shape[0], _ptr(jump), jump.shape[0],
+                                   int(bool(fixed_amplitude)), float(phase_shift)))
+        return self
+
     def lpt_potential(self, noise, amplitudes=None, shift=(0.0, 0.0, 0.0), factor=1.0):
         """realize_grid (scalar case, ic.py:711-764) + laplacian_inverse (mesh.py:3422-3437) of
         the Fourier content of `noise` into this mesh; amplitudes: float64 tensor of

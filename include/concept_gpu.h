@@ -904,6 +904,36 @@ int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitudes /*DEV k
                     int64_t k2_max, int tensor_rank, int index0);
 int cg_fluid_from_mesh(cg_ctx *mesh, double *out /*DEV nxl*N*N*/, int mode, double c0, double c1);
 
+/* --- initial conditions: the primordial noise on the device (ic.py:928-1163) ---------------
+ * cg_noise_generate: the primordial white noise of the 'distributed' imprinting scheme
+ *   (ic.py:928-1163) written into the Fourier view of `mesh` (one domain), from the reference's
+ *   own random streams: numpy's PCG64DXSM, its ziggurat for the standard exponential
+ *   distribution (csrc/cg_ziggurat_tables.h) under the Rayleigh amplitudes sqrt(2 E)/sqrt(2),
+ *   and its uniform doubles under the phases -pi + U*(pi - (-pi)) (+ phase_shift when that is
+ *   not 0).  One workgroup per spawn key kappa = -N/2 + 1 .. N/2 - 1 draws the amplitude stream
+ *   and the phase stream of that key once, n_slice numbers each, in trips of cg_noise_trip()
+ *   raw words; draw t belongs to point order[t] = (ki, kk) of a j-slice (the curve's order,
+ *   fourier_curve_slice_loop, mesh.py:2984-3044).  r (cos theta, sin theta) goes to mode
+ *   (ki, kj = kappa, kk) when kk != 0 or ki < 0 or (ki = 0 and kappa < 0), and its conjugate to
+ *   mode (-ki, -kappa, 0) when kk = 0 and not (ki > 0 or (ki = 0 and kappa > 0)).  Every other
+ *   element of the view (the three Nyquist planes, the origin, the row padding) is written as
+ *   0, each element exactly once: the mesh need not be zeroed.  The unused row of a layer is
+ *   not written.  With fixed_amplitude r = 1 and the amplitude streams are not read.
+ *   streams: DEV uint64[n_keys][8], n_keys = N - 1, row kappa + N/2 - 1: (state lo, state hi,
+ *     inc lo, inc hi) of the amplitude stream, then of the phase stream.
+ *   order: DEV int32[n_slice][2], n_slice = (N - 1)*N/2; an entry outside -N/2 < ki < N/2,
+ *     0 <= kk < N/2 is skipped.
+ *   jump: DEV uint64[n_jump][4], n_jump = cg_noise_trip() + 1, row k: (a^k lo, a^k hi, S_k lo,
+ *     S_k hi) mod 2^128 with a = 0xda942042e4dd58b5, S_k = 1 + a + ... + a^(k-1): the state
+ *     after k steps is a^k*state + S_k*inc.
+ *   The amplitudes, the uniform numbers and the square root are numpy's to the bit; log1p (the
+ *   ziggurat's tail), exp (its wedges), cos and sin are the device library's. */
+int cg_noise_trip(void);
+int cg_noise_generate(cg_ctx *mesh, const uint64_t *streams /*DEV n_keys*8*/, int64_t n_keys,
+                      const int32_t *order /*DEV n_slice*2*/, int64_t n_slice,
+                      const uint64_t *jump /*DEV n_jump*4*/, int64_t n_jump, int fixed_amplitude,
+                      double phase_shift);
+
 /* --- debug fetch (parity tests) -------------------------------------------- */
 int cg_fetch(cg_ctx *ctx, int which, double *out /*HOST*/, int64_t n_doubles);
 /* CIC cell indices exactly as set_weights_CIC returns them for the deposit

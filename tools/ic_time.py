@@ -1,10 +1,11 @@
 """Time one particle realisation (concept_amd/ic.py) on one GPU, split by kind of pass:
-noise (host, wall clock), upload of the noise slab, k-space passes (lpt_potential, lpt_diff),
+noise (host, wall clock) and upload of the noise slab, or with --noise-on device the noise drawn
+on the GPU (stream table on the host and kernel), k-space passes (lpt_potential, lpt_diff),
 transforms, grid products and particle passes (lattice, displacement, wrap), hipEvents around
 every pass.
 
   python tools/ic_time.py [--gridsize 512] [--lpt 2] [--dealias] [--runs 2] [--fused]
-                          [--out profiles/ic_512.json]
+                          [--noise-on host|device] [--out profiles/ic_512.json]
 
 --lpt 3 and --dealias go through realize_particles(extended=True).  --fused also times, on the
 realisation's own meshes in this process, each of the three passes between the realisation size N
@@ -76,6 +77,34 @@ def fused_vs_unfused(grids, p, device):
     return ms
 
 
+def noise_kernel(g, p, device):
+    """the noise kernel alone (tables already on the device): median of 5 after a warm-up, and its
+    rate in raw words of PCG64DXSM, one per phase and what the ziggurat took per amplitude"""
+    from concept_amd import ic, lib
+    from concept_amd.mesh import get_mesh
+    mesh = get_mesh(g, p.boxsize, p.nghosts, p.cell_centered, role='lpt tmp0', device=device)
+    trip = int(lib.raw().cg_noise_trip())
+    streams = torch.from_numpy(ic.noise_stream_table(g, False, p).view(np.int64)).to(device)
+    order = torch.from_numpy(ic.noise_order_table(g)).to(device)
+    jump = torch.from_numpy(ic.pcg64dxsm_jump_table(trip).view(np.int64)).to(device)
+    times = []
+    for _ in range(6):
+        e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(2))
+        e0.record()
+        mesh.noise_generate(streams, order, jump, p.primordial_amplitude_fixed,
+                            p.primordial_phase_shift)
+        e1.record()
+        torch.cuda.synchronize()
+        times.append(e0.elapsed_time(e1))
+    ms = sorted(times[1:])[2]
+    draws = (g - 1)*((g - 1)*g//2)
+    # a trip of `trip` words makes about trip/1.02 amplitudes: the words the kernel hashes
+    trips = -(-int(draws/(g - 1)*1.0235)//trip)
+    words = (g - 1)*trips*trip + draws
+    return {'ms': ms, 'draws per stream kind': draws, 'raw words (estimate)': words,
+            'raw words per second': words/(ms*1e-3), 'trip': trip}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gridsize', type=int, default=512)
@@ -83,6 +112,7 @@ def main():
     ap.add_argument('--dealias', action='store_true')
     ap.add_argument('--fused', action='store_true')
     ap.add_argument('--runs', type=int, default=2)
+    ap.add_argument('--noise-on', choices=('host', 'device'), default='host')
     ap.add_argument('--out', default=None)
     args = ap.parse_args()
     from concept_amd import commons, ic
@@ -109,16 +139,21 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         grids = ic.realize_particles(c, p.a_begin, amplitudes, growth_factors=growth,
-                                     timings=timings, **({'extended': True} if extended else {}))
+                                     timings=timings, **({'extended': True} if extended else {}),
+                                     **({'noise_on': 'device'} if args.noise_on == 'device'
+                                        else {}))
         torch.cuda.synchronize()
         record = {'device': torch.cuda.get_device_name(), 'gridsize': g, 'particles': g**3,
                   'lpt': args.lpt, 'backscale': True, 'dealias': args.dealias,
+                  'noise_on': args.noise_on,
                   'gridsize_dealias': grids.get('gridsize_dealias', g),
                   'wall_ms': (time.perf_counter() - t0)*1e3,
                   'ms': {k_: v for k_, v in timings.items() if not k_.endswith(' passes')},
                   'passes': {k_[:-7]: v for k_, v in timings.items() if k_.endswith(' passes')}}
         record['gpu_ms'] = sum(v for k_, v in record['ms'].items() if k_ != 'noise (host)')
     assert bool(((c.pos >= 0) & (c.pos < L)).all())
+    if args.noise_on == 'device':
+        record['noise_kernel'] = noise_kernel(g, p, c.device)
     if args.fused:
         record['fused_vs_unfused_ms'] = fused_vs_unfused(grids, p, c.device)
     text = json.dumps(record, indent=1)
