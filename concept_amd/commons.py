@@ -424,8 +424,9 @@ def _load_ic_params(p, user):
     """What the particle realisation reads (commons.py:3742-3832, 3899-3925): the pseudo-random
     number generator and its seeds, the noise imprinting scheme, fixed amplitudes and the phase
     shift, and realization_options as {option: {selector: value}} (looked up per component
-    with is_selected).  'structure' defaults to 'primordial' here: the other value, the
-    reference's default for late-time fluid realisations, is not built."""
+    with is_selected).  'structure' defaults to 'primordial' here; the other value, 'nonlinear'
+    (the reference's default for late-time fluid realisations), is selected per component for
+    the shear of closure 'class' (ic.realize_shear, fluid.shear_sources)."""
     p.random_generator = str(user.get('random_generator', 'PCG64DXSM'))
     seeds_default = {'general': 0, 'primordial amplitudes': 1_000, 'primordial phases': 2_000}
     p.random_seeds = dict(user.get('random_seeds') or {})

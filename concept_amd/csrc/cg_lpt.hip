@@ -8,6 +8,9 @@
 //   k_realize_grid   realize_grid (scalar and vector)   ic.py:708-764
 //   k_fluid_from_mesh  domain_decompose and the move to ϱ or Jⁱ of realize_fluid
 //                                                       ic.py:418-456
+//   k_realize_grid_tensor  realize_grid (rank 2, one element)     ic.py:743-762
+//   k_shear_divergence     ∂ʲςⁱⱼ of the Euler equation, formed in Fourier space
+//                                                       fluid.py:1011-1043, mesh.py:4966-4970
 //   k_lpt_diff_enlarge       fourier_diff + resize_grid up, of diff_ifft   ic.py:2093-2101
 //   k_lpt_dealias_cube       nullify_modes('beyond cube of |k| < …')       ic.py:2025
 //   k_lpt_shrink_accumulate  resize_grid down + the move to the output     ic.py:2029-2057
@@ -191,8 +194,70 @@ __global__ __launch_bounds__(kThreads) void k_realize_grid(double2 *dst, const d
     }
 }
 
+// dst = (amp[k2] * K) * src off the origin and the Nyquist planes, 0 on them;
+// K = 0.5 [index0 == index1] - ((1.5 k_index0) k_index1) / k2, ic.py:744-759
+__global__ __launch_bounds__(kThreads) void k_realize_grid_tensor(double2 *dst, const double2 *src,
+                                                                  int N, i64 dst_si, i64 src_si,
+                                                                  i64 cp, int j0, int nj,
+                                                                  const double *amp, int index0,
+                                                                  int index1) {
+#pragma clang fp contract(off)
+    const double half_delta = 0.5 * (index0 == index1);  // ℝ[0.5*(index0 == index1)]
+    const i64 total = (i64)N * nj * (N / 2 + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const KspaceMode m = kspace_mode(e, N, j0, nj);
+        double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
+        if (m.live) {
+            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
+            const i64 kl = index0 == 0 ? m.ki : (index0 == 1 ? m.kj : m.kk);
+            const i64 km = index1 == 0 ? m.ki : (index1 == 1 ? m.kj : m.kk);
+            const double amplitude =
+                amp[m.k2] * (half_delta - ((1.5 * (double)kl) * (double)km) / (double)m.k2);
+            out = make_double2(amplitude * z.x, amplitude * z.y);  // ic.py:761-762
+        }
+        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
+    }
+}
+
+// dst = (amp[k2] * S) * i src off the origin and the Nyquist planes, 0 on them;
+// S = Σ_j s_j K_dim,j = 0.5 s_dim - ((1.5 k_dim) (s_0 ki + s_1 kj + s_2 kk)) / k2 with K of
+// k_realize_grid_tensor and s_j = sin(2π k_j/N)/Δx, the order-2 central difference of
+// diff_domaingrid (mesh.py:4966-4970) in Fourier space.  The N sines by array index are
+// tabulated once per workgroup (dynamic LDS, N doubles): a mode reads three of them.
+__global__ __launch_bounds__(kThreads) void k_shear_divergence(double2 *dst, const double2 *src,
+                                                               int N, i64 dst_si, i64 src_si,
+                                                               i64 cp, int j0, int nj,
+                                                               const double *amp, int dim,
+                                                               double inv_dx) {
+#pragma clang fp contract(off)
+    extern __shared__ double s_sin[];
+    for (int a = threadIdx.x; a < N; a += kThreads) {
+        const int k = a - (a >= N / 2 ? N : 0);
+        s_sin[a] = sinpi((double)(2 * k) / (double)N) * inv_dx;
+    }
+    __syncthreads();
+    const i64 total = (i64)N * nj * (N / 2 + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads) {
+        const KspaceMode m = kspace_mode(e, N, j0, nj);
+        double2 out = make_double2(0.0, 0.0);
+        if (m.live) {
+            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
+            const double s0 = s_sin[m.a], s1 = s_sin[j0 + m.bl], s2 = s_sin[m.kk];
+            const i64 kd = dim == 0 ? m.ki : (dim == 1 ? m.kj : m.kk);
+            const double sd = dim == 0 ? s0 : (dim == 1 ? s1 : s2);
+            const double dot = (s0 * (double)m.ki + s1 * (double)m.kj) + s2 * (double)m.kk;
+            const double amplitude =
+                amp[m.k2] * (0.5 * sd - ((1.5 * (double)kd) * dot) / (double)m.k2);
+            out = make_double2(amplitude * -z.y, amplitude * z.x);
+        }
+        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
+    }
+}
+
 // out[layer][j][k] (dense) from the real cells of the mesh's owned layers.
-// kVar 0: c0 * (1 + v); 1: the same after v += c1 * v²; 2: v * c0
+// kVar 0: c0 * (1 + v); 1: the same after v += c1 * v²; 2: v * c0; 3: out + c0 * v
 template <int kVar>
 __global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh, double *out,
                                                               int N, i64 nrows, i64 ny, i64 pad,
@@ -208,9 +273,16 @@ __global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh
         double2 v = *(const double2 *)(mesh + (layer * ny + (row - layer * N)) * pad + 2 * p);
         if (kVar == 1)  // ic.py:436
             v = make_double2(v.x + c1 * (v.x * v.x), v.y + c1 * (v.y * v.y));
-        if (kVar == 2) v = make_double2(v.x * c0, v.y * c0);  // ic.py:456
-        else v = make_double2(c0 * (1 + v.x), c0 * (1 + v.y));  // ic.py:437
-        *(double2 *)(out + row * N + 2 * p) = v;
+        double2 *o = (double2 *)(out + row * N + 2 * p);
+        if (kVar == 3) {  // fluid.py:1028, 1042
+            const double2 w = *o;
+            v = make_double2(w.x + c0 * v.x, w.y + c0 * v.y);
+        } else if (kVar == 2) {
+            v = make_double2(v.x * c0, v.y * c0);  // ic.py:456
+        } else {
+            v = make_double2(c0 * (1 + v.x), c0 * (1 + v.y));  // ic.py:437
+        }
+        *o = v;
     }
 }
 
@@ -318,6 +390,19 @@ int fourier_pair_checks(const char *name, cg_ctx *dst, cg_ctx *src) {
     CG_CHECK(same_geometry(dst, src), "%s: the two meshes differ in grid size or domain", name);
     CG_CHECK(dst->N * (i64)dst->f_nj < ((i64)1 << 31), "%s: %lld rows", name,
              (long long)(dst->N * (i64)dst->f_nj));
+    return 0;
+}
+
+// two meshes of a realisation in Fourier space and its k²-indexed table of amplitudes
+int realize_checks(const char *name, cg_ctx *out, cg_ctx *src, const double *amplitudes,
+                   int64_t k2_max) {
+    if (fourier_pair_checks(name, out, src)) return 1;
+    const i64 nyq = out->N / 2;
+    CG_CHECK(amplitudes != nullptr, "%s: no amplitudes", name);
+    CG_CHECK(k2_max == 3 * (nyq - 1) * (nyq - 1),
+             "%s: %lld amplitudes for grid size %lld, which needs 3*(nyquist - 1)**2 + 1 = %lld",
+             name, (long long)(k2_max + 1), (long long)out->N,
+             (long long)(3 * (nyq - 1) * (nyq - 1) + 1));
     return 0;
 }
 
@@ -486,13 +571,8 @@ extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
 
 extern "C" int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitudes, int64_t k2_max,
                                int tensor_rank, int index0) {
-    if (fourier_pair_checks("cg_realize_grid", out, noise)) return 1;
+    if (realize_checks("cg_realize_grid", out, noise, amplitudes, k2_max)) return 1;
     const i64 nyq = out->N / 2;
-    CG_CHECK(amplitudes != nullptr, "cg_realize_grid: no amplitudes");
-    CG_CHECK(k2_max == 3 * (nyq - 1) * (nyq - 1),
-             "cg_realize_grid: %lld amplitudes for grid size %lld, which needs "
-             "3*(nyquist - 1)**2 + 1 = %lld", (long long)(k2_max + 1), (long long)out->N,
-             (long long)(3 * (nyq - 1) * (nyq - 1) + 1));
     CG_CHECK(tensor_rank == 0 || tensor_rank == 1,
              "cg_realize_grid: tensor rank %d (0 and 1 are implemented)", tensor_rank);
     CG_CHECK(tensor_rank == 0 || (index0 >= 0 && index0 < 3),
@@ -507,6 +587,51 @@ extern "C" int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitu
     if (tensor_rank == 0) CG_REALIZE_GRID(0);
     else CG_REALIZE_GRID(1);
 #undef CG_REALIZE_GRID
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_realize_grid_tensor(cg_ctx *out, cg_ctx *structure, const double *amplitudes,
+                                      int64_t k2_max, int index0, int index1) {
+    if (realize_checks("cg_realize_grid_tensor", out, structure, amplitudes, k2_max)) return 1;
+    CG_CHECK(index0 >= 0 && index0 < 3 && index1 >= 0 && index1 < 3,
+             "cg_realize_grid_tensor: indices (%d, %d) not in {0, 1, 2}", index0, index1);
+    const i64 total = out->N * (i64)out->f_nj * (out->N / 2 + 1);
+    hipLaunchKernelGGL(k_realize_grid_tensor, dim3(grid_for(total)), dim3(kThreads), 0,
+                       out->stream, out->four, (const double2 *)structure->four, (int)out->N,
+                       out->f_si, structure->f_si, out->pad / 2, out->f_j0, out->f_nj, amplitudes,
+                       index0, index1);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_shear_divergence(cg_ctx *out, cg_ctx *structure, const double *amplitudes,
+                                   int64_t k2_max, int dim) {
+    if (realize_checks("cg_shear_divergence", out, structure, amplitudes, k2_max)) return 1;
+    CG_CHECK(dim >= 0 && dim < 3, "cg_shear_divergence: dim = %d not in {0, 1, 2}", dim);
+    CG_CHECK(out->N <= 4096, "cg_shear_divergence: grid size %lld above 4096 (the table of sines "
+             "is kept in LDS)", (long long)out->N);
+    const double inv_dx = (double)out->N / out->p.boxsize;
+    const i64 total = out->N * (i64)out->f_nj * (out->N / 2 + 1);
+    hipLaunchKernelGGL(k_shear_divergence, dim3(grid_for(total)), dim3(kThreads),
+                       (size_t)out->N * sizeof(double), out->stream, out->four,
+                       (const double2 *)structure->four, (int)out->N, out->f_si, structure->f_si,
+                       out->pad / 2, out->f_j0, out->f_nj, amplitudes, dim, inv_dx);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int cg_fluid_add_from_mesh(cg_ctx *mesh, double *out, double factor) {
+    CG_CHECK(mesh && out, "cg_fluid_add_from_mesh: null %s", mesh ? "output grid" : "context");
+    CG_CHECK(mesh->N >= 2 && mesh->N % 2 == 0,
+             "cg_fluid_add_from_mesh: grid size %lld is not even", (long long)mesh->N);
+    CG_CHECK((uintptr_t)out % 16 == 0,
+             "cg_fluid_add_from_mesh: the output grid is not 16-byte aligned");
+    const i64 nrows = mesh->xmap.nxl * mesh->N;
+    const i64 total = nrows * (mesh->N / 2);
+    hipLaunchKernelGGL(k_fluid_from_mesh<3>, dim3(grid_for(total)), dim3(kThreads), 0,
+                       mesh->stream, (const double *)mesh->mesh0, out, (int)mesh->N, nrows,
+                       mesh->ny, mesh->pad, factor, 0.0);
     CG_LAUNCH_CHECK();
     return 0;
 }

@@ -15,6 +15,14 @@ Kurganov-Tadmor, in the same scope: Runge-Kutta orders 1 and 2 and the nine flux
 launch per Runge-Kutta step with the pressure term in the flux (kurganov_tadmor); no vacuum
 correction exists in that scheme.
 
+Closure 'class' (a fluid whose hierarchy is closed by realising ς at every step from its own
+non-linear ϱ and the caller's table of transfer-function ratios) is opted into: shear_sources is
+the shear term of the Euler equation, ΔJⁱ = -ᔑa**(-3*w_eff)dt ∂ʲςⁱⱼ, with the divergence formed in
+Fourier space (csrc/cg_lpt.hip), closure_sources / closure_hooks the hooks of the time loop that
+know it, and the functions of the MacCormack path take closure_class=True.  Without the keyword
+the closure is refused as before; with it boltzmann_order ≠ 1, the P=wρ approximation off, a
+structure other than 'nonlinear', Kurganov-Tadmor and several domains are refused by name.
+
 Use is explicit — nothing calls this module on its own:
 
     stepper.Timeloop(comps, fluid_drift=fluid.drift, fluid_limiter=fluid.courant_limit,
@@ -101,16 +109,38 @@ def _neighbour_layers(component, tensors, H):
     return lo, hi
 
 
-def _check_scope(component, a):
+def _check_closure_class(component):
+    """what the shear term of closure 'class' (shear_sources) needs beyond _check_scope"""
+    from . import ic
+    name = component.name
+    ic.check_shear_scope(component)
+    if not component.approximations['P=wρ']:
+        raise ConceptGPUError(
+            f'{name}: Boltzmann closure "class" without the P=wρ approximation: the realisation '
+            'of δ𝒫 with CLASS and the Hubble term of the continuity equation (fluid.py:1059-1067) '
+            'are not implemented')
+    scheme = is_selected(component, component.params.fluid_scheme_select)
+    if scheme != 'maccormack':
+        raise ConceptGPUError(
+            f'{name}: Boltzmann closure "class" with the fluid scheme "{scheme}": the ς flux '
+            'inside the limiter stage of Kurganov-Tadmor (fluid.py:425-460) is not implemented, '
+            'only the source term of "maccormack"')
+
+
+def _check_scope(component, a, closure_class=False):
+    """closure_class: accept closure 'class' where the shear term is in scope (_check_closure_class);
+    without it the closure is refused as it always was."""
     if component.representation != 'fluid':
         raise ConceptGPUError(f'{component.name}: the fluid solver was given a particle component')
+    if closure_class and getattr(component, 'boltzmann_closure', 'truncate') == 'class':
+        _check_closure_class(component)
     if component.boltzmann_order > 1:
         raise ConceptGPUError(
             f'{component.name}: boltzmann_order = {component.boltzmann_order}: the non-linear '
             'evolution of ς and 𝒫 (the shear term of maccormack_internal_sources) is not '
             'implemented')
     closure = getattr(component, 'boltzmann_closure', 'truncate')
-    if closure != 'truncate':
+    if closure != 'truncate' and not (closure_class and closure == 'class'):
         raise ConceptGPUError(
             f'{component.name}: Boltzmann closure "{closure}": realising ς with CLASS (the shear '
             'term of maccormack_internal_sources) is not implemented, only "truncate"')
@@ -133,16 +163,16 @@ def _c2w(component, a):
     return component.params.light_speed**2*component.w(a=a)
 
 
-def realize_𝒫(component, a=1.0):
+def realize_𝒫(component, a=1.0, closure_class=False):
     """realize_if_linear(2, 'trace') under the P=wρ approximation (realize_approximative,
     ic.py:495-509): 𝒫 = ϱ*(c²w)."""
-    _check_scope(component, a)
+    _check_scope(component, a, closure_class)
     check(_L.cg_fluid_pressure_sources(
         _ctx(component), _ptr(component.ϱ), None, None, _ptr(component.𝒫), None,
         component.gridsize, component.nxl, float(_c2w(component, a)), 0.0, 0.0))
 
 
-def internal_sources(component, ᔑdt, a_next=-1):
+def internal_sources(component, ᔑdt, a_next=-1, closure_class=False):
     """maccormack_internal_sources (fluid.py:990-1067) within scope: the pressure term of the
     Euler equation, ΔJⁱ = -ᔑa**(-3*w_eff)dt ∂ⁱ𝒫, with the order-2 difference of diff_domaingrid
     (mesh.py:4966-4970).  The reference reads the 𝒫 grid that kick_long realised just before
@@ -151,7 +181,7 @@ def internal_sources(component, ᔑdt, a_next=-1):
     closure 'class' (refused), the Hubble term of the continuity equation to
     not approximations['P=wρ'], which species.py:1678-1685 rules out for this scope."""
     a = a_next if a_next != -1 else 1.0
-    _check_scope(component, a)
+    _check_scope(component, a, closure_class)
     p = component.params
     Δx = p.boxsize/component.gridsize
     lo, hi = _neighbour_layers(component, [component.ϱ], 1)
@@ -260,13 +290,16 @@ def finish(component, halve=True):
                                 _ptrs(st.Δ), component.ϱ.numel(), int(bool(halve))))
 
 
-def maccormack(component, ᔑdt, a_next=-1, record=None):
+def maccormack(component, ᔑdt, a_next=-1, record=None, closure_class=False):
     """maccormack (fluid.py:724-792).  component.maccormack_attempts holds the number of
-    attempts of the two steps of the last call, component.maccormack_sweeps the vacuum sweeps."""
+    attempts of the two steps of the last call, component.maccormack_sweeps the vacuum sweeps.
+    closure_class: take a component of closure 'class' too (its flux terms are these; its shear
+    term is a source, shear_sources)."""
     if component.boltzmann_order == 0:
         return   # no J variable: nothing to do (fluid.py:727-730)
     a = a_next if a_next != -1 else 1.0
-    _check_scope(component, a)
+    _check_scope(component, a, closure_class)
+    scope = {'closure_class': True} if closure_class else {}  # (callers without it: as before)
     # (a w = 0 component takes the path it always took: its 𝒫 grid is left as it is)
     pressure = getattr(component, 'w_constant', 0.0) != 0
     mc = component.params.fluid_options['maccormack']
@@ -287,7 +320,7 @@ def maccormack(component, ᔑdt, a_next=-1, record=None):
                 if mc_step == 0 and pressure:
                     # 𝒫 is re-realised from the unstarred ϱ before every first step
                     # (fluid.py:912-913) and used as it is in the second
-                    realize_𝒫(component, a)
+                    realize_𝒫(component, a, **scope)
                 maccormack_step(component, ᔑdt, steps, mc_step, halve=halved)
             if correct:
                 if not correct_vacuum(component, mc_step, record):
@@ -307,9 +340,9 @@ def maccormack(component, ᔑdt, a_next=-1, record=None):
     finish(component, halve=not halved)
 
 
-def drift(component, ᔑdt, a_end=-1):
+def drift(component, ᔑdt, a_end=-1, closure_class=False):
     """Component.drift for fluids (species.py:2200-2216); the `fluid_drift` hook of
-    stepper.Timeloop."""
+    stepper.Timeloop.  closure_class: as for maccormack()."""
     if component.representation != 'fluid':
         raise ConceptGPUError(f'{component.name}: fluid.drift() is for fluid components')
     scheme = is_selected(component, component.params.fluid_scheme_select)
@@ -317,7 +350,7 @@ def drift(component, ᔑdt, a_end=-1):
         raise ConceptGPUError(
             f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
             'Kurganov-Tadmor is outside this path)')
-    maccormack(component, ᔑdt, a_end)
+    maccormack(component, ᔑdt, a_end, **({'closure_class': True} if closure_class else {}))
 
 
 # -- the Kurganov-Tadmor scheme --------------------------------------------------------------------
@@ -451,11 +484,11 @@ def sources_selected(component, ᔑdt, a_next=-1):
     kurganov_tadmor_internal_sources(component, ᔑdt, a_next)
 
 
-def v_max(component, a):
+def v_max(component, a, closure_class=False):
     """measure(component, 'v_max') for a fluid with non-linear J (analysis.py:3940-3963): the
     largest bulk velocity plus the sound speed light_speed*sqrt(w)/a.  The 𝒫 grid is read as it
     stands (realize_𝒫 or the last source pass filled it)."""
-    _check_scope(component, a)
+    _check_scope(component, a, closure_class)
     if component.boltzmann_order == 0:
         return 0.0
     p = component.params
@@ -476,12 +509,78 @@ def v_max(component, a):
     return v
 
 
-def courant_limit(component, a):
+def courant_limit(component, a, closure_class=False):
     """The Courant condition on the base step (main.py:803-823, fac_courant of main.py:2413);
     the `fluid_limiter` hook of stepper.Timeloop."""
     p = component.params
     fac_courant = 0.21*p.Δt_base_nonlinear_factor
-    v = v_max(component, a)
+    v = v_max(component, a, closure_class=True) if closure_class else v_max(component, a)
     if v == 0:
         v = machine_ϵ   # a completely static component counts as just above 0
     return fac_courant*(p.boxsize/component.gridsize)/v
+
+
+# -- closure 'class': the shear term of the Euler equation -----------------------------------------
+def shear_sources(component, ᔑdt, amplitudes, a_next=-1, timings=None):
+    """The shear term of maccormack_internal_sources (fluid.py:1011-1043) for a component of
+    closure 'class' and boltzmann_order = 1: ΔJⁱ = -ᔑa**(-3*w_eff)dt ∂ʲςⁱⱼ, ς realised from the
+    component's own ϱ (ic.fluid_structure) and the k²-indexed table `amplitudes` of σ
+    (ic.amplitudes_from_transfer_ratio; the caller's transfer functions at a_next).
+
+    The reference realises the six ςⁱⱼ, each with a backward transform, and differentiates them
+    with the order-2 central difference.  On a periodic grid that difference along j is the
+    factor i·sin(2π kⱼ/gridsize)/Δx in Fourier space, so the divergence is formed there
+    (cg_shear_divergence): one forward transform of ϱ and three backward transforms, no ς grid.
+    ς itself is ic.realize_shear().  timings: a dict that receives milliseconds by kind of pass
+    (synchronises)."""
+    from . import ic
+    a = a_next if a_next != -1 else 1.0
+    _check_scope(component, a, closure_class=True)
+    if component.boltzmann_closure != 'class':
+        raise ConceptGPUError(
+            f'{component.name}: Boltzmann closure "{component.boltzmann_closure}" has no shear '
+            'term: shear_sources() is for closure "class"')
+    amplitudes_dev = ic._amplitudes_dev(component, amplitudes, component.gridsize,
+                                        'a fluid grid of {}³ cells')
+    # ς = ϱ_bar(1 + w)σ (ic.py:471-475) under the factor of the potential (fluid.py:1028)
+    factor = -ᔑdt['a**(-3*w_eff)', component.name]*(component.ϱ_bar*(1 + component.w(a=a)))
+    watch = ic._Stopwatch(timings)
+    with watch('structure'):
+        structure = ic.fluid_structure(component)
+    work = ic._realization_mesh(component, 'realize work')
+    for dim in range(3):
+        with watch('k-space'):
+            work.shear_divergence(structure, amplitudes_dev, dim)
+        with watch('transforms'):
+            work.poisson_backward()
+        with watch('stores'):
+            work.fluid_add_from_mesh(component.J[dim], factor)
+    watch.finish()
+
+
+def closure_sources(amplitudes_of):
+    """A `fluid_sources` hook of stepper.Timeloop that knows closure 'class'.  For a component
+    of that closure with boltzmann_order = 1 it calls amplitudes_of(component, a) for the
+    k²-indexed table of σ at the scale factor of the kick's end, applies the shear term
+    (shear_sources) and then the pressure term (internal_sources): the reference's order
+    (fluid.py:1011-1058).  Every other component goes to sources_selected() unchanged."""
+    def sources(component, ᔑdt, a_next=-1):
+        if (component.representation != 'fluid'
+                or getattr(component, 'boltzmann_closure', 'truncate') != 'class'):
+            return sources_selected(component, ᔑdt, a_next)
+        a = a_next if a_next != -1 else 1.0
+        _check_scope(component, a, closure_class=True)
+        shear_sources(component, ᔑdt, amplitudes_of(component, a), a_next)
+        if not (component.w_type == 'constant' and component.w_constant == 0):
+            internal_sources(component, ᔑdt, a_next, closure_class=True)
+    return sources
+
+
+def closure_hooks(amplitudes_of):
+    """The three fluid hooks of stepper.Timeloop with closure 'class' in scope:
+    Timeloop(components, **fluid.closure_hooks(amplitudes_of)).  Components of another closure
+    take the paths of drift(), courant_limit() and sources_selected()."""
+    import functools
+    return {'fluid_drift': functools.partial(drift, closure_class=True),
+            'fluid_limiter': functools.partial(courant_limit, closure_class=True),
+            'fluid_sources': closure_sources(amplitudes_of)}

@@ -23,9 +23,16 @@ GPU (csrc/cg_lpt.hip through PotentialMesh.lpt_*):
       -> back to real space                                       the mesh's inverse transform
       -> ϱ = ϱ_bar(1 + δ) or Jⁱ = a**(1 - 3w_eff)ϱ_bar(1 + w)uⁱ    fluid_from_mesh
 
+    the shear of closure 'class' (realize_shear; the time loop's path is fluid.shear_sources):
+      ϱ of the component itself, transformed forward                fluid_structure
+      -> amplitude·(½δₘₙ - (3/2)kₘkₙ/k²)·ℱ[ϱ]                        realize_grid_tensor
+      -> back to real space, ςₘₙ = ϱ_bar(1 + w)σₘₙ                  fluid_from_mesh
+    the table is the caller's (amplitudes_from_transfer_ratio), as for the particles.
+
 Out of scope, refused by name.  Particles: 3LPT and Orszag dealiasing unless extended=True,
-non-Gaussianity, non-primordial structure, N without a cubic lattice.  Fluids: the variables above J (ς, δP), closure 'class'.
-Both: several domains."""
+non-Gaussianity, non-primordial structure, N without a cubic lattice.  Fluids: δP, ς from the
+primordial noise or above boltzmann_order = 1; realize_fluid and realize refuse ς and closure
+'class' as they always did: ς is opted into through realize_shear.  Both: several domains."""
 import contextlib
 import math
 
@@ -987,6 +994,99 @@ def realize(component, a, amplitudes, amplitudes_θ=None, **kw):
     # 𝒫 = ϱ·ℝ[light_speed**2*w] (ic.py:504-508)
     torch.mul(component.ϱ, component.params.light_speed**2*component.w(a=a), out=component.𝒫)
     return noise
+
+
+# ---- the shear of closure 'class' (ic.py:471-475, 599-626, 743-762, 863-871) ------------------------
+def amplitudes_from_transfer_ratio(k, ratio, gridsize, boxsize, ϱ_bar):
+    """The k²-indexed table get_amplitudes makes for a variable realised from the non-linear
+    structure (ic.py:599-626, use_primordial False), from a tabulated ratio of transfer functions
+    T(k)/T_δ(k): amplitudes[k2] = ratio(k_f·√k2)·(gridsize**(-3)/ϱ_bar) for k2 = 1 ..
+    3(nyquist-1)², the ratio interpolated linearly in log k; amplitudes[0] = 0.  The gridsize⁻³
+    normalises the forward transform of ϱ, the 1/ϱ_bar turns ϱ into 1 + δ."""
+    k, ratio = np.asarray(k, dtype=np.float64), np.asarray(ratio, dtype=np.float64)
+    if k.ndim != 1 or k.shape != ratio.shape or k.size < 2 or np.any(np.diff(k) <= 0):
+        raise ConceptGPUError('amplitudes_from_transfer_ratio(): k must be increasing, ratio of '
+                              'its length')
+    nyquist = int(gridsize)//2
+    k2_max = 3*(nyquist - 1)**2
+    k_fundamental = 2*π/boxsize
+    amplitudes = np.zeros(k2_max + 1, dtype=np.float64)
+    k_magnitude = k_fundamental*np.sqrt(np.arange(1, k2_max + 1, dtype=np.float64))
+    if k2_max and (k_magnitude[0] < k[0] or k_magnitude[-1] > k[-1]):
+        raise ConceptGPUError(
+            f'amplitudes_from_transfer_ratio(): the table covers k in [{k[0]}, {k[-1]}], the grid '
+            f'needs [{k_magnitude[0]}, {k_magnitude[-1]}]')
+    amplitudes[1:] = np.interp(np.log(k_magnitude), np.log(k), ratio)*(
+        float(gridsize)**(-3)/ϱ_bar)
+    return amplitudes
+
+
+def check_shear_scope(component):
+    """what the realisation of ς needs of a component; fluid.py adds what the Euler equation needs"""
+    name = component.name
+    if component.representation != 'fluid':
+        raise ConceptGPUError(f'{name}: the shear ς is a variable of fluid components')
+    closure = getattr(component, 'boltzmann_closure', 'truncate')
+    if closure != 'class' or component.boltzmann_order != 1:
+        raise ConceptGPUError(
+            f'{name}: Boltzmann closure "{closure}" with boltzmann_order = '
+            f'{component.boltzmann_order}: ς is realised for closure "class" at boltzmann_order = 1 '
+            '(non-linear ϱ and J) alone; a non-linear ς or 𝒫 and a linear J are not implemented')
+    structure = is_selected(component, component.params.realization_options['structure'])
+    if structure != 'nonlinear':
+        raise ConceptGPUError(
+            f'{name}: realization_options["structure"] = "{structure}": ς is realised from the '
+            'component\'s own density field, select "nonlinear" for it (ς from the primordial '
+            'noise is not implemented)')
+    if _comm.active() is not None or getattr(component, 'nprocs', 1) > 1:
+        raise ConceptGPUError(f'{name}: the realisation of ς with an active comm process group: '
+                              'multi-GPU realisation is not implemented')
+
+
+def fluid_structure(component, out=None):
+    """ℱₓ[ϱ(x⃗)] of a fluid component (get_slab_structure, ic.py:863-871): its ϱ grid as plain
+    values in a realisation mesh (`out`, or the component's own), transformed forward,
+    unnormalised.  No deposit factor and no deconvolution apply.  Returns the mesh."""
+    mesh = out if out is not None else _realization_mesh(component, 'realize structure')
+    if mesh.gridsize != component.gridsize:
+        raise ConceptGPUError(f'{component.name}: a structure mesh of grid size {mesh.gridsize} '
+                              f'for a fluid of grid size {component.gridsize}')
+    mesh.fluid_add(component.ϱ, 1.0, '=')
+    mesh.fft_forward()
+    return mesh
+
+
+def realize_shear(component, a, amplitudes, multi_index=(0, 0), structure=None, out=None):
+    """ςₘₙ of a fluid component with closure 'class' at scale factor a (realize_fluid with
+    variable 2, ic.py:400-475, the non-compound case), realised from the component's own
+    non-linear density: amplitudes[k²]·(½δₘₙ - (3/2)kₘkₙ/k²)·ℱ[ϱ], back to real space, times
+    ϱ_bar(1 + w).  The inspection and test path: the time loop forms the divergence of ς in
+    Fourier space without the six grids (fluid.shear_sources).
+
+    amplitudes: the k²-indexed table of σ (amplitudes_from_transfer_ratio).
+    structure: the mesh fluid_structure() returned, to realise several elements from one
+      transform of ϱ.
+    out: a (gridsize, gridsize, gridsize) device tensor to receive ςₘₙ; it is not stored on the
+      component.  Returns it."""
+    check_shear_scope(component)
+    try:
+        index0, index1 = (int(i) for i in multi_index)
+    except (TypeError, ValueError):
+        index0 = index1 = -1
+    if not (0 <= index0 < 3 and 0 <= index1 < 3):
+        raise ConceptGPUError(f'{component.name}: realize_shear() needs a multi_index (m, n) with '
+                              f'm, n in {{0, 1, 2}}, not {multi_index!r}')
+    gridsize = component.gridsize
+    amplitudes_dev = _amplitudes_dev(component, amplitudes, gridsize, 'a fluid grid of {}³ cells')
+    if structure is None:
+        structure = fluid_structure(component)
+    if out is None:
+        out = torch.empty_like(component.ϱ)
+    work = _realization_mesh(component, 'realize work')
+    work.realize_grid_tensor(structure, amplitudes_dev, index0, index1)
+    work.poisson_backward()
+    # σⁱⱼ → ςⁱⱼ ≈ ϱ_bar(1 + w)σⁱⱼ (ic.py:471-475)
+    return work.fluid_from_mesh(out, 1, component.ϱ_bar*(1 + component.w(a=a)))
 
 
 def _amplitudes_dev(component, amplitudes, gridsize, what='a lattice of {}³ particles'):

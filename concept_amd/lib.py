@@ -167,6 +167,9 @@ SYMBOLS = {
     'cg_lpt_shrink_accumulate': (_int, [_vp, _vp, _int, _dbl]),
     'cg_realize_grid': (_int, [_vp, _vp, _vp, _i64, _int, _int]),
     'cg_fluid_from_mesh': (_int, [_vp, _vp, _int, _dbl, _dbl]),
+    'cg_realize_grid_tensor': (_int, [_vp, _vp, _vp, _i64, _int, _int]),
+    'cg_shear_divergence': (_int, [_vp, _vp, _vp, _i64, _int]),
+    'cg_fluid_add_from_mesh': (_int, [_vp, _vp, _dbl]),
     'cg_noise_trip': (_int, []),
     'cg_noise_generate': (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _dbl]),
     'cg_fluid_kt_step': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _int, _int, _dbl, _dbl,

@@ -608,14 +608,42 @@ class PotentialMesh:
     def realize_grid(self, noise, amplitudes, tensor_rank=0, index0=0):
         """realize_grid (ic.py:708-764) without a lattice shift: the Fourier content of `noise`
         times amplitudes[k2] (rank 0), and for rank 1 times -i·k_index0/k², into this mesh."""
-        if (amplitudes.dtype != torch.float64 or amplitudes.device != self.device
-                or not amplitudes.is_contiguous() or amplitudes.dim() != 1):
-            raise lib.ConceptGPUError(
-                f'realize_grid(): amplitudes must be a contiguous 1D float64 tensor on '
-                f'{self.device}')
+        self._check_amplitudes('realize_grid', amplitudes)
         check(_L.cg_realize_grid(self._ctx, noise._ctx, _ptr(amplitudes), amplitudes.numel() - 1,
                                  int(tensor_rank), int(index0)))
         return self
+
+    def _check_amplitudes(self, caller, amplitudes):
+        if (amplitudes.dtype != torch.float64 or amplitudes.device != self.device
+                or not amplitudes.is_contiguous() or amplitudes.dim() != 1):
+            raise lib.ConceptGPUError(
+                f'{caller}(): amplitudes must be a contiguous 1D float64 tensor on '
+                f'{self.device}')
+
+    def realize_grid_tensor(self, structure, amplitudes, index0, index1):
+        """The rank-2 case of realize_grid (ic.py:743-762) for the element (index0, index1): the
+        Fourier content of `structure` times amplitudes[k2]·(½δ - (3/2)·k_index0·k_index1/k²),
+        into this mesh."""
+        self._check_amplitudes('realize_grid_tensor', amplitudes)
+        check(_L.cg_realize_grid_tensor(self._ctx, structure._ctx, _ptr(amplitudes),
+                                        amplitudes.numel() - 1, int(index0), int(index1)))
+        return self
+
+    def shear_divergence(self, structure, amplitudes, dim):
+        """Σⱼ ∂ʲ of the elements (dim, j) of realize_grid_tensor, ∂ʲ the order-2 central difference
+        of diff_domaingrid (mesh.py:4966-4970) as the factor i·sin(2π kⱼ/gridsize)/Δx, in one pass
+        from the Fourier content of `structure` into this mesh (fluid.py:1011-1043)."""
+        self._check_amplitudes('shear_divergence', amplitudes)
+        check(_L.cg_shear_divergence(self._ctx, structure._ctx, _ptr(amplitudes),
+                                     amplitudes.numel() - 1, int(dim)))
+        return self
+
+    def fluid_add_from_mesh(self, out, factor):
+        """out += factor × this mesh's real-space content, `out` a dense fluid grid (this domain's
+        layers): fluid_from_mesh as an accumulation (fluid.py:1028, 1042)."""
+        self._check_fluid(out)
+        check(_L.cg_fluid_add_from_mesh(self._ctx, _ptr(out), float(factor)))
+        return out
 
     def fluid_from_mesh(self, out, variable, c0, c1=0.0):
         """This mesh's real-space content into the dense fluid grid `out` (this domain's

@@ -904,6 +904,35 @@ int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitudes /*DEV k
                     int64_t k2_max, int tensor_rank, int index0);
 int cg_fluid_from_mesh(cg_ctx *mesh, double *out /*DEV nxl*N*N*/, int mode, double c0, double c1);
 
+/* --- fluid closure 'class': the shear and its term of the Euler equation --------------------
+ * (ic.py:743-762, 863-871; fluid.py:1011-1043; mesh.py:4966-4970.)  `structure` holds the
+ * unnormalised forward transform of a fluid's own density grid (get_slab_structure with
+ * realization_options['structure'] = 'nonlinear', ic.py:863-871: cg_fluid_add with factor 1 and
+ * operation '=', then cg_poisson_forward without its kernel), the contexts' Fourier views as above.
+ * cg_realize_grid_tensor: the rank-2 case of realize_grid (ic.py:743-762) for one element
+ *   (index0, index1): k2 = (kj^2 + ki^2) + kk^2, amplitude = amplitudes[k2]*K with
+ *   K = 0.5*(index0 == index1) - ((1.5*k_index0)*k_index1)/k2 (K = 3/2 (delta_ij/3 - k_i k_j/k^2)),
+ *   out = (amplitude*re, amplitude*im); the origin and the three Nyquist planes are written as 0
+ *   (ic.py:764).  The checks of cg_realize_grid; out may be structure.
+ * cg_shear_divergence: the divergence over j of the elements (dim, j) in one pass, with the
+ *   order-2 central difference of diff_domaingrid (mesh.py:4966-4970) taken in Fourier space: on a
+ *   periodic grid (f[x + 1] - f[x - 1])*((1/2)/dx) multiplies mode k by i*sin(2 pi k_j/N)/dx, so
+ *   out = (amplitudes[k2]*S)*i*structure, S = sum_j s_j*K_dim,j = 0.5*s_dim -
+ *   ((1.5*k_dim)*(s_0 ki + s_1 kj + s_2 kk))/k2, s_j = sin(2 pi k_j/N)/dx, dx = boxsize/N; (re, im)
+ *   -> (-im, re).  The sines are tabulated once per workgroup from the integer wave numbers.  The
+ *   origin and the Nyquist planes are written as 0 (the reference nullifies them in every element
+ *   before it differentiates).  Its inverse transform is d_j sigma_dim,j of the six-grid route to
+ *   rounding.  One domain size N <= 4096 (the table is N doubles of LDS).
+ * cg_fluid_add_from_mesh: the accumulating sibling of cg_fluid_from_mesh: out[(x*N + j)*N + k] +=
+ *   factor*value over the real-space content of `mesh`, product and sum rounded in turn; for the
+ *   shear term factor = -dt[a^(-3 w_eff)]*rho_bar*(1 + w) (ic.py:471-475, fluid.py:1028, 1042). */
+int cg_realize_grid_tensor(cg_ctx *out, cg_ctx *structure,
+                           const double *amplitudes /*DEV k2_max + 1*/, int64_t k2_max, int index0,
+                           int index1);
+int cg_shear_divergence(cg_ctx *out, cg_ctx *structure,
+                        const double *amplitudes /*DEV k2_max + 1*/, int64_t k2_max, int dim);
+int cg_fluid_add_from_mesh(cg_ctx *mesh, double *out /*DEV nxl*N*N*/, double factor);
+
 /* --- initial conditions: the primordial noise on the device (ic.py:928-1163) ---------------
  * cg_noise_generate: the primordial white noise of the 'distributed' imprinting scheme
  *   (ic.py:928-1163) written into the Fourier view of `mesh` (one domain), from the reference's
