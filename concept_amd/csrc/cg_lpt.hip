@@ -1,4 +1,5 @@
-// cg_lpt.hip — the mesh and particle passes of the realisations: 1LPT / 2LPT particles, fluids.
+// cg_lpt.hip — the mesh and particle passes of the realisations: particles (1LPT to 3LPT, with
+// Orszag dealiasing), fluids (ϱ, Jⁱ) and the shear of closure 'class'.
 //   k_lpt_potential  realize_grid (scalar case)         ic.py:711-764
 //                    fused with laplacian_inverse       mesh.py:3422-3437
 //   k_lpt_diff       fourier_diff                       mesh.py:3466-3510
@@ -15,13 +16,20 @@
 //   k_lpt_dealias_cube       nullify_modes('beyond cube of |k| < …')       ic.py:2025
 //   k_lpt_shrink_accumulate  resize_grid down + the move to the output     ic.py:2029-2057
 // All of them are streaming maps: one grid-stride loop, a thread per complex mode or per pair of
-// neighbouring real cells (16-byte loads and stores), no LDS, no atomics, nothing wave-level.
-// The k-space kernels walk the Fourier view of the contexts (cg_ctx::four, the view
-// k_fourier_operate walks) over the N/2 + 1 modes of every row, the real-space kernels the N
-// cells of the N rows of the owned layers: the row padding and the unused row of a layer are
-// neither read nor written.  Compiled with -ffp-contract=off: every product and sum is rounded
-// on its own, in the reference's order.  FP64 throughout.  The k-space kernels share their walk
-// over the modes: kspace_mode (cg_kspace.h).
+// neighbouring real cells (16-byte loads and stores), no atomics, nothing wave-level, and no LDS
+// but the sine table of k_shear_divergence.  A kernel is the body of one of two walks:
+//   for_each_mode / write_each_mode  the modes of a Fourier view of the contexts (cg_ctx::four,
+//                    the view k_fourier_operate walks), N/2 + 1 of every row, by kspace_mode
+//                    (cg_kspace.h); a mode's address comes from a Slab
+//   for_each_cell_pair  the N cells of the N rows of a mesh's owned layers: the row padding and the
+//                    unused row of a layer are neither read nor written
+// and the bodies share wave_number, derivative (fourier_diff's rounding), rotate (the lattice
+// shift and the size-change phase) and accumulate ('=', '+=', '-=' with a factor).  On the host:
+// launch, with_case (a template argument from a run-time integer) and the *_checks.
+// Compiled with -ffp-contract=off, and every function that rounds says so itself: every product
+// and sum is rounded on its own, in the reference's order.  FP64 throughout.
+#include <type_traits>
+
 #include "cg_internal.h"
 #include "cg_kspace.h"
 
@@ -34,6 +42,117 @@ const double kPi = 3.141592653589793;  // float(np.pi), commons.py:1816
 unsigned grid_for(i64 work) {
     i64 b = (work + kThreads - 1) / kThreads;
     return (unsigned)(b < 1 ? 1 : (b > kMaxBlocks ? kMaxBlocks : b));
+}
+
+// one thread per item of `work`, up to kMaxBlocks workgroups
+template <class Kernel, class... Args>
+int launch(Kernel kernel, i64 work, size_t lds_bytes, hipStream_t stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(work)), dim3(kThreads), lds_bytes, stream, args...);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+// f(std::integral_constant<int, K>) for K = which.  The last of the kCases takes whatever is left,
+// as the `else` of a chain does: the caller has refused a `which` outside 0 .. kCases - 1 before
+template <int kCases, int K = 0, class F>
+int with_case(int which, F f) {
+    if constexpr (K + 1 < kCases) {
+        if (which != K) return with_case<kCases, K + 1>(which, f);
+    }
+    return f(std::integral_constant<int, K>{});
+}
+
+// ---- the Fourier view and the walk over its modes
+
+// complex[N][nj][N/2 + 1] at p, rows `cp` and slices `si` complex numbers apart
+template <class T>
+struct SlabOf {
+    T *p;
+    i64 si, cp;
+    __device__ __forceinline__ T *at_index(i64 a, i64 bl, i64 kk) const {
+        return p + (a * si + bl * cp + kk);
+    }
+    __device__ __forceinline__ T *at(KspaceMode m) const { return at_index(m.a, m.bl, m.kk); }
+    // by signed wave numbers, in a (whole) grid of size n
+    __device__ __forceinline__ T *at_wave(i64 ki, i64 kj, i64 kk, int n) const {
+        return at_index(ki + (ki < 0 ? n : 0), kj + (kj < 0 ? n : 0), kk);
+    }
+};
+using Slab = SlabOf<double2>;
+using ConstSlab = SlabOf<const double2>;
+
+Slab slab(const cg_ctx *c) { return Slab{c->four, c->f_si, c->pad / 2}; }
+ConstSlab const_slab(const cg_ctx *c) { return ConstSlab{c->four, c->f_si, c->pad / 2}; }
+i64 mode_count(i64 N, i64 nj) { return N * nj * (N / 2 + 1); }
+
+// body(m) for every mode of the rows j0 .. j0 + nj of a grid of size N
+template <class Body>
+__device__ __forceinline__ void for_each_mode(int N, int j0, int nj, Body body) {
+    const i64 total = (i64)N * nj * (N / 2 + 1);
+    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
+         e += (i64)gridDim.x * kThreads)
+        body(kspace_mode(e, N, j0, nj));
+}
+
+// dst = value(m) at every mode: each one is written exactly once
+template <class Value>
+__device__ __forceinline__ void write_each_mode(Slab dst, int N, int j0, int nj, Value value) {
+    for_each_mode(N, j0, nj, [=](KspaceMode m) { *dst.at(m) = value(m); });
+}
+
+__device__ __forceinline__ double2 zero2() { return make_double2(0.0, 0.0); }
+
+__device__ __forceinline__ i64 wave_number(KspaceMode m, int dim) {
+    return dim == 0 ? m.ki : (dim == 1 ? m.kj : m.kk);
+}
+
+// scale * i k_dim0 z (dim1 < 0) or scale * -k_dim0 k_dim1 z: fourier_diff
+__device__ __forceinline__ double2 derivative(KspaceMode m, double2 z, int dim0, int dim1,
+                                              double scale) {
+#pragma clang fp contract(off)
+    const i64 kl0 = wave_number(m, dim0);
+    if (dim1 < 0) {
+        const double amplitude = scale * (double)kl0;  // mesh.py:3496
+        return make_double2(amplitude * -z.y, amplitude * z.x);
+    }
+    const i64 kl1 = wave_number(m, dim1);
+    const double amplitude = scale * (double)kl0 * (double)kl1;  // mesh.py:3506
+    return make_double2(amplitude * -z.x, amplitude * -z.y);
+}
+
+// z exp(i theta): mesh.py:2873-2888 (lattice shift), mesh.py:1310-1313 (change of size)
+__device__ __forceinline__ double2 rotate(double2 z, double theta) {
+#pragma clang fp contract(off)
+    const double c = cos(theta), s = sin(theta);
+    return make_double2(z.x * c - z.y * s, z.x * s + z.y * c);
+}
+
+// *o (= | += | -=) factor * v, factor and sum rounded in turn, a factor of 1 left out
+template <int kOp>
+__device__ __forceinline__ void accumulate(double2 *o, double2 v, double factor) {
+#pragma clang fp contract(off)
+    if (factor != 1) v = make_double2(factor * v.x, factor * v.y);  // ic.py:2042-2057
+    if (kOp == 0) {
+        *o = v;
+    } else {
+        const double2 w = *o;
+        *o = kOp == 1 ? make_double2(w.x + v.x, w.y + v.y) : make_double2(w.x - v.x, w.y - v.y);
+    }
+}
+
+// body(offset in the mesh, offset in a dense [nrows][N] array) for every pair of neighbouring
+// real cells of the nrows = layers * N rows of a mesh's owned layers (N is even)
+template <class Body>
+__device__ __forceinline__ void for_each_cell_pair(int N, i64 nrows, i64 ny, i64 pad, Body body) {
+    const int half = N / 2;  // pairs of cells per row
+    const i64 total = nrows * half;
+    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
+         t += (i64)gridDim.x * kThreads) {
+        const i64 row = t / half;
+        const int p = (int)(t - row * half);
+        const i64 layer = row / N;
+        body((layer * ny + (row - layer * N)) * pad + 2 * p, row * N + 2 * p);
+    }
 }
 
 bool same_geometry(const cg_ctx *a, const cg_ctx *b) {
@@ -50,63 +169,30 @@ struct LptPotential {
 };
 
 // dst = (amp[k2] * rotated src) * (lap / k2) off the origin and the Nyquist planes, 0 on them
-__global__ __launch_bounds__(kThreads) void k_lpt_potential(double2 *dst, const double2 *src,
-                                                            int N, i64 dst_si, i64 src_si, i64 cp,
-                                                            int j0, int nj, LptPotential P) {
+__global__ __launch_bounds__(kThreads) void k_lpt_potential(Slab dst, ConstSlab src, int N, int j0,
+                                                            int nj, LptPotential P) {
+    write_each_mode(dst, N, j0, nj, [=](KspaceMode m) {
 #pragma clang fp contract(off)
-    const i64 total = (i64)N * nj * (N / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, N, j0, nj);
-        double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
-        if (m.live) {
-            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
-            double re = z.x, im = z.y;
-            if (P.shifted) {  // mesh.py:2873-2888, ic.py:719-726
-                const double theta =
-                    ((double)m.ki * P.A + (double)m.kj * P.B) + (double)m.kk * P.Cc;
-                const double c = cos(theta), s = sin(theta);
-                const double re2 = re * c - im * s, im2 = re * s + im * c;
-                re = re2;
-                im = im2;
-            }
-            if (P.amp) {  // ic.py:715, 761-762
-                const double amplitude = P.amp[m.k2];
-                re = amplitude * re;
-                im = amplitude * im;
-            }
-            const double inv = P.lap / (double)m.k2;  // mesh.py:3434-3436
-            out = make_double2(re * inv, im * inv);
+        if (!m.live) return zero2();  // nullify_modes(['origin', 'nyquist']), ic.py:764
+        double2 z = *src.at(m);
+        if (P.shifted)  // mesh.py:2873-2888, ic.py:719-726
+            z = rotate(z, ((double)m.ki * P.A + (double)m.kj * P.B) + (double)m.kk * P.Cc);
+        if (P.amp) {  // ic.py:715, 761-762
+            const double amplitude = P.amp[m.k2];
+            z = make_double2(amplitude * z.x, amplitude * z.y);
         }
-        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
-    }
+        const double inv = P.lap / (double)m.k2;  // mesh.py:3434-3436
+        return make_double2(z.x * inv, z.y * inv);
+    });
 }
 
 // dst = i k_dim0 src (dim1 < 0) or -k_dim0 k_dim1 src, times factor; 0 on the origin and the
 // Nyquist planes (the nullified output slab of mesh.py:3477)
-__global__ __launch_bounds__(kThreads) void k_lpt_diff(double2 *dst, const double2 *src, int N,
-                                                       i64 dst_si, i64 src_si, i64 cp, int j0,
+__global__ __launch_bounds__(kThreads) void k_lpt_diff(Slab dst, ConstSlab src, int N, int j0,
                                                        int nj, int dim0, int dim1, double scale) {
-#pragma clang fp contract(off)
-    const i64 total = (i64)N * nj * (N / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, N, j0, nj);
-        double2 out = make_double2(0.0, 0.0);
-        if (m.live) {
-            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
-            const i64 kl0 = dim0 == 0 ? m.ki : (dim0 == 1 ? m.kj : m.kk);
-            if (dim1 < 0) {
-                const double amplitude = scale * (double)kl0;  // mesh.py:3496
-                out = make_double2(amplitude * -z.y, amplitude * z.x);
-            } else {
-                const i64 kl1 = dim1 == 0 ? m.ki : (dim1 == 1 ? m.kj : m.kk);
-                const double amplitude = scale * (double)kl0 * (double)kl1;  // mesh.py:3506
-                out = make_double2(amplitude * -z.x, amplitude * -z.y);
-            }
-        }
-        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
-    }
+    write_each_mode(dst, N, j0, nj, [=](KspaceMode m) {
+        return m.live ? derivative(m, *src.at(m), dim0, dim1, scale) : zero2();
+    });
 }
 
 // out (= | += | -=) factor * a * b over the real cells; the three grids may be one another:
@@ -117,26 +203,12 @@ template <int kOp>
 __global__ __launch_bounds__(kThreads) void k_lpt_product(double *out, const double *a,
                                                           const double *b, int N, i64 nrows, i64 ny,
                                                           i64 pad, double factor) {
+    for_each_cell_pair(N, nrows, ny, pad, [=](i64 off, i64) {
 #pragma clang fp contract(off)
-    const int half = N / 2;  // pairs of cells per row (N is even)
-    const i64 total = nrows * half;
-    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
-         t += (i64)gridDim.x * kThreads) {
-        const i64 row = t / half;
-        const int p = (int)(t - row * half);
-        const i64 layer = row / N;
-        const i64 off = (layer * ny + (row - layer * N)) * pad + 2 * p;
         const double2 x = *(const double2 *)(a + off), y = *(const double2 *)(b + off);
-        double2 v = make_double2(x.x * y.x, x.y * y.y);  // ic.py:2020-2021
-        if (factor != 1) v = make_double2(factor * v.x, factor * v.y);  // ic.py:2042-2057
-        double2 *o = (double2 *)(out + off);
-        if (kOp == 0) {
-            *o = v;
-        } else {
-            const double2 w = *o;
-            *o = kOp == 1 ? make_double2(w.x + v.x, w.y + v.y) : make_double2(w.x - v.x, w.y - v.y);
-        }
-    }
+        const double2 v = make_double2(x.x * y.x, x.y * y.y);  // ic.py:2020-2021
+        accumulate<kOp>((double2 *)(out + off), v, factor);
+    });
 }
 
 // particle p = (i*N + j)*N + k of the rows from index_bgn on takes cell (i, j, k) of psi
@@ -144,16 +216,10 @@ __global__ __launch_bounds__(kThreads) void k_lpt_displace(const double *psi, in
                                                            i64 pad, double *pos, double *mom,
                                                            int dim, double pos_factor,
                                                            double mom_factor) {
+    for_each_cell_pair(N, (i64)N * N, ny, pad, [=](i64 off, i64 cell) {
 #pragma clang fp contract(off)
-    const int half = N / 2;
-    const i64 total = (i64)N * N * half;
-    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
-         t += (i64)gridDim.x * kThreads) {
-        const i64 row = t / half;  // i*N + j
-        const int kp = (int)(t - row * half);
-        const i64 i = row / N;
-        const double2 v = *(const double2 *)(psi + (i * ny + (row - i * N)) * pad + 2 * kp);
-        const i64 r = 3 * (row * N + 2 * kp) + dim;
+        const double2 v = *(const double2 *)(psi + off);
+        const i64 r = 3 * cell + dim;
         if (pos_factor != 0) {  // ic.py:2277-2279 (1*psi is psi: no branch for a factor of 1)
             pos[r] = pos[r] + pos_factor * v.x;
             pos[r + 3] = pos[r + 3] + pos_factor * v.y;
@@ -162,62 +228,49 @@ __global__ __launch_bounds__(kThreads) void k_lpt_displace(const double *psi, in
             mom[r] = mom[r] + mom_factor * v.x;
             mom[r + 3] = mom[r + 3] + mom_factor * v.y;
         }
-    }
+    });
 }
 
 // dst = amp[k2] * src (rank 0) or (amp[k2] * ((vec * k_index0) / k2)) * i src (rank 1) off the
 // origin and the Nyquist planes, 0 on them; vec = ℝ[-boxsize/(2*π)] of ic.py:741
 template <int kRank>
-__global__ __launch_bounds__(kThreads) void k_realize_grid(double2 *dst, const double2 *src, int N,
-                                                           i64 dst_si, i64 src_si, i64 cp, int j0,
+__global__ __launch_bounds__(kThreads) void k_realize_grid(Slab dst, ConstSlab src, int N, int j0,
                                                            int nj, const double *amp, int index0,
                                                            double vec) {
+    write_each_mode(dst, N, j0, nj, [=](KspaceMode m) {
 #pragma clang fp contract(off)
-    const i64 total = (i64)N * nj * (N / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, N, j0, nj);
-        double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
-        if (m.live) {
-            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
-            double amplitude = amp[m.k2];  // ic.py:715
-            double re = z.x, im = z.y;
-            if (kRank == 1) {  // K(k) = -i k^l/k², ic.py:732-742
-                const i64 kl = index0 == 0 ? m.ki : (index0 == 1 ? m.kj : m.kk);
-                amplitude = amplitude * ((vec * (double)kl) / (double)m.k2);
-                re = -z.y;
-                im = z.x;
-            }
-            out = make_double2(amplitude * re, amplitude * im);  // ic.py:761-762
+        if (!m.live) return zero2();  // nullify_modes(['origin', 'nyquist']), ic.py:764
+        const double2 z = *src.at(m);
+        double amplitude = amp[m.k2];  // ic.py:715
+        double re = z.x, im = z.y;
+        if (kRank == 1) {  // K(k) = -i k^l/k², ic.py:732-742
+            const i64 kl = wave_number(m, index0);
+            amplitude = amplitude * ((vec * (double)kl) / (double)m.k2);
+            re = -z.y;
+            im = z.x;
         }
-        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
-    }
+        return make_double2(amplitude * re, amplitude * im);  // ic.py:761-762
+    });
 }
 
 // dst = (amp[k2] * K) * src off the origin and the Nyquist planes, 0 on them;
 // K = 0.5 [index0 == index1] - ((1.5 k_index0) k_index1) / k2, ic.py:744-759
-__global__ __launch_bounds__(kThreads) void k_realize_grid_tensor(double2 *dst, const double2 *src,
-                                                                  int N, i64 dst_si, i64 src_si,
-                                                                  i64 cp, int j0, int nj,
+__global__ __launch_bounds__(kThreads) void k_realize_grid_tensor(Slab dst, ConstSlab src, int N,
+                                                                  int j0, int nj,
                                                                   const double *amp, int index0,
                                                                   int index1) {
 #pragma clang fp contract(off)
     const double half_delta = 0.5 * (index0 == index1);  // ℝ[0.5*(index0 == index1)]
-    const i64 total = (i64)N * nj * (N / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, N, j0, nj);
-        double2 out = make_double2(0.0, 0.0);  // nullify_modes(['origin', 'nyquist']), ic.py:764
-        if (m.live) {
-            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
-            const i64 kl = index0 == 0 ? m.ki : (index0 == 1 ? m.kj : m.kk);
-            const i64 km = index1 == 0 ? m.ki : (index1 == 1 ? m.kj : m.kk);
-            const double amplitude =
-                amp[m.k2] * (half_delta - ((1.5 * (double)kl) * (double)km) / (double)m.k2);
-            out = make_double2(amplitude * z.x, amplitude * z.y);  // ic.py:761-762
-        }
-        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
-    }
+    write_each_mode(dst, N, j0, nj, [=](KspaceMode m) {
+#pragma clang fp contract(off)
+        if (!m.live) return zero2();  // nullify_modes(['origin', 'nyquist']), ic.py:764
+        const double2 z = *src.at(m);
+        const i64 kl = wave_number(m, index0);
+        const i64 km = wave_number(m, index1);
+        const double amplitude =
+            amp[m.k2] * (half_delta - ((1.5 * (double)kl) * (double)km) / (double)m.k2);
+        return make_double2(amplitude * z.x, amplitude * z.y);  // ic.py:761-762
+    });
 }
 
 // dst = (amp[k2] * S) * i src off the origin and the Nyquist planes, 0 on them;
@@ -225,11 +278,9 @@ __global__ __launch_bounds__(kThreads) void k_realize_grid_tensor(double2 *dst, 
 // k_realize_grid_tensor and s_j = sin(2π k_j/N)/Δx, the order-2 central difference of
 // diff_domaingrid (mesh.py:4966-4970) in Fourier space.  The N sines by array index are
 // tabulated once per workgroup (dynamic LDS, N doubles): a mode reads three of them.
-__global__ __launch_bounds__(kThreads) void k_shear_divergence(double2 *dst, const double2 *src,
-                                                               int N, i64 dst_si, i64 src_si,
-                                                               i64 cp, int j0, int nj,
-                                                               const double *amp, int dim,
-                                                               double inv_dx) {
+__global__ __launch_bounds__(kThreads) void k_shear_divergence(Slab dst, ConstSlab src, int N,
+                                                               int j0, int nj, const double *amp,
+                                                               int dim, double inv_dx) {
 #pragma clang fp contract(off)
     extern __shared__ double s_sin[];
     for (int a = threadIdx.x; a < N; a += kThreads) {
@@ -237,23 +288,18 @@ __global__ __launch_bounds__(kThreads) void k_shear_divergence(double2 *dst, con
         s_sin[a] = sinpi((double)(2 * k) / (double)N) * inv_dx;
     }
     __syncthreads();
-    const i64 total = (i64)N * nj * (N / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, N, j0, nj);
-        double2 out = make_double2(0.0, 0.0);
-        if (m.live) {
-            const double2 z = src[(i64)m.a * src_si + (i64)m.bl * cp + m.kk];
-            const double s0 = s_sin[m.a], s1 = s_sin[j0 + m.bl], s2 = s_sin[m.kk];
-            const i64 kd = dim == 0 ? m.ki : (dim == 1 ? m.kj : m.kk);
-            const double sd = dim == 0 ? s0 : (dim == 1 ? s1 : s2);
-            const double dot = (s0 * (double)m.ki + s1 * (double)m.kj) + s2 * (double)m.kk;
-            const double amplitude =
-                amp[m.k2] * (0.5 * sd - ((1.5 * (double)kd) * dot) / (double)m.k2);
-            out = make_double2(amplitude * -z.y, amplitude * z.x);
-        }
-        dst[(i64)m.a * dst_si + (i64)m.bl * cp + m.kk] = out;
-    }
+    write_each_mode(dst, N, j0, nj, [=](KspaceMode m) {
+#pragma clang fp contract(off)
+        if (!m.live) return zero2();
+        const double2 z = *src.at(m);
+        const double s0 = s_sin[m.a], s1 = s_sin[j0 + m.bl], s2 = s_sin[m.kk];
+        const i64 kd = wave_number(m, dim);
+        const double sd = dim == 0 ? s0 : (dim == 1 ? s1 : s2);
+        const double dot = (s0 * (double)m.ki + s1 * (double)m.kj) + s2 * (double)m.kk;
+        const double amplitude =
+            amp[m.k2] * (0.5 * sd - ((1.5 * (double)kd) * dot) / (double)m.k2);
+        return make_double2(amplitude * -z.y, amplitude * z.x);
+    });
 }
 
 // out[layer][j][k] (dense) from the real cells of the mesh's owned layers.
@@ -262,18 +308,12 @@ template <int kVar>
 __global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh, double *out,
                                                               int N, i64 nrows, i64 ny, i64 pad,
                                                               double c0, double c1) {
+    for_each_cell_pair(N, nrows, ny, pad, [=](i64 off, i64 dense) {
 #pragma clang fp contract(off)
-    const int half = N / 2;  // pairs of cells per row (N is even)
-    const i64 total = nrows * half;
-    for (i64 t = (i64)blockIdx.x * kThreads + threadIdx.x; t < total;
-         t += (i64)gridDim.x * kThreads) {
-        const i64 row = t / half;
-        const int p = (int)(t - row * half);
-        const i64 layer = row / N;
-        double2 v = *(const double2 *)(mesh + (layer * ny + (row - layer * N)) * pad + 2 * p);
+        double2 v = *(const double2 *)(mesh + off);
         if (kVar == 1)  // ic.py:436
             v = make_double2(v.x + c1 * (v.x * v.x), v.y + c1 * (v.y * v.y));
-        double2 *o = (double2 *)(out + row * N + 2 * p);
+        double2 *o = (double2 *)(out + dense);
         if (kVar == 3) {  // fluid.py:1028, 1042
             const double2 w = *o;
             v = make_double2(w.x + c0 * v.x, w.y + c0 * v.y);
@@ -283,7 +323,7 @@ __global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh
             v = make_double2(c0 * (1 + v.x), c0 * (1 + v.y));  // ic.py:437
         }
         *o = v;
-    }
+    });
 }
 
 // ---- 3LPT and Orszag dealiasing: the passes between the realisation size N and the dealiasing
@@ -291,95 +331,56 @@ __global__ __launch_bounds__(kThreads) void k_fluid_from_mesh(const double *mesh
 // theta = (pi/N_onto - pi/N_from)*((ki + kj) + kk), applied on the way up and on the way down.
 
 // `small` is the cube of |k| < n/2 of a grid of size n inside a larger one
-__device__ __forceinline__ bool in_cube(const KspaceMode &m, int n) {
+__device__ __forceinline__ bool in_cube(KspaceMode m, int n) {
     const int h = n / 2;
     return m.ki > -h && m.ki < h && m.kj > -h && m.kj < h && m.kk < h;
 }
-// array index of signed wave number k in a grid of size n
-__device__ __forceinline__ i64 wrap_index(i64 k, int n) { return k + (k < 0 ? n : 0); }
+__device__ __forceinline__ double resize_phase(KspaceMode m, double dtheta) {
+#pragma clang fp contract(off)
+    return dtheta * (double)((m.ki + m.kj) + m.kk);  // mesh.py:1302
+}
 
 // fourier_diff at N (k_lpt_diff's rounding) + resize_grid to M (mesh.py:916-922) in one pass over
 // dst: inside the cube the rotated derivative, everywhere else (src's Nyquist planes and all of
 // dst's included) zero without a read.  Every mode of dst is written exactly once.
-__global__ __launch_bounds__(kThreads) void k_lpt_diff_enlarge(double2 *dst, const double2 *src,
-                                                               int M, int N, i64 dst_si, i64 dst_cp,
-                                                               i64 src_si, i64 src_cp, int dim0,
-                                                               int dim1, double scale,
-                                                               double dtheta) {
-#pragma clang fp contract(off)
-    const i64 total = (i64)M * M * (M / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, M, 0, M);
-        double2 out = make_double2(0.0, 0.0);
-        if (m.k2 != 0 && in_cube(m, N)) {
-            const double2 z =
-                src[wrap_index(m.ki, N) * src_si + wrap_index(m.kj, N) * src_cp + m.kk];
-            const i64 kl0 = dim0 == 0 ? m.ki : (dim0 == 1 ? m.kj : m.kk);
-            double re, im;
-            if (dim1 < 0) {
-                const double amplitude = scale * (double)kl0;  // mesh.py:3496
-                re = amplitude * -z.y;
-                im = amplitude * z.x;
-            } else {
-                const i64 kl1 = dim1 == 0 ? m.ki : (dim1 == 1 ? m.kj : m.kk);
-                const double amplitude = scale * (double)kl0 * (double)kl1;  // mesh.py:3506
-                re = amplitude * -z.x;
-                im = amplitude * -z.y;
-            }
-            const double theta = dtheta * (double)((m.ki + m.kj) + m.kk);  // mesh.py:1302
-            const double c = cos(theta), s = sin(theta);
-            out = make_double2(re * c - im * s, re * s + im * c);  // mesh.py:1310-1313
-        }
-        dst[(i64)m.a * dst_si + (i64)m.bl * dst_cp + m.kk] = out;
-    }
+__global__ __launch_bounds__(kThreads) void k_lpt_diff_enlarge(Slab dst, ConstSlab src, int M,
+                                                               int N, int dim0, int dim1,
+                                                               double scale, double dtheta) {
+    write_each_mode(dst, M, 0, M, [=](KspaceMode m) {
+        if (m.k2 == 0 || !in_cube(m, N)) return zero2();
+        const double2 z = *src.at_wave(m.ki, m.kj, m.kk, N);
+        return rotate(derivative(m, z, dim0, dim1, scale), resize_phase(m, dtheta));
+    });
 }
 
 // nullify_modes(slab, 'beyond cube of |k| < n/2') (ic.py:2025): zeros outside the cube, nothing
 // read, nothing written inside
-__global__ __launch_bounds__(kThreads) void k_lpt_dealias_cube(double2 *mesh, int M, int n, i64 si,
-                                                               i64 cp) {
-    const i64 total = (i64)M * M * (M / 2 + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, M, 0, M);
-        if (!in_cube(m, n)) mesh[(i64)m.a * si + (i64)m.bl * cp + m.kk] = make_double2(0.0, 0.0);
-    }
+__global__ __launch_bounds__(kThreads) void k_lpt_dealias_cube(Slab mesh, int M, int n) {
+    for_each_mode(M, 0, M, [=](KspaceMode m) {
+        if (!in_cube(m, n)) *mesh.at(m) = zero2();
+    });
 }
 
 // resize_grid down to N (nullify 'nyquist', copy_modes; mesh.py:912-922) + the move to the output
 // grid (ic.py:2038-2057) in one pass over out: rotation, factor and sum rounded in turn.  On
 // out's Nyquist planes the shrunk grid is zero: '=' writes it, '+=' and '-=' leave out as it is.
 template <int kOp>
-__global__ __launch_bounds__(kThreads) void k_lpt_shrink_accumulate(double2 *out,
-                                                                    const double2 *src, int N,
-                                                                    int M, i64 out_si, i64 out_cp,
-                                                                    i64 src_si, i64 src_cp,
-                                                                    double factor, double dtheta) {
-#pragma clang fp contract(off)
+__global__ __launch_bounds__(kThreads) void k_lpt_shrink_accumulate(Slab out, ConstSlab src, int N,
+                                                                    int M, double factor,
+                                                                    double dtheta) {
     const int nyq = N / 2;
-    const i64 total = (i64)N * N * (nyq + 1);
-    for (i64 e = (i64)blockIdx.x * kThreads + threadIdx.x; e < total;
-         e += (i64)gridDim.x * kThreads) {
-        const KspaceMode m = kspace_mode(e, N, 0, N);
-        double2 *o = out + (i64)m.a * out_si + (i64)m.bl * out_cp + m.kk;
+    for_each_mode(N, 0, N, [=](KspaceMode m) {
+        double2 *o = out.at(m);
         if (m.a == nyq || m.bl == nyq || m.kk == nyq) {
-            if (kOp == 0) *o = make_double2(0.0, 0.0);
-            continue;
+            if (kOp == 0) *o = zero2();
+            return;
         }
-        const double2 z = src[wrap_index(m.ki, M) * src_si + wrap_index(m.kj, M) * src_cp + m.kk];
-        const double theta = dtheta * (double)((m.ki + m.kj) + m.kk);  // mesh.py:1302
-        const double c = cos(theta), s = sin(theta);
-        double2 v = make_double2(z.x * c - z.y * s, z.x * s + z.y * c);
-        if (factor != 1) v = make_double2(factor * v.x, factor * v.y);  // ic.py:2042-2057
-        if (kOp == 0) {
-            *o = v;
-        } else {
-            const double2 w = *o;
-            *o = kOp == 1 ? make_double2(w.x + v.x, w.y + v.y) : make_double2(w.x - v.x, w.y - v.y);
-        }
-    }
+        const double2 z = *src.at_wave(m.ki, m.kj, m.kk, M);
+        accumulate<kOp>(o, rotate(z, resize_phase(m, dtheta)), factor);
+    });
 }
+
+// ---- what the entry points refuse, under the entry's name
 
 int fourier_pair_checks(const char *name, cg_ctx *dst, cg_ctx *src) {
     CG_CHECK(dst && src, "%s: null context", name);
@@ -393,35 +394,76 @@ int fourier_pair_checks(const char *name, cg_ctx *dst, cg_ctx *src) {
     return 0;
 }
 
-// two meshes of a realisation in Fourier space and its k²-indexed table of amplitudes
-int realize_checks(const char *name, cg_ctx *out, cg_ctx *src, const double *amplitudes,
-                   int64_t k2_max) {
-    if (fourier_pair_checks(name, out, src)) return 1;
-    const i64 nyq = out->N / 2;
-    CG_CHECK(amplitudes != nullptr, "%s: no amplitudes", name);
+// a k²-indexed table of k2_max + 1 amplitudes for the grid of c
+int amplitude_count_check(const char *name, const cg_ctx *c, int64_t k2_max) {
+    const i64 nyq = c->N / 2;
     CG_CHECK(k2_max == 3 * (nyq - 1) * (nyq - 1),
              "%s: %lld amplitudes for grid size %lld, which needs 3*(nyquist - 1)**2 + 1 = %lld",
-             name, (long long)(k2_max + 1), (long long)out->N,
+             name, (long long)(k2_max + 1), (long long)c->N,
              (long long)(3 * (nyq - 1) * (nyq - 1) + 1));
     return 0;
 }
 
-// two single-domain contexts of different grid size in Fourier space: `large` of size M, `small`
-// of size N < M
-int resize_pair_checks(const char *name, cg_ctx *large, cg_ctx *small) {
+// two meshes of a realisation in Fourier space and its table of amplitudes
+int realize_checks(const char *name, cg_ctx *out, cg_ctx *src, const double *amplitudes,
+                   int64_t k2_max) {
+    if (fourier_pair_checks(name, out, src)) return 1;
+    CG_CHECK(amplitudes != nullptr, "%s: no amplitudes", name);
+    return amplitude_count_check(name, out, k2_max);
+}
+
+// a single-domain context `large` of size M in Fourier space and a smaller size N: that of the
+// context `small` of the same box, or a bare number, with `large` itself in the place of `small`:
+// the tests of `small` then repeat those of `large`, and there is no second box to compare
+int resize_checks(const char *name, cg_ctx *large, cg_ctx *small, i64 N) {
     CG_CHECK(large && small, "%s: null context", name);
     CG_CHECK(large->four != nullptr && small->four != nullptr,
              "%s: no Fourier buffer bound (cg_dist_bind_fourier)", name);
     CG_CHECK(large->p.nprocs == 1 && small->p.nprocs == 1, "%s: single-domain entry point", name);
-    CG_CHECK(small->N >= 2 && small->N % 2 == 0 && large->N % 2 == 0,
-             "%s: grid sizes %lld and %lld are not both even", name, (long long)small->N,
+    CG_CHECK(N >= 2 && N % 2 == 0 && large->N % 2 == 0,
+             "%s: grid sizes %lld and %lld are not both even", name, (long long)N,
              (long long)large->N);
-    CG_CHECK(large->N > small->N, "%s: grid size %lld is not larger than %lld", name,
-             (long long)large->N, (long long)small->N);
-    CG_CHECK(large->p.boxsize == small->p.boxsize, "%s: the two meshes span different boxes", name);
+    CG_CHECK(large->N > N, "%s: grid size %lld is not larger than %lld", name,
+             (long long)large->N, (long long)N);
+    CG_CHECK(small == large || large->p.boxsize == small->p.boxsize,
+             "%s: the two meshes span different boxes", name);
     CG_CHECK(large->N * large->N < ((i64)1 << 31), "%s: %lld rows", name,
              (long long)(large->N * large->N));
     return 0;
+}
+int resize_pair_checks(const char *name, cg_ctx *large, cg_ctx *small) {
+    return resize_checks(name, large, small, small ? small->N : 0);
+}
+// (pi/N_onto - pi/N_from) of the size-change phase
+double resize_dtheta(const cg_ctx *onto, const cg_ctx *from) {
+    return kPi / (double)onto->N - kPi / (double)from->N;  // mesh.py:1302
+}
+
+// the dimensions of a derivative, and ℝ[factor*k_fundamental] or ℝ[factor*k_fundamental**2] of
+// fourier_diff in the box of c
+int diff_scale(const char *name, const cg_ctx *c, int dim0, int dim1, double factor,
+               double *scale) {
+    CG_CHECK(dim0 >= 0 && dim0 < 3 && dim1 >= -1 && dim1 < 3,
+             "%s: dimensions (%d, %d) outside 0..2 (the second may be -1)", name, dim0, dim1);
+    const double k_fundamental = 2 * kPi / c->p.boxsize;
+    *scale = dim1 < 0 ? factor * k_fundamental : factor * (k_fundamental * k_fundamental);
+    return 0;
+}
+
+// both entries of k_fluid_from_mesh: kVar = var, none (-1) where the caller's `mode` names none
+int fluid_from_mesh(const char *name, cg_ctx *mesh, double *out, int var, int mode, double c0,
+                    double c1) {
+    CG_CHECK(mesh && out, "%s: null %s", name, mesh ? "output grid" : "context");
+    CG_CHECK(var >= 0, "%s: mode %d not in {0 ϱ, 1 J}", name, mode);
+    CG_CHECK(mesh->N >= 2 && mesh->N % 2 == 0, "%s: grid size %lld is not even", name,
+             (long long)mesh->N);
+    CG_CHECK((uintptr_t)out % 16 == 0, "%s: the output grid is not 16-byte aligned", name);
+    const i64 nrows = mesh->xmap.nxl * mesh->N;
+    return with_case<4>(var, [=](auto k) {
+        return launch(k_fluid_from_mesh<decltype(k)::value>, nrows * (mesh->N / 2), 0,
+                      mesh->stream, (const double *)mesh->mesh0, out, (int)mesh->N, nrows,
+                      mesh->ny, mesh->pad, c0, c1);
+    });
 }
 
 }  // namespace
@@ -429,11 +471,7 @@ int resize_pair_checks(const char *name, cg_ctx *large, cg_ctx *small) {
 extern "C" int cg_lpt_potential(cg_ctx *dst, cg_ctx *noise_src, const double *amplitudes,
                                 int64_t k2_max, const double *shift, double factor) {
     if (fourier_pair_checks("cg_lpt_potential", dst, noise_src)) return 1;
-    const i64 nyq = dst->N / 2;
-    CG_CHECK(!amplitudes || k2_max == 3 * (nyq - 1) * (nyq - 1),
-             "cg_lpt_potential: %lld amplitudes for grid size %lld, which needs "
-             "3*(nyquist - 1)**2 + 1 = %lld", (long long)(k2_max + 1), (long long)dst->N,
-             (long long)(3 * (nyq - 1) * (nyq - 1) + 1));
+    if (amplitudes && amplitude_count_check("cg_lpt_potential", dst, k2_max)) return 1;
     LptPotential P{};
     P.amp = amplitudes;
     P.shifted = shift && (shift[0] != 0 || shift[1] != 0 || shift[2] != 0);
@@ -445,30 +483,19 @@ extern "C" int cg_lpt_potential(cg_ctx *dst, cg_ctx *noise_src, const double *am
     }
     const double k_fundamental = 2 * kPi / dst->p.boxsize;
     P.lap = -factor / (k_fundamental * k_fundamental);
-    const i64 total = dst->N * (i64)dst->f_nj * (nyq + 1);
-    hipLaunchKernelGGL(k_lpt_potential, dim3(grid_for(total)), dim3(kThreads), 0, dst->stream,
-                       dst->four, (const double2 *)noise_src->four, (int)dst->N, dst->f_si,
-                       noise_src->f_si, dst->pad / 2, dst->f_j0, dst->f_nj, P);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return launch(k_lpt_potential, mode_count(dst->N, dst->f_nj), 0, dst->stream, slab(dst),
+                  const_slab(noise_src), (int)dst->N, dst->f_j0, dst->f_nj, P);
 }
 
 extern "C" int cg_lpt_diff(cg_ctx *dst, cg_ctx *src, int dim0, int dim1, double factor) {
+    double scale;
     if (fourier_pair_checks("cg_lpt_diff", dst, src)) return 1;
-    CG_CHECK(dim0 >= 0 && dim0 < 3 && dim1 >= -1 && dim1 < 3,
-             "cg_lpt_diff: dimensions (%d, %d) outside 0..2 (the second may be -1)", dim0, dim1);
+    if (diff_scale("cg_lpt_diff", dst, dim0, dim1, factor, &scale)) return 1;
     // the first derivative with factor 1 into another mesh is fourier_operate(diff_dim) to the bit
     if (dim1 < 0 && factor == 1 && dst != src)
         return cgk_fourier_operate(dst, src, 0, 1, nullptr, dim0, 0);
-    const double k_fundamental = 2 * kPi / dst->p.boxsize;
-    const double scale = dim1 < 0 ? factor * k_fundamental
-                                  : factor * (k_fundamental * k_fundamental);
-    const i64 total = dst->N * (i64)dst->f_nj * (dst->N / 2 + 1);
-    hipLaunchKernelGGL(k_lpt_diff, dim3(grid_for(total)), dim3(kThreads), 0, dst->stream,
-                       dst->four, (const double2 *)src->four, (int)dst->N, dst->f_si, src->f_si,
-                       dst->pad / 2, dst->f_j0, dst->f_nj, dim0, dim1, scale);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return launch(k_lpt_diff, mode_count(dst->N, dst->f_nj), 0, dst->stream, slab(dst),
+                  const_slab(src), (int)dst->N, dst->f_j0, dst->f_nj, dim0, dim1, scale);
 }
 
 extern "C" int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double factor) {
@@ -479,72 +506,37 @@ extern "C" int cg_lpt_product(cg_ctx *out, cg_ctx *a, cg_ctx *b, int op, double 
     CG_CHECK(same_geometry(out, a) && same_geometry(out, b),
              "cg_lpt_product: the meshes differ in grid size or domain");
     const i64 nrows = out->xmap.nxl * out->N;
-    const i64 total = nrows * (out->N / 2);
-#define CG_LPT_PRODUCT(OP)                                                                      \
-    hipLaunchKernelGGL(k_lpt_product<OP>, dim3(grid_for(total)), dim3(kThreads), 0, out->stream, \
-                       out->mesh0, (const double *)a->mesh0, (const double *)b->mesh0,          \
-                       (int)out->N, nrows, out->ny, out->pad, factor)
-    if (op == 0) CG_LPT_PRODUCT(0);
-    else if (op == 1) CG_LPT_PRODUCT(1);
-    else CG_LPT_PRODUCT(2);
-#undef CG_LPT_PRODUCT
-    CG_LAUNCH_CHECK();
-    return 0;
+    return with_case<3>(op, [=](auto k) {
+        return launch(k_lpt_product<decltype(k)::value>, nrows * (out->N / 2), 0, out->stream,
+                      out->mesh0, (const double *)a->mesh0, (const double *)b->mesh0, (int)out->N,
+                      nrows, out->ny, out->pad, factor);
+    });
 }
 
 extern "C" int cg_lpt_diff_enlarge(cg_ctx *dst, cg_ctx *src, int dim0, int dim1, double factor) {
+    double scale;
     if (resize_pair_checks("cg_lpt_diff_enlarge", dst, src)) return 1;
-    CG_CHECK(dim0 >= 0 && dim0 < 3 && dim1 >= -1 && dim1 < 3,
-             "cg_lpt_diff_enlarge: dimensions (%d, %d) outside 0..2 (the second may be -1)", dim0,
-             dim1);
-    const double k_fundamental = 2 * kPi / src->p.boxsize;
-    const double scale = dim1 < 0 ? factor * k_fundamental
-                                  : factor * (k_fundamental * k_fundamental);
-    const double dtheta = kPi / (double)dst->N - kPi / (double)src->N;  // mesh.py:1302
-    const i64 total = dst->N * dst->N * (dst->N / 2 + 1);
-    hipLaunchKernelGGL(k_lpt_diff_enlarge, dim3(grid_for(total)), dim3(kThreads), 0, dst->stream,
-                       dst->four, (const double2 *)src->four, (int)dst->N, (int)src->N, dst->f_si,
-                       dst->pad / 2, src->f_si, src->pad / 2, dim0, dim1, scale, dtheta);
-    CG_LAUNCH_CHECK();
-    return 0;
+    if (diff_scale("cg_lpt_diff_enlarge", src, dim0, dim1, factor, &scale)) return 1;
+    return launch(k_lpt_diff_enlarge, mode_count(dst->N, dst->N), 0, dst->stream, slab(dst),
+                  const_slab(src), (int)dst->N, (int)src->N, dim0, dim1, scale,
+                  resize_dtheta(dst, src));
 }
 
 extern "C" int cg_lpt_dealias_cube(cg_ctx *mesh, int64_t n_small) {
-    CG_CHECK(mesh, "cg_lpt_dealias_cube: null context");
-    CG_CHECK(mesh->four != nullptr,
-             "cg_lpt_dealias_cube: no Fourier buffer bound (cg_dist_bind_fourier)");
-    CG_CHECK(mesh->p.nprocs == 1, "cg_lpt_dealias_cube: single-domain entry point");
-    CG_CHECK(n_small >= 2 && n_small % 2 == 0 && mesh->N % 2 == 0,
-             "cg_lpt_dealias_cube: grid sizes %lld and %lld are not both even", (long long)n_small,
-             (long long)mesh->N);
-    CG_CHECK(n_small < mesh->N, "cg_lpt_dealias_cube: grid size %lld is not larger than %lld",
-             (long long)mesh->N, (long long)n_small);
-    CG_CHECK(mesh->N * mesh->N < ((i64)1 << 31), "cg_lpt_dealias_cube: %lld rows",
-             (long long)(mesh->N * mesh->N));
-    const i64 total = mesh->N * mesh->N * (mesh->N / 2 + 1);
-    hipLaunchKernelGGL(k_lpt_dealias_cube, dim3(grid_for(total)), dim3(kThreads), 0, mesh->stream,
-                       mesh->four, (int)mesh->N, (int)n_small, mesh->f_si, mesh->pad / 2);
-    CG_LAUNCH_CHECK();
-    return 0;
+    if (resize_checks("cg_lpt_dealias_cube", mesh, mesh, n_small)) return 1;
+    return launch(k_lpt_dealias_cube, mode_count(mesh->N, mesh->N), 0, mesh->stream, slab(mesh),
+                  (int)mesh->N, (int)n_small);
 }
 
 extern "C" int cg_lpt_shrink_accumulate(cg_ctx *out, cg_ctx *src, int op, double factor) {
     if (resize_pair_checks("cg_lpt_shrink_accumulate", src, out)) return 1;
     CG_CHECK(op >= 0 && op <= 2,
              "cg_lpt_shrink_accumulate: operation %d not in {0 '=', 1 '+=', 2 '-='}", op);
-    const double dtheta = kPi / (double)out->N - kPi / (double)src->N;  // mesh.py:1302
-    const i64 total = out->N * out->N * (out->N / 2 + 1);
-#define CG_LPT_SHRINK(OP)                                                                        \
-    hipLaunchKernelGGL(k_lpt_shrink_accumulate<OP>, dim3(grid_for(total)), dim3(kThreads), 0,    \
-                       out->stream, out->four, (const double2 *)src->four, (int)out->N,          \
-                       (int)src->N, out->f_si, out->pad / 2, src->f_si, src->pad / 2, factor,    \
-                       dtheta)
-    if (op == 0) CG_LPT_SHRINK(0);
-    else if (op == 1) CG_LPT_SHRINK(1);
-    else CG_LPT_SHRINK(2);
-#undef CG_LPT_SHRINK
-    CG_LAUNCH_CHECK();
-    return 0;
+    return with_case<3>(op, [=](auto k) {
+        return launch(k_lpt_shrink_accumulate<decltype(k)::value>, mode_count(out->N, out->N), 0,
+                      out->stream, slab(out), const_slab(src), (int)out->N, (int)src->N, factor,
+                      resize_dtheta(out, src));
+    });
 }
 
 extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
@@ -561,34 +553,24 @@ extern "C" int cg_lpt_displace(cg_ctx *psi, double *pos, double *mom, int64_t n,
     CG_CHECK((pos || pos_factor == 0) && (mom || mom_factor == 0),
              "cg_lpt_displace: null particle array with a non-zero factor");
     if (pos_factor == 0 && mom_factor == 0) return 0;
-    hipLaunchKernelGGL(k_lpt_displace, dim3(grid_for(n / 2)), dim3(kThreads), 0, psi->stream,
-                       (const double *)psi->mesh0, (int)psi->N, psi->ny, psi->pad,
-                       pos ? pos + 3 * index_bgn : nullptr, mom ? mom + 3 * index_bgn : nullptr,
-                       dim, pos_factor, mom_factor);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return launch(k_lpt_displace, n / 2, 0, psi->stream, (const double *)psi->mesh0, (int)psi->N,
+                  psi->ny, psi->pad, pos ? pos + 3 * index_bgn : nullptr,
+                  mom ? mom + 3 * index_bgn : nullptr, dim, pos_factor, mom_factor);
 }
 
 extern "C" int cg_realize_grid(cg_ctx *out, cg_ctx *noise, const double *amplitudes, int64_t k2_max,
                                int tensor_rank, int index0) {
     if (realize_checks("cg_realize_grid", out, noise, amplitudes, k2_max)) return 1;
-    const i64 nyq = out->N / 2;
     CG_CHECK(tensor_rank == 0 || tensor_rank == 1,
              "cg_realize_grid: tensor rank %d (0 and 1 are implemented)", tensor_rank);
     CG_CHECK(tensor_rank == 0 || (index0 >= 0 && index0 < 3),
              "cg_realize_grid: index %d not in {0, 1, 2}", index0);
     const double vec = -out->p.boxsize / (2 * kPi);  // ℝ[-boxsize/(2*π)], ic.py:741
-    const i64 total = out->N * (i64)out->f_nj * (nyq + 1);
-#define CG_REALIZE_GRID(RANK)                                                                     \
-    hipLaunchKernelGGL(k_realize_grid<RANK>, dim3(grid_for(total)), dim3(kThreads), 0,           \
-                       out->stream, out->four, (const double2 *)noise->four, (int)out->N,        \
-                       out->f_si, noise->f_si, out->pad / 2, out->f_j0, out->f_nj, amplitudes,   \
-                       index0, vec)
-    if (tensor_rank == 0) CG_REALIZE_GRID(0);
-    else CG_REALIZE_GRID(1);
-#undef CG_REALIZE_GRID
-    CG_LAUNCH_CHECK();
-    return 0;
+    return with_case<2>(tensor_rank, [=](auto k) {
+        return launch(k_realize_grid<decltype(k)::value>, mode_count(out->N, out->f_nj), 0,
+                      out->stream, slab(out), const_slab(noise), (int)out->N, out->f_j0, out->f_nj,
+                      amplitudes, index0, vec);
+    });
 }
 
 extern "C" int cg_realize_grid_tensor(cg_ctx *out, cg_ctx *structure, const double *amplitudes,
@@ -596,13 +578,9 @@ extern "C" int cg_realize_grid_tensor(cg_ctx *out, cg_ctx *structure, const doub
     if (realize_checks("cg_realize_grid_tensor", out, structure, amplitudes, k2_max)) return 1;
     CG_CHECK(index0 >= 0 && index0 < 3 && index1 >= 0 && index1 < 3,
              "cg_realize_grid_tensor: indices (%d, %d) not in {0, 1, 2}", index0, index1);
-    const i64 total = out->N * (i64)out->f_nj * (out->N / 2 + 1);
-    hipLaunchKernelGGL(k_realize_grid_tensor, dim3(grid_for(total)), dim3(kThreads), 0,
-                       out->stream, out->four, (const double2 *)structure->four, (int)out->N,
-                       out->f_si, structure->f_si, out->pad / 2, out->f_j0, out->f_nj, amplitudes,
-                       index0, index1);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return launch(k_realize_grid_tensor, mode_count(out->N, out->f_nj), 0, out->stream, slab(out),
+                  const_slab(structure), (int)out->N, out->f_j0, out->f_nj, amplitudes, index0,
+                  index1);
 }
 
 extern "C" int cg_shear_divergence(cg_ctx *out, cg_ctx *structure, const double *amplitudes,
@@ -612,46 +590,16 @@ extern "C" int cg_shear_divergence(cg_ctx *out, cg_ctx *structure, const double 
     CG_CHECK(out->N <= 4096, "cg_shear_divergence: grid size %lld above 4096 (the table of sines "
              "is kept in LDS)", (long long)out->N);
     const double inv_dx = (double)out->N / out->p.boxsize;
-    const i64 total = out->N * (i64)out->f_nj * (out->N / 2 + 1);
-    hipLaunchKernelGGL(k_shear_divergence, dim3(grid_for(total)), dim3(kThreads),
-                       (size_t)out->N * sizeof(double), out->stream, out->four,
-                       (const double2 *)structure->four, (int)out->N, out->f_si, structure->f_si,
-                       out->pad / 2, out->f_j0, out->f_nj, amplitudes, dim, inv_dx);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return launch(k_shear_divergence, mode_count(out->N, out->f_nj),
+                  (size_t)out->N * sizeof(double), out->stream, slab(out), const_slab(structure),
+                  (int)out->N, out->f_j0, out->f_nj, amplitudes, dim, inv_dx);
 }
 
 extern "C" int cg_fluid_add_from_mesh(cg_ctx *mesh, double *out, double factor) {
-    CG_CHECK(mesh && out, "cg_fluid_add_from_mesh: null %s", mesh ? "output grid" : "context");
-    CG_CHECK(mesh->N >= 2 && mesh->N % 2 == 0,
-             "cg_fluid_add_from_mesh: grid size %lld is not even", (long long)mesh->N);
-    CG_CHECK((uintptr_t)out % 16 == 0,
-             "cg_fluid_add_from_mesh: the output grid is not 16-byte aligned");
-    const i64 nrows = mesh->xmap.nxl * mesh->N;
-    const i64 total = nrows * (mesh->N / 2);
-    hipLaunchKernelGGL(k_fluid_from_mesh<3>, dim3(grid_for(total)), dim3(kThreads), 0,
-                       mesh->stream, (const double *)mesh->mesh0, out, (int)mesh->N, nrows,
-                       mesh->ny, mesh->pad, factor, 0.0);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return fluid_from_mesh("cg_fluid_add_from_mesh", mesh, out, 3, 0, factor, 0.0);
 }
 
 extern "C" int cg_fluid_from_mesh(cg_ctx *mesh, double *out, int mode, double c0, double c1) {
-    CG_CHECK(mesh && out, "cg_fluid_from_mesh: null %s", mesh ? "output grid" : "context");
-    CG_CHECK(mode == 0 || mode == 1, "cg_fluid_from_mesh: mode %d not in {0 ϱ, 1 J}", mode);
-    CG_CHECK(mesh->N >= 2 && mesh->N % 2 == 0, "cg_fluid_from_mesh: grid size %lld is not even",
-             (long long)mesh->N);
-    CG_CHECK((uintptr_t)out % 16 == 0, "cg_fluid_from_mesh: the output grid is not 16-byte aligned");
-    const i64 nrows = mesh->xmap.nxl * mesh->N;
-    const i64 total = nrows * (mesh->N / 2);
-#define CG_FLUID_FROM_MESH(VAR)                                                                   \
-    hipLaunchKernelGGL(k_fluid_from_mesh<VAR>, dim3(grid_for(total)), dim3(kThreads), 0,         \
-                       mesh->stream, (const double *)mesh->mesh0, out, (int)mesh->N, nrows,      \
-                       mesh->ny, mesh->pad, c0, c1)
-    if (mode == 1) CG_FLUID_FROM_MESH(2);
-    else if (c1 != 0) CG_FLUID_FROM_MESH(1);
-    else CG_FLUID_FROM_MESH(0);
-#undef CG_FLUID_FROM_MESH
-    CG_LAUNCH_CHECK();
-    return 0;
+    const int var = mode == 1 ? 2 : (mode == 0 ? (c1 != 0 ? 1 : 0) : -1);
+    return fluid_from_mesh("cg_fluid_from_mesh", mesh, out, var, mode, c0, c1);
 }

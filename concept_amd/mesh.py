@@ -550,11 +550,7 @@ class PotentialMesh:
         3*(nyquist - 1)**2 + 1 entries on the device, or None for laplacian_inverse alone."""
         k2_max = 0
         if amplitudes is not None:
-            if (amplitudes.dtype != torch.float64 or amplitudes.device != self.device
-                    or not amplitudes.is_contiguous() or amplitudes.dim() != 1):
-                raise lib.ConceptGPUError(
-                    f'lpt_potential(): amplitudes must be a contiguous 1D float64 tensor on '
-                    f'{self.device}')
+            self._check_amplitudes('lpt_potential', amplitudes)
             k2_max = amplitudes.numel() - 1
         sh = (ctypes.c_double*3)(*[float(x) for x in shift])
         check(_L.cg_lpt_potential(self._ctx, noise._ctx, _ptr(amplitudes), k2_max, sh,
@@ -566,9 +562,13 @@ class PotentialMesh:
         check(_L.cg_lpt_diff(self._ctx, source._ctx, int(dim0), int(dim1), float(factor)))
         return self
 
+    @staticmethod
+    def _lpt_operation(operation):
+        return ('=', '+=', '-=').index(operation)
+
     def lpt_product(self, a, b, operation='=', factor=1.0):
         """this mesh (= | += | -=) factor*a*b in real space (handle_lpt_term, ic.py:2020-2057)"""
-        check(_L.cg_lpt_product(self._ctx, a._ctx, b._ctx, ('=', '+=', '-=').index(operation),
+        check(_L.cg_lpt_product(self._ctx, a._ctx, b._ctx, self._lpt_operation(operation),
                                 float(factor)))
         return self
 
@@ -587,7 +587,7 @@ class PotentialMesh:
         """this mesh (= | += | -=) factor*(the larger `source` shrunk to this size), in Fourier
         space (resize_grid and the move to the output grid, ic.py:2029-2057)"""
         check(_L.cg_lpt_shrink_accumulate(self._ctx, source._ctx,
-                                          ('=', '+=', '-=').index(operation), float(factor)))
+                                          self._lpt_operation(operation), float(factor)))
         return self
 
     def lpt_displace(self, pos, mom, dim, pos_factor, mom_factor, index_bgn=0):
