@@ -20,6 +20,13 @@
 // (one domain, nxl = g); else lo holds the H layers below the first own one and hi the H layers
 // above the last, each double[H][g][g] in ascending x (the caller exchanged them).
 //
+// The three stencil kernels (k_mc_step, k_pressure_sources, k_kt_step) share StepTile, a
+// workgroup's tile of cells and its walk along x (k_kt_step spells its values out, see there), and
+// stage(), the copy of a layer's tile and halo into LDS; they differ in the halo and in what stays
+// resident.  On the host: tile_grid and
+// launch_stride (the two launch shapes), take4 (a pack of grids from the caller's pointers),
+// take_layers, check_shape and check_aliasing (no pass reads what it writes).
+//
 // FP64, compiled with -ffp-contract=off: every sum, product and quotient is evaluated as the
 // reference writes it.  No floating-point atomics: the results do not depend on the launch.
 #include "cg_internal.h"
@@ -61,6 +68,44 @@ __device__ inline const double *layer_of(const Layers &a, int l, int nxl, i64 g2
 
 __device__ inline int wrap(int a, int g) { return a < 0 ? a + g : (a >= g ? a - g : a); }
 
+// layer l of each of the n grids
+template <int H, int n>
+__device__ inline void layers_of(const LayersN<n> &a, int l, int nxl, i64 g2,
+                                 const double *(&layer)[n]) {
+#pragma unroll
+    for (int v = 0; v < n; v++) layer[v] = layer_of<H>(a.v[v], l, nxl, g2);
+}
+
+// What a workgroup of a step kernel (k_mc_step, k_pressure_sources, k_kt_step) works on: a tile of
+// kTY x kTZ cells with its first cell at (y0, z0), a thread per cell, walked over the layers
+// [xa, xb) of a chunk of xc layers along x.
+struct StepTile {
+    int y0, z0;   // the tile's first cell
+    int ty, tz;   // the thread's cell within the tile
+    int xa, xb;   // the layers of the walk
+    bool mine;    // the thread's cell lies within the grid (a partial tile has threads that only stage)
+    i64 col;      // the thread's cell within a layer, (y0 + ty) g + (z0 + tz); 0 when not mine
+    __device__ StepTile(int g, int nxl, int xc)
+        : y0(blockIdx.y * kTY), z0(blockIdx.x * kTZ), ty(threadIdx.x / kTZ), tz(threadIdx.x % kTZ),
+          xa(blockIdx.z * xc), xb(xa + xc < nxl ? xa + xc : nxl), mine(y0 + ty < g && z0 + tz < g),
+          col(mine ? (i64)(y0 + ty) * g + (z0 + tz) : 0) {}
+};
+
+// Stage EY x EZ cells of one layer of NV grids in LDS, by the whole workgroup: local (ly, lz) is
+// cell (y + ly, z + lz) of the layer, wrapped, so a tile with a halo of h cells passes its first
+// cell less h.  (A partial tile's rows beyond the grid wrap as well: loaded, never used.)  The
+// caller synchronises.
+template <int NV, int EY, int EZ>
+__device__ inline void stage(const double *(&layer)[NV], int y, int z, int g,
+                             double (&tile)[NV][EY][EZ]) {
+    for (int e = threadIdx.x; e < EY * EZ; e += kThreads) {
+        const int ly = e / EZ, lz = e - ly * EZ;
+        const i64 at = (i64)((y + ly + g) % g) * g + (z + lz + g) % g;
+#pragma unroll
+        for (int v = 0; v < NV; v++) tile[v][ly][lz] = layer[v][at];
+    }
+}
+
 // One MacCormack step.  src: ϱ, Jx, Jy, Jz as the stencil reads them (the unstarred grids in
 // step 0, the starred in step 1) and 𝒫 (always the unstarred grid); dst: the four grids the step
 // writes (the starred in step 0, the unstarred in step 1).  The prologue of fluid.py:862-870
@@ -74,33 +119,24 @@ __global__ __launch_bounds__(kThreads) void k_mc_step(LayersN<5> src, Out4 dst, 
                                                       double inv_c2, int mc_step, int halve) {
 #pragma clang fp contract(off)
     __shared__ double tile[2][5][kTY + 1][kTZ + 1];
-    const int tz = threadIdx.x % kTZ, ty = threadIdx.x / kTZ;
-    const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
-    const int xa = blockIdx.z * kXC, xb = xa + kXC < nxl ? xa + kXC : nxl;
+    const StepTile t(g, nxl, kXC);
     const i64 g2 = (i64)g * g;
-    // the halo row sits on the side the step points to: local (ly, lz) is cell
-    // (y0 - oy + ly, z0 - oz + lz) of the layer, wrapped
+    // the halo row sits on the side the step points to
     const int oy = sy < 0, oz = sz < 0;
     auto load = [&](int buf, int l) {
-        for (int e = threadIdx.x; e < (kTY + 1) * (kTZ + 1); e += kThreads) {
-            const int ly = e / (kTZ + 1), lz = e - ly * (kTZ + 1);
-            // (a partial tile's rows beyond the grid wrap as well: loaded, never used)
-            const int y = (y0 - oy + ly + g) % g, z = (z0 - oz + lz + g) % g;
-            const i64 at = (i64)y * g + z;
-#pragma unroll
-            for (int v = 0; v < 5; v++) tile[buf][v][ly][lz] = layer_of<1>(src.v[v], l, nxl, g2)[at];
-        }
+        const double *layer[5];
+        layers_of<1>(src, l, nxl, g2, layer);
+        stage(layer, t.y0 - oy, t.z0 - oz, g, tile[buf]);
     };
-    const int count = xb - xa, first = sx > 0 ? xa : xb - 1;
-    const bool mine = y0 + ty < g && z0 + tz < g;
-    const int cy = ty + oy, cz = tz + oz;
+    const int count = t.xb - t.xa, first = sx > 0 ? t.xa : t.xb - 1;
+    const int cy = t.ty + oy, cz = t.tz + oz;
     load(0, first);
     for (int n = 0; n < count; n++) {
         const int l = first + n * sx, b = n & 1;
         load(b ^ 1, l + sx);
         __syncthreads();
-        if (mine) {
-            const i64 at = ((i64)l * g + (y0 + ty)) * g + (z0 + tz);
+        if (t.mine) {
+            const i64 at = (i64)l * g2 + t.col;
             // the cell itself and its +s_x, +s_y, +s_z neighbours: J and ϱ + c⁻²𝒫
             double J0[3], JN[3][3], den0, denN[3];
 #pragma unroll
@@ -252,36 +288,27 @@ __global__ __launch_bounds__(kThreads) void k_pressure_sources(Layers rho, doubl
                                                                double minus_dt,
                                                                double half_inv_dx) {
 #pragma clang fp contract(off)
-    __shared__ double tile[3][kTY + 2][kTZ + 2];
-    const int tz = threadIdx.x % kTZ, ty = threadIdx.x / kTZ;
-    const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
-    const int xa = blockIdx.z * kXC, xb = xa + kXC < nxl ? xa + kXC : nxl;
+    __shared__ double tile[3][1][kTY + 2][kTZ + 2];   // [buffer][the one grid staged: ϱ]
+    const StepTile t(g, nxl, kXC);
     const i64 g2 = (i64)g * g;
-    // local (ly, lz) is cell (y0 - 1 + ly, z0 - 1 + lz) of the layer, wrapped
     auto load = [&](int buf, int l) {
-        const double *layer = layer_of<1>(rho, l, nxl, g2);
-        for (int e = threadIdx.x; e < (kTY + 2) * (kTZ + 2); e += kThreads) {
-            const int ly = e / (kTZ + 2), lz = e - ly * (kTZ + 2);
-            // (a partial tile's rows beyond the grid wrap as well: loaded, never used)
-            const int y = (y0 - 1 + ly + g) % g, z = (z0 - 1 + lz + g) % g;
-            tile[buf][ly][lz] = layer[(i64)y * g + z];
-        }
+        const double *layer[1] = {layer_of<1>(rho, l, nxl, g2)};
+        stage(layer, t.y0 - 1, t.z0 - 1, g, tile[buf]);
     };
-    const bool mine = y0 + ty < g && z0 + tz < g;
-    const int cy = ty + 1, cz = tz + 1;
-    load(0, xa - 1);
-    load(1, xa);
-    for (int l = xa, n = 0; l < xb; l++, n++) {
+    const int cy = t.ty + 1, cz = t.tz + 1;
+    load(0, t.xa - 1);
+    load(1, t.xa);
+    for (int l = t.xa, n = 0; l < t.xb; l++, n++) {
         const int below = n % 3, own = (n + 1) % 3, above = (n + 2) % 3;
         load(above, l + 1);
         __syncthreads();
-        if (mine) {
-            const i64 at = ((i64)l * g + (y0 + ty)) * g + (z0 + tz);
-            P[at] = tile[own][cy][cz] * c2w;
-            const double up[3] = {tile[above][cy][cz] * c2w, tile[own][cy + 1][cz] * c2w,
-                                  tile[own][cy][cz + 1] * c2w};
-            const double down[3] = {tile[below][cy][cz] * c2w, tile[own][cy - 1][cz] * c2w,
-                                    tile[own][cy][cz - 1] * c2w};
+        if (t.mine) {
+            const i64 at = (i64)l * g2 + t.col;
+            P[at] = tile[own][0][cy][cz] * c2w;
+            const double up[3] = {tile[above][0][cy][cz] * c2w, tile[own][0][cy + 1][cz] * c2w,
+                                  tile[own][0][cy][cz + 1] * c2w};
+            const double down[3] = {tile[below][0][cy][cz] * c2w, tile[own][0][cy - 1][cz] * c2w,
+                                    tile[own][0][cy][cz - 1] * c2w};
 #pragma unroll
             for (int d = 0; d < 3; d++)
                 J.p[d][at] = J.p[d][at] + minus_dt * (half_inv_dx * (up[d] - down[d]));
@@ -433,6 +460,34 @@ __device__ inline void kt_flux(const double (&q)[4][4], const KtFactors &k, doub
     }
 }
 
+// What the cell at (cy, cz) of a staged layer receives through its two faces across direction D
+// (1: y, 2: z), the lower face first: out += Δ(-½), then out -= Δ(+½), with Δ = flux*to_delta.
+// The two faces share three of their four cells: the five cells of the line are read once (read
+// per face, the compiler keeps the second face's loads apart and spills more registers).
+template <int LIM, int D, int EY, int EZ>
+__device__ inline void kt_add_faces(const double (&tile)[4][EY][EZ], int cy, int cz,
+                                    const KtFactors &k, double (&out)[4]) {
+#pragma clang fp contract(off)
+    static_assert(D == 1 || D == 2, "the faces along x are the walk's own");
+    double line[4][5], flux[4], q[4][4];
+#pragma unroll
+    for (int var = 0; var < 4; var++)
+#pragma unroll
+        for (int o = 0; o < 5; o++)
+            line[var][o] = D == 1 ? tile[var][cy - 2 + o][cz] : tile[var][cy][cz - 2 + o];
+#pragma unroll
+    for (int side = 0; side < 2; side++) {
+#pragma unroll
+        for (int var = 0; var < 4; var++)
+#pragma unroll
+            for (int o = 0; o < 4; o++) q[var][o] = line[var][side + o];
+        kt_flux<LIM, D>(q, k, flux);
+#pragma unroll
+        for (int var = 0; var < 4; var++)
+            out[var] = side ? out[var] - flux[var] * k.to_delta : out[var] + flux[var] * k.to_delta;
+    }
+}
+
 // One Runge-Kutta step of kurganov_tadmor (fluid.py:103-464) with its finalize_rk_step
 // (:565-586), as a gather.  The reference scatters Δ = flux*to_delta of every interface to the two
 // cells beside it, in loops over the variable, the direction and the interfaces in ascending
@@ -452,6 +507,9 @@ __global__ __launch_bounds__(kThreads) void k_kt_step(LayersN<4> src, Out4 dst,
                                                       int rk_step, KtFactors k) {
 #pragma clang fp contract(off)
     __shared__ double tile[4][kTY + 2 * kKtH][kTZ + 2 * kKtH];
+    // (the StepTile of this kernel, spelt out: built through the struct, the same values reach the
+    // register allocator in another order, and this kernel, at the register limit, moves more
+    // values to and from the accumulation registers and runs 1 % slower)
     const int tz = threadIdx.x % kTZ, ty = threadIdx.x / kTZ;
     const int z0 = blockIdx.x * kTZ, y0 = blockIdx.y * kTY;
     const int xa = blockIdx.z * kKtXC, xb = xa + kKtXC < nxl ? xa + kKtXC : nxl;
@@ -470,20 +528,13 @@ __global__ __launch_bounds__(kThreads) void k_kt_step(LayersN<4> src, Out4 dst,
         kt_flux<LIM, 0>(w, k, lower);
     }
     for (int l = xa; l < xb; l++) {
-        // local (ly, lz) is cell (y0 - 2 + ly, z0 - 2 + lz) of the layer, wrapped
-        for (int e = threadIdx.x; e < (kTY + 2 * kKtH) * (kTZ + 2 * kKtH); e += kThreads) {
-            const int ly = e / (kTZ + 2 * kKtH), lz = e - ly * (kTZ + 2 * kKtH);
-            // (a partial tile's rows beyond the grid wrap as well: loaded, never used)
-            const int y = (y0 - kKtH + ly + g) % g, z = (z0 - kKtH + lz + g) % g;
-            const i64 at = (i64)y * g + z;
-#pragma unroll
-            for (int var = 0; var < 4; var++)
-                tile[var][ly][lz] = layer_of<kKtH>(src.v[var], l, nxl, g2)[at];
-        }
+        const double *layer[4];
+        layers_of<kKtH>(src, l, nxl, g2, layer);
+        stage(layer, y0 - kKtH, z0 - kKtH, g, tile);
         __syncthreads();
         if (mine) {
             const i64 at = (i64)l * g2 + col;
-            double out[4], flux[4], q[4][4];
+            double out[4];
 #pragma unroll
             for (int var = 0; var < 4; var++) {
                 out[var] = rk_step == 0 ? 0.0 : dst.p[var][at];
@@ -497,30 +548,8 @@ __global__ __launch_bounds__(kThreads) void k_kt_step(LayersN<4> src, Out4 dst,
             kt_flux<LIM, 0>(w, k, lower);
 #pragma unroll
             for (int var = 0; var < 4; var++) out[var] = out[var] - lower[var] * k.to_delta;
-#pragma unroll
-            for (int side = 0; side < 2; side++) {
-#pragma unroll
-                for (int var = 0; var < 4; var++)
-#pragma unroll
-                    for (int o = 0; o < 4; o++) q[var][o] = tile[var][cy - 2 + side + o][cz];
-                kt_flux<LIM, 1>(q, k, flux);
-#pragma unroll
-                for (int var = 0; var < 4; var++)
-                    out[var] = side ? out[var] - flux[var] * k.to_delta
-                                    : out[var] + flux[var] * k.to_delta;
-            }
-#pragma unroll
-            for (int side = 0; side < 2; side++) {
-#pragma unroll
-                for (int var = 0; var < 4; var++)
-#pragma unroll
-                    for (int o = 0; o < 4; o++) q[var][o] = tile[var][cy][cz - 2 + side + o];
-                kt_flux<LIM, 2>(q, k, flux);
-#pragma unroll
-                for (int var = 0; var < 4; var++)
-                    out[var] = side ? out[var] - flux[var] * k.to_delta
-                                    : out[var] + flux[var] * k.to_delta;
-            }
+            kt_add_faces<LIM, 1>(tile, cy, cz, k, out);
+            kt_add_faces<LIM, 2>(tile, cy, cz, k, out);
             if (P) P[at] = w[0][1] * k.c2w;
 #pragma unroll
             for (int var = 0; var < 4; var++)
@@ -534,6 +563,44 @@ unsigned grid_for(i64 n, i64 cap) {
     i64 blocks = (n + kThreads - 1) / kThreads;
     if (blocks > cap) blocks = cap;
     return (unsigned)(blocks < 1 ? 1 : blocks);
+}
+
+// an element-wise kernel over n elements: grid stride, at most `cap` workgroups
+template <class Kernel, class... Args>
+int launch_stride(cg_ctx *c, Kernel kernel, i64 n, i64 cap, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n, cap)), dim3(kThreads), 0, c->stream, args...);
+    CG_LAUNCH_CHECK();
+    return 0;
+}
+
+// a step kernel: a workgroup per StepTile with chunks of xc layers
+dim3 tile_grid(int64_t gridsize, int64_t nxl, int xc) {
+    return dim3((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
+                (unsigned)((nxl + xc - 1) / xc));
+}
+
+// the first `count` grids of a pack (Out4 or In4); `what` names a missing one ("null grid")
+template <class Pack, class Ptr>
+int take4(const char *who, const char *what, Ptr *const *ptrs, int count, Pack &out) {
+    using Grid = std::remove_reference_t<decltype(*out.p)>;
+    for (int v = 0; v < count; v++) {
+        CG_CHECK(ptrs[v], "%s: %s %d", who, what, v);
+        out.p[v] = (Grid)ptrs[v];
+    }
+    return 0;
+}
+
+// The stencil must not read what the pass writes, and no grid is written twice: refuses a written
+// grid that is one of those read, and two written grids that are one.  `what` names a written grid.
+int check_aliasing(const char *who, const char *what, const void *const *reads, int nreads,
+                   const void *const *writes, int nwrites) {
+    for (int v = 0; v < nwrites; v++) {
+        for (int u = 0; u < nreads; u++)
+            CG_CHECK(writes[v] != reads[u], "%s: %s %d is read and written", who, what, v);
+        for (int u = 0; u < v; u++)
+            CG_CHECK(writes[v] != writes[u], "%s: %ss %d and %d are one", who, what, u, v);
+    }
+    return 0;
 }
 
 // nvar grids with their layers beyond the own ones (both lists or neither)
@@ -570,38 +637,17 @@ extern "C" int cg_fluid_mc_step(cg_ctx *c, const void *const *src, const void *c
     if (take_layers("cg_fluid_mc_step", s.v, 5, src, src_lo, src_hi)) return 1;
     if (check_shape("cg_fluid_mc_step", gridsize, nxl, src_lo == nullptr, 1)) return 1;
     CG_CHECK(mc_step == 0 || mc_step == 1, "cg_fluid_mc_step: mc_step %d", mc_step);
+    for (int i = 0; i < 3; i++)
+        CG_CHECK(steps[i] == 1 || steps[i] == -1, "cg_fluid_mc_step: step %d", steps[i]);
     Out4 d;
-    for (int v = 0; v < 4; v++) {
-        CG_CHECK(dst[v], "cg_fluid_mc_step: null grid %d", v);
-        CG_CHECK(steps[v % 3] == 1 || steps[v % 3] == -1, "cg_fluid_mc_step: step %d", steps[v % 3]);
-        d.p[v] = (double *)dst[v];
-        // the stencil must not read what the pass writes
-        for (int u = 0; u < 5; u++)
-            CG_CHECK(dst[v] != src[u], "cg_fluid_mc_step: grid %d is read and written", v);
-    }
-    const dim3 grid((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
-                    (unsigned)((nxl + kXC - 1) / kXC));
-    hipLaunchKernelGGL(k_mc_step, grid, dim3(kThreads), 0, c->stream, s, d, (int)gridsize, (int)nxl,
-                       steps[0], steps[1], steps[2], factor, inv_c2, mc_step, halve);
+    if (take4("cg_fluid_mc_step", "null grid", dst, 4, d)) return 1;
+    if (check_aliasing("cg_fluid_mc_step", "grid", src, 5, dst, 4)) return 1;
+    hipLaunchKernelGGL(k_mc_step, tile_grid(gridsize, nxl, kXC), dim3(kThreads), 0, c->stream, s, d,
+                       (int)gridsize, (int)nxl, steps[0], steps[1], steps[2], factor, inv_c2,
+                       mc_step, halve);
     CG_LAUNCH_CHECK();
     return 0;
 }
-
-namespace {
-
-template <int LIM>
-void launch_kt_step(cg_ctx *c, dim3 grid, const LayersN<4> &s, const Out4 &d, double *P, int g,
-                    int nxl, int rk_step, int limiter, const KtFactors &k) {
-    if constexpr (LIM < kLimiters) {
-        if (limiter == LIM)
-            hipLaunchKernelGGL(k_kt_step<LIM>, grid, dim3(kThreads), 0, c->stream, s, d, P, g, nxl,
-                               rk_step, k);
-        else
-            launch_kt_step<LIM + 1>(c, grid, s, d, P, g, nxl, rk_step, limiter, k);
-    }
-}
-
-}  // namespace
 
 extern "C" int cg_fluid_kt_step(cg_ctx *c, const void *const *src, const void *const *src_lo,
                                 const void *const *src_hi, void *const *dst, double *P,
@@ -615,22 +661,20 @@ extern "C" int cg_fluid_kt_step(cg_ctx *c, const void *const *src, const void *c
     CG_CHECK(rk_step == 0 || rk_step == 1, "cg_fluid_kt_step: rk_step %d", rk_step);
     CG_CHECK(limiter >= 0 && limiter < kLimiters, "cg_fluid_kt_step: flux limiter %d", limiter);
     Out4 d;
-    for (int v = 0; v < 4; v++) {
-        CG_CHECK(dst[v] && dst[v] != (void *)P, "cg_fluid_kt_step: null grid %d", v);
-        d.p[v] = (double *)dst[v];
-        // the stencil must not read what the pass writes
-        for (int u = 0; u < 4; u++) {
-            CG_CHECK(dst[v] != src[u], "cg_fluid_kt_step: grid %d is read and written", v);
-            CG_CHECK(u == v || dst[v] != dst[u], "cg_fluid_kt_step: grids %d and %d are one", u, v);
-        }
-        CG_CHECK(src[v] != (const void *)P, "cg_fluid_kt_step: 𝒫 and grid %d are one", v);
-    }
-    const dim3 grid((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
-                    (unsigned)((nxl + kKtXC - 1) / kKtXC));
+    if (take4("cg_fluid_kt_step", "null grid", dst, 4, d)) return 1;
+    if (check_aliasing("cg_fluid_kt_step", "grid", src, 4, dst, 4)) return 1;
+    // (𝒫 is written as well, and may be left out)
+    for (int v = 0; v < 4; v++)
+        CG_CHECK(src[v] != (const void *)P && dst[v] != (void *)P,
+                 "cg_fluid_kt_step: 𝒫 and grid %d are one", v);
     const KtFactors k{c2w, inv_c2, a_pow, soundspeed, f_J, f_P, to_delta};
-    launch_kt_step<0>(c, grid, s, d, P, (int)gridsize, (int)nxl, rk_step, limiter, k);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return with_case<kLimiters>(limiter, [=](auto lim) {
+        hipLaunchKernelGGL(k_kt_step<decltype(lim)::value>, tile_grid(gridsize, nxl, kKtXC),
+                           dim3(kThreads), 0, c->stream, s, d, P, (int)gridsize, (int)nxl, rk_step,
+                           k);
+        CG_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 extern "C" int cg_fluid_mc_finish(cg_ctx *c, void *const *grids, void *const *starred,
@@ -638,13 +682,8 @@ extern "C" int cg_fluid_mc_finish(cg_ctx *c, void *const *grids, void *const *st
     CG_CHECK(c && grids && starred && n >= 1, "cg_fluid_mc_finish: null argument");
     if (halve) {
         Out4 gr;
-        for (int v = 0; v < 4; v++) {
-            CG_CHECK(grids[v], "cg_fluid_mc_finish: null grid %d", v);
-            gr.p[v] = (double *)grids[v];
-        }
-        hipLaunchKernelGGL(k_mc_halve, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, gr,
-                           (i64)n);
-        CG_LAUNCH_CHECK();
+        if (take4("cg_fluid_mc_finish", "null grid", grids, 4, gr)) return 1;
+        if (launch_stride(c, k_mc_halve, n, 4096, gr, (i64)n)) return 1;
     }
     for (int v = 0; v < 4; v++) {
         CG_CHECK(starred[v], "cg_fluid_mc_finish: null starred grid %d", v);
@@ -662,10 +701,8 @@ extern "C" int cg_fluid_vacuum_detect(cg_ctx *c, const double *a, const double *
     CG_CHECK((mode == 1 || a) && (mode == 2 || (b && fac_time)),
              "cg_fluid_vacuum_detect: null grid for mode %d", mode);
     CG_HIP(hipMemsetAsync(flag, 0, sizeof(int), c->stream));
-    hipLaunchKernelGGL(k_vacuum_detect, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, a, b,
-                       (i64)n, mode, k1, threshold, rho_vacuum, fac_time, flag);
-    CG_LAUNCH_CHECK();
-    return 0;
+    return launch_stride(c, k_vacuum_detect, n, 4096, a, b, (i64)n, mode, k1, threshold, rho_vacuum,
+                         fac_time, flag);
 }
 
 extern "C" int cg_fluid_vacuum_gather(cg_ctx *c, const void *const *var, const void *const *var_lo,
@@ -681,10 +718,9 @@ extern "C" int cg_fluid_vacuum_gather(cg_ctx *c, const void *const *var, const v
                  (fac_time_hi == nullptr) == (var_lo == nullptr),
              "cg_fluid_vacuum_gather: fac_time and the variables need the same neighbours");
     Out4 d;
-    for (int v = 0; v < 4; v++) {
-        CG_CHECK(delta[v] && delta[v] != var[v], "cg_fluid_vacuum_gather: Δ buffer %d", v);
-        d.p[v] = (double *)delta[v];
-    }
+    if (take4("cg_fluid_vacuum_gather", "Δ buffer", delta, 4, d)) return 1;
+    const void *reads[5] = {var[0], var[1], var[2], var[3], fac_time};
+    if (check_aliasing("cg_fluid_vacuum_gather", "Δ buffer", reads, 5, delta, 4)) return 1;
     const i64 n = nxl * gridsize * gridsize;
     hipLaunchKernelGGL(k_vacuum_gather, dim3((unsigned)((n + kThreads - 1) / kThreads)),
                        dim3(kThreads), 0, c->stream, s, Layers{fac_time, fac_time_lo, fac_time_hi},
@@ -698,32 +734,24 @@ extern "C" int cg_fluid_vacuum_apply(cg_ctx *c, void *const *var, const void *co
     CG_CHECK(c && var && delta && n >= 1, "cg_fluid_vacuum_apply: null argument");
     Out4 o;
     In4 d;
-    for (int v = 0; v < 4; v++) {
-        CG_CHECK(var[v] && delta[v], "cg_fluid_vacuum_apply: null grid %d", v);
-        o.p[v] = (double *)var[v];
-        d.p[v] = (const double *)delta[v];
-    }
-    hipLaunchKernelGGL(k_vacuum_apply, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, o, d,
-                       (i64)n);
-    CG_LAUNCH_CHECK();
-    return 0;
+    if (take4("cg_fluid_vacuum_apply", "null grid", var, 4, o) ||
+        take4("cg_fluid_vacuum_apply", "null grid", delta, 4, d))
+        return 1;
+    if (check_aliasing("cg_fluid_vacuum_apply", "grid", delta, 4, var, 4)) return 1;
+    return launch_stride(c, k_vacuum_apply, n, 4096, o, d, (i64)n);
 }
 
 extern "C" int cg_fluid_vmax(cg_ctx *c, const double *rho, const double *P, const void *const *J,
                              int64_t n, double inv_c2, double *out) {
     CG_CHECK(c && rho && P && J && out && n >= 1, "cg_fluid_vmax: null argument");
     In4 j{};
-    for (int v = 0; v < 3; v++) {
-        CG_CHECK(J[v], "cg_fluid_vmax: null grid %d", v);
-        j.p[v] = (const double *)J[v];
-    }
+    if (take4("cg_fluid_vmax", "null grid", J, 3, j)) return 1;
     if (c->fluid_partial.reserve(c, sizeof(double) * kPartials)) return 1;
-    const unsigned blocks = grid_for(n, kPartials);
-    hipLaunchKernelGGL(k_vmax, dim3(blocks), dim3(kThreads), 0, c->stream, rho, P, j, (i64)n, inv_c2,
-                       (double *)c->fluid_partial);
-    CG_LAUNCH_CHECK();
+    if (launch_stride(c, k_vmax, n, kPartials, rho, P, j, (i64)n, inv_c2,
+                      (double *)c->fluid_partial))
+        return 1;
     hipLaunchKernelGGL(k_reduce_columns<OpGreaterFrom0>, dim3(1), dim3(256), 0, c->stream,
-                       (const double *)c->fluid_partial, (i64)blocks, (i64)1, out);
+                       (const double *)c->fluid_partial, (i64)grid_for(n, kPartials), (i64)1, out);
     CG_LAUNCH_CHECK();
     return 0;
 }
@@ -744,24 +772,15 @@ extern "C" int cg_fluid_pressure_sources(cg_ctx *c, const double *rho, const dou
     CG_CHECK((const double *)P != rho, "cg_fluid_pressure_sources: 𝒫 and ϱ are one grid");
     if (!J) {   // the realisation alone
         const i64 n = nxl * gridsize * gridsize;
-        hipLaunchKernelGGL(k_realize_P, dim3(grid_for(n, 4096)), dim3(kThreads), 0, c->stream, rho,
-                           P, n, c2w);
-        CG_LAUNCH_CHECK();
-        return 0;
+        return launch_stride(c, k_realize_P, n, 4096, rho, P, n, c2w);
     }
     Out4 j{};
-    for (int d = 0; d < 3; d++) {
-        // the stencil must not read what the pass writes
-        CG_CHECK(J[d] && J[d] != (const void *)rho && J[d] != (void *)P,
-                 "cg_fluid_pressure_sources: J grid %d", d);
-        for (int e = 0; e < d; e++)
-            CG_CHECK(J[d] != J[e], "cg_fluid_pressure_sources: J grids %d and %d are one", e, d);
-        j.p[d] = (double *)J[d];
-    }
-    const dim3 grid((unsigned)((gridsize + kTZ - 1) / kTZ), (unsigned)((gridsize + kTY - 1) / kTY),
-                    (unsigned)((nxl + kXC - 1) / kXC));
-    hipLaunchKernelGGL(k_pressure_sources, grid, dim3(kThreads), 0, c->stream, r, P, j, (int)gridsize,
-                       (int)nxl, c2w, minus_dt, half_inv_dx);
+    if (take4("cg_fluid_pressure_sources", "J grid", J, 3, j)) return 1;
+    // (𝒫 is written as well: it counts as J grid 3)
+    const void *reads[1] = {rho}, *writes[4] = {J[0], J[1], J[2], P};
+    if (check_aliasing("cg_fluid_pressure_sources", "J grid", reads, 1, writes, 4)) return 1;
+    hipLaunchKernelGGL(k_pressure_sources, tile_grid(gridsize, nxl, kXC), dim3(kThreads), 0,
+                       c->stream, r, P, j, (int)gridsize, (int)nxl, c2w, minus_dt, half_inv_dx);
     CG_LAUNCH_CHECK();
     return 0;
 }

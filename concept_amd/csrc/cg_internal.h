@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "concept_gpu.h"
@@ -42,6 +43,17 @@ void cg_set_error(const char *fmt, ...);
             return 1;                                                                         \
         }                                                                                     \
     } while (0)
+
+// A template argument from a run-time integer (host): f(std::integral_constant<int, K>) for
+// K = which.  The last of the kCases takes whatever is left, as the `else` of a chain does: the
+// caller has refused a `which` outside 0 .. kCases - 1 before
+template <int kCases, int K = 0, class F>
+int with_case(int which, F f) {
+    if constexpr (K + 1 < kCases) {
+        if (which != K) return with_case<kCases, K + 1>(which, f);
+    }
+    return f(std::integral_constant<int, K>{});
+}
 
 // Geometry of the CIC index map for one domain, computed on the host with
 // the reference's own expressions (mesh.py:1577-1606 deposit, :408-432 gather).

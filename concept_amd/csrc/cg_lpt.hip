@@ -25,7 +25,7 @@
 //                    unused row of a layer are neither read nor written
 // and the bodies share wave_number, derivative (fourier_diff's rounding), rotate (the lattice
 // shift and the size-change phase) and accumulate ('=', '+=', '-=' with a factor).  On the host:
-// launch, with_case (a template argument from a run-time integer) and the *_checks.
+// launch, with_case of cg_internal.h (a template argument from a run-time integer) and the *_checks.
 // Compiled with -ffp-contract=off, and every function that rounds says so itself: every product
 // and sum is rounded on its own, in the reference's order.  FP64 throughout.
 #include <type_traits>
@@ -50,16 +50,6 @@ int launch(Kernel kernel, i64 work, size_t lds_bytes, hipStream_t stream, Args..
     hipLaunchKernelGGL(kernel, dim3(grid_for(work)), dim3(kThreads), lds_bytes, stream, args...);
     CG_LAUNCH_CHECK();
     return 0;
-}
-
-// f(std::integral_constant<int, K>) for K = which.  The last of the kCases takes whatever is left,
-// as the `else` of a chain does: the caller has refused a `which` outside 0 .. kCases - 1 before
-template <int kCases, int K = 0, class F>
-int with_case(int which, F f) {
-    if constexpr (K + 1 < kCases) {
-        if (which != K) return with_case<kCases, K + 1>(which, f);
-    }
-    return f(std::integral_constant<int, K>{});
 }
 
 // ---- the Fourier view and the walk over its modes

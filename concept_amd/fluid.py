@@ -7,10 +7,11 @@ MacCormack steps with their vacuum check and correction, the eight-fold cycle of
 v_max with the sound speed and the Courant limit, and for w ≠ 0 the realisation 𝒫 = ϱ c²w and the
 pressure term of the Euler equation (realize_𝒫, internal_sources, apply_internal_sources).  A
 w = 0 component takes the kernels and launches of the flux terms alone.  Out of scope (the
-functions raise and name the missing piece): boltzmann_order > 1 and the shear term (ς), closure
-'class' and linear variables realised by CLASS, a w that is not a constant number, decaying
-species (mom_decay_factor).  The Hubble term of the continuity equation needs
-approximations['P=wρ'] off, which the reference rules out for this scope (species.py:1678-1685).
+functions raise and name the missing piece): boltzmann_order > 1 with its non-linear ς and 𝒫,
+linear variables realised by CLASS other than the ς of closure 'class' below, a w that is not a
+constant number, decaying species (mom_decay_factor).  The Hubble term of the continuity
+equation needs approximations['P=wρ'] off, which the reference rules out for this scope
+(species.py:1678-1685).
 Kurganov-Tadmor, in the same scope: Runge-Kutta orders 1 and 2 and the nine flux limiters, one
 launch per Runge-Kutta step with the pressure term in the flux (kurganov_tadmor); no vacuum
 correction exists in that scheme.
@@ -72,6 +73,12 @@ def _ptrs(tensors):
     return (ctypes.c_void_p*len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _halo_ptr(stack):
+    """the address of the neighbour layers of a single grid, stack = lo or hi of
+    _neighbour_layers(component, [grid], H); None (one domain) stays None"""
+    return None if stack is None else _ptr(stack[0])
+
+
 def _state(component):
     """the solver's buffers of a component, made at its first maccormack()"""
     st = component.__dict__.get('_maccormack_state')
@@ -107,6 +114,15 @@ def _neighbour_layers(component, tensors, H):
     comm.sendrecv(up, comm.next, lo, comm.prev)
     comm.sendrecv(down, comm.prev, hi, comm.next)
     return lo, hi
+
+
+def _require_maccormack(component):
+    """drift() and apply_internal_sources() are the MacCormack scheme and refuse any other"""
+    scheme = is_selected(component, component.params.fluid_scheme_select)
+    if scheme != 'maccormack':
+        raise ConceptGPUError(
+            f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
+            'Kurganov-Tadmor is outside this path)')
 
 
 def _check_closure_class(component):
@@ -186,9 +202,8 @@ def internal_sources(component, ᔑdt, a_next=-1, closure_class=False):
     Δx = p.boxsize/component.gridsize
     lo, hi = _neighbour_layers(component, [component.ϱ], 1)
     check(_L.cg_fluid_pressure_sources(
-        _ctx(component), _ptr(component.ϱ), _ptr(lo[0]) if lo is not None else None,
-        _ptr(hi[0]) if hi is not None else None, _ptr(component.𝒫), _ptrs(list(component.J)),
-        component.gridsize, component.nxl, float(_c2w(component, a)),
+        _ctx(component), _ptr(component.ϱ), _halo_ptr(lo), _halo_ptr(hi), _ptr(component.𝒫),
+        _ptrs(list(component.J)), component.gridsize, component.nxl, float(_c2w(component, a)),
         float(-ᔑdt['a**(-3*w_eff)', component.name]), float((1/2)/Δx)))
 
 
@@ -201,11 +216,7 @@ def apply_internal_sources(component, ᔑdt, a_next=-1):
     is never applied here."""
     if component.representation != 'fluid':
         return   # particle components have no special internal source terms
-    scheme = is_selected(component, component.params.fluid_scheme_select)
-    if scheme != 'maccormack':
-        raise ConceptGPUError(
-            f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
-            'Kurganov-Tadmor is outside this path)')
+    _require_maccormack(component)
     _check_scope(component, a_next if a_next != -1 else 1.0)
     if component.boltzmann_order > 0 and not (component.w_type == 'constant'
                                               and component.w_constant == 0):
@@ -264,10 +275,8 @@ def correct_vacuum(component, mc_step, record=None):
     lo, hi = _neighbour_layers(component, var, 2)
     ft_lo, ft_hi = _neighbour_layers(component, [st.fac_time], 1)
     check(_L.cg_fluid_vacuum_gather(
-        ctx, _ptrs(var), _ptrs(lo), _ptrs(hi), _ptr(st.fac_time),
-        _ptr(ft_lo[0]) if ft_lo is not None else None,
-        _ptr(ft_hi[0]) if ft_hi is not None else None, _ptrs(st.Δ), component.gridsize,
-        component.nxl, float(fac_smoothing)))
+        ctx, _ptrs(var), _ptrs(lo), _ptrs(hi), _ptr(st.fac_time), _halo_ptr(ft_lo),
+        _halo_ptr(ft_hi), _ptrs(st.Δ), component.gridsize, component.nxl, float(fac_smoothing)))
     check(_L.cg_fluid_vacuum_apply(ctx, _ptrs(var), _ptrs(st.Δ), n))
     return True
 
@@ -299,7 +308,6 @@ def maccormack(component, ᔑdt, a_next=-1, record=None, closure_class=False):
         return   # no J variable: nothing to do (fluid.py:727-730)
     a = a_next if a_next != -1 else 1.0
     _check_scope(component, a, closure_class)
-    scope = {'closure_class': True} if closure_class else {}  # (callers without it: as before)
     # (a w = 0 component takes the path it always took: its 𝒫 grid is left as it is)
     pressure = getattr(component, 'w_constant', 0.0) != 0
     mc = component.params.fluid_options['maccormack']
@@ -320,7 +328,7 @@ def maccormack(component, ᔑdt, a_next=-1, record=None, closure_class=False):
                 if mc_step == 0 and pressure:
                     # 𝒫 is re-realised from the unstarred ϱ before every first step
                     # (fluid.py:912-913) and used as it is in the second
-                    realize_𝒫(component, a, **scope)
+                    realize_𝒫(component, a, closure_class=closure_class)
                 maccormack_step(component, ᔑdt, steps, mc_step, halve=halved)
             if correct:
                 if not correct_vacuum(component, mc_step, record):
@@ -345,12 +353,8 @@ def drift(component, ᔑdt, a_end=-1, closure_class=False):
     stepper.Timeloop.  closure_class: as for maccormack()."""
     if component.representation != 'fluid':
         raise ConceptGPUError(f'{component.name}: fluid.drift() is for fluid components')
-    scheme = is_selected(component, component.params.fluid_scheme_select)
-    if scheme != 'maccormack':
-        raise ConceptGPUError(
-            f'{component.name}: fluid scheme "{scheme}" is not implemented (only "maccormack"; '
-            'Kurganov-Tadmor is outside this path)')
-    maccormack(component, ᔑdt, a_end, **({'closure_class': True} if closure_class else {}))
+    _require_maccormack(component)
+    maccormack(component, ᔑdt, a_end, closure_class=closure_class)
 
 
 # -- the Kurganov-Tadmor scheme --------------------------------------------------------------------
@@ -514,7 +518,7 @@ def courant_limit(component, a, closure_class=False):
     the `fluid_limiter` hook of stepper.Timeloop."""
     p = component.params
     fac_courant = 0.21*p.Δt_base_nonlinear_factor
-    v = v_max(component, a, closure_class=True) if closure_class else v_max(component, a)
+    v = v_max(component, a, closure_class=closure_class)
     if v == 0:
         v = machine_ϵ   # a completely static component counts as just above 0
     return fac_courant*(p.boxsize/component.gridsize)/v

@@ -326,9 +326,9 @@ def test_courant_limit_formula(monkeypatch):
     from concept_amd import commons, fluid
     p = commons.load_params({'boxsize': 8.0, 'Δt_base_nonlinear_factor': 0.5})
     c = fake_component(p, gridsize=16)
-    monkeypatch.setattr(fluid, 'v_max', lambda comp, a: 2.5)
+    monkeypatch.setattr(fluid, 'v_max', lambda comp, a, closure_class=False: 2.5)
     assert fluid.courant_limit(c, 0.5) == 0.21*0.5*(8.0/16)/2.5
-    monkeypatch.setattr(fluid, 'v_max', lambda comp, a: 0.0)
+    monkeypatch.setattr(fluid, 'v_max', lambda comp, a, closure_class=False: 0.0)
     assert fluid.courant_limit(c, 0.5) == 0.21*0.5*(8.0/16)/commons.machine_ϵ
     assert len(list(itertools.islice(fluid._steps, 3))) == 3
     fluid.reset_steps()
