@@ -23,8 +23,17 @@ The bispectrum's computational core:
   bispec_measure()               compute_bispec (analysis.py:3031-3166) and the mode counting
                                  of get_bispec_bins (analysis.py:1293-1316) for explicit bins
 The configuration grammar, the shell boundaries, the tree-level bispectrum, the file, the
-dump of the time loop, plots and the on-disk mode cache are not built."""
+dump of the time loop, plots and the on-disk mode cache are not built.
+
+Conservation and shock diagnostics:
+  measure()                      analysis.py:3860-4230: 'v_max', 'v_rms', 'momentum', 'ϱ', 'mass'
+                                 and 'discontinuity' of a particle or fluid component; the sums
+                                 in double-double on the GPU (cg_measure_sums,
+                                 cg_measure_fluid_velocity, cg_measure_discontinuity,
+                                 csrc/cg_measure.hip) and finished in decimal by combine_sums()
+The utility info --stats and decaying species (w_eff ≠ w) are not built."""
 import collections
+import decimal
 import hashlib
 import itertools
 import math
@@ -38,7 +47,7 @@ import torch
 from . import commons
 from . import comm as _comm
 from .interactions import interpolate_upstream
-from .lib import ConceptGPUError
+from .lib import ConceptGPUError, _ptr, check, raw
 from .mesh import get_mesh
 
 π = commons.π
@@ -666,3 +675,196 @@ def bispec_measure(components, shells_per_bin, gridsize, *, interpolation='PCS',
         bpower_reduced = bpower/(power[0]*power[1] + power[1]*power[2] + power[2]*power[0])
     return BispecResult(n_modes=n_modes, bpower=bpower, power=power,
                         bpower_reduced=bpower_reduced, n_modes_power=modes_power)
+
+
+# -- measure (analysis.py:3860-4230) -----------------------------------------------------------
+MeasuredSums = collections.namedtuple('MeasuredSums', ('sum', 'sigma', 'mean', 'min', 'max_abs'))
+# the numbers cg_measure_sums leaves per column: Σx (hi, lo), Σx² (hi, lo), min x, max |x|
+SUMS_PER_COLUMN = 6
+
+
+def combine_sums(partials, count, scale=1.0):
+    """The end of a reduction of measure(), on the host: `partials` holds the six numbers of
+    cg_measure_sums for one column from every domain (shape (domains, 6), or (6,) for one), in
+    domain order; `count` is the number of values over all domains; `scale` multiplies every value
+    (Vcell for the momentum of a fluid cell).  Returns MeasuredSums: the sum, the standard
+    deviation sqrt(Σx²/count - (Σx/count)²) (a negative variance counts as 0) and the mean as the
+    reference computes them in decimal with 34 digits (analysis.py:4031-4056, 4066-4090), rounded to
+    double at the end, and the extremes.  A domain without values contributes 0, 0, 0, 0, +inf, 0.
+    A NaN or an infinity in the sums is passed on in floating point (decimal would refuse the
+    compare)."""
+    partials = np.asarray(partials, dtype=np.float64).reshape(-1, SUMS_PER_COLUMN)
+    x_min = float(np.min(partials[:, 4])) if partials.shape[0] else math.inf
+    x_max = float(np.max(partials[:, 5])) if partials.shape[0] else 0.0
+    if not np.all(np.isfinite(partials[:, :4])):
+        with np.errstate(invalid='ignore'):
+            total = float(np.sum(partials[:, 0]))*scale
+        mean = total/count if count else math.nan
+        return MeasuredSums(total, math.nan, mean, x_min, x_max)
+    with decimal.localcontext() as ctx:
+        ctx.prec = 2*17
+        D = decimal.Decimal
+        Σ = Σ2 = D(0)
+        for hi, lo, hi2, lo2 in partials[:, :4].tolist():
+            Σ += D(hi)
+            Σ += D(lo)
+            Σ2 += D(hi2)
+            Σ2 += D(lo2)
+        Σ *= D(scale)
+        Σ2 *= D(scale)**2
+        if count == 0:
+            return MeasuredSums(float(Σ), math.nan, math.nan, x_min, x_max)
+        mean = Σ/count
+        σ2 = Σ2/count - mean**2
+        σ = D(0) if σ2 < 0 else σ2.sqrt()
+        return MeasuredSums(float(Σ), float(σ), float(mean), x_min, x_max)
+
+
+def fluidscalar_names(component):
+    """(name, grid) of the fluid scalars iterate_fluidscalars (species.py:3570-3578) yields for
+    the component, in its order and with the names str(fluidscalar) gives (species.py:427-431:
+    '<fluidscalar varnum[multi_index]>').  𝒫 lives on ς as its trace and is a FluidScalar(0, 0)
+    (species.py:1718): it carries the name of ϱ."""
+    order, closure = component.boltzmann_order, component.boltzmann_closure
+    if closure != 'truncate' or order > 1:
+        raise ConceptGPUError(
+            f'{component.name}: measure(): quantity "discontinuity" with boltzmann_order = {order} '
+            f'and Boltzmann closure "{closure}" is not implemented: the linear fluid variable of '
+            'closure "class" and the ς of boltzmann_order > 1 are not kept as grids')
+    scalars = [('<fluidscalar 0[0]>', component.ϱ)]
+    if order == 1:
+        scalars += [(f'<fluidscalar 1[{dim}]>', component.J[dim]) for dim in range(3)]
+        scalars.append(('<fluidscalar 0[0]>', component.𝒫))
+    return scalars
+
+
+def _gather_domains(component, values):
+    """float64 (domains, len(values)) in domain order"""
+    if component.comm is not None and component.nprocs > 1:
+        return component.comm.all_gather_floats(list(values)).numpy()
+    return np.asarray(values, dtype=np.float64).reshape(1, -1)
+
+
+def _measure_ctx(component):
+    # (the kernels use a context for its stream, launch checks and scratch memory only)
+    if component.representation == 'particles':
+        return component._store.mesh._ctx
+    return component._mesh()._ctx
+
+
+def _device_sums(ctx, device, x, n, stride, offset, ncols, start=None, count=None, nregions=0):
+    out = torch.empty(SUMS_PER_COLUMN*ncols, dtype=torch.float64, device=device)
+    check(raw().cg_measure_sums(ctx, _ptr(x), int(n), int(stride), int(offset), int(ncols),
+                                _ptr(start), _ptr(count), int(nregions), _ptr(out)))
+    return out.tolist()
+
+
+def _grid_sums(component, grid, scale=1.0):
+    """combine_sums over all domains of one fluid grid"""
+    local = _device_sums(_measure_ctx(component), component.device, grid, grid.numel(), 1, 0, 1)
+    return combine_sums(_gather_domains(component, local), component.gridsize**3, scale)
+
+
+def _particle_momentum_sums(component, regions):
+    """the 18 numbers of cg_measure_sums for the three columns of this domain's mom, read once"""
+    if regions is not None:
+        regions.finish_exchange()
+        mom = regions.mom[regions.cur]
+        ctx = regions.mesh._ctx
+        if regions.count is None:
+            return _device_sums(ctx, mom.device, mom, regions.n_dense, 3, 0, 3)
+        return _device_sums(ctx, mom.device, mom, 0, 3, 0, 3, regions.start, regions.count,
+                            regions.start.numel() - 1)
+    mom = component.mom.contiguous()
+    return _device_sums(_measure_ctx(component), component.device, mom, mom.shape[0], 3, 0, 3)
+
+
+def measure(component, quantity, a=1.0, regions=None):
+    """measure(component, quantity) of the reference (analysis.py:3860-4230) at scale factor a;
+    collective over the x-slab domains.  regions: a particle component's particles in streaming
+    form (distributed.RegionParticles).
+
+      'v_max', 'v_rms'   particles: stepper.measure.  Fluids: fluid.v_max, and the rms bulk
+                         velocity plus the global sound speed (0 without a J variable)
+      'momentum'         (Σmom, σmom), two arrays of 3: of the particles' momenta, or of Vcell*J
+      'ϱ'                (ϱ_bar, σϱ, ϱ_min) of a fluid
+      'mass'             a**(-3*w_eff)*N*mass, or a**(-3*w_eff)*Vcell*Σϱ
+      'discontinuity'    (names, Δdiff_max_list, Δdiff_max_normalized_list) over the fluid's
+                         scalars: per dimension the largest |forward − backward difference|, and
+                         that over the largest |difference| (0 where the former is 0)
+    The sums are taken in double-double on the GPU and finished in decimal (combine_sums): the
+    number of domains changes a sum by less than count·2⁻¹⁰⁰ Σ|x| and the extremes not at all."""
+    from . import fluid, stepper
+    name = component.name
+    particles = component.representation == 'particles'
+    if quantity in ('v_max', 'v_rms') and particles:
+        return stepper.measure(component, quantity, a, regions)
+    if quantity not in ('v_max', 'v_rms', 'momentum', 'ϱ', 'mass', 'discontinuity'):
+        raise ConceptGPUError(f'measure(): quantity "{quantity}" not implemented')
+    w_eff = component.w_eff(a=a)
+    if particles:
+        if quantity == 'momentum':
+            parts = _gather_domains(component, _particle_momentum_sums(component, regions))
+            sums = [combine_sums(parts[:, SUMS_PER_COLUMN*dim:SUMS_PER_COLUMN*(dim + 1)],
+                                 component.N) for dim in range(3)]
+            return np.array([s_.sum for s_ in sums]), np.array([s_.sigma for s_ in sums])
+        if quantity == 'mass':
+            return a**(-3*w_eff)*component.N*component.mass
+        if quantity == 'ϱ':
+            raise ConceptGPUError(f'The measure function was called with {name} and '
+                                  "quantity='ϱ', but particle components do not have ϱ")
+        raise ConceptGPUError(f'The measure function was called with {name} and '
+                              "quantity='discontinuity', which is not applicable to particle "
+                              'components')
+    p = component.params
+    N_elements = component.gridsize**3
+    Vcell = p.boxsize**3/N_elements
+    closure_class = component.boltzmann_closure == 'class'
+    if quantity == 'v_max':
+        return fluid.v_max(component, a, closure_class=closure_class)
+    if quantity == 'v_rms':
+        if component.boltzmann_order == 0 and not closure_class:
+            return 0.0   # without J as a fluid variable no velocity exists
+        if component.boltzmann_order == 0:
+            raise ConceptGPUError(
+                f'{name}: measure(): quantity "v_rms" with J as a linear fluid variable '
+                '(boltzmann_order = 0, Boltzmann closure "class") is not implemented')
+        fluid._check_scope(component, a, closure_class)
+        out = torch.empty(SUMS_PER_COLUMN, dtype=torch.float64, device=component.device)
+        check(raw().cg_measure_fluid_velocity(
+            _measure_ctx(component), _ptr(component.ϱ), _ptr(component.𝒫),
+            fluid._ptrs(list(component.J)), component.ϱ.numel(), float(p.light_speed**(-2)),
+            _ptr(out)))
+        # sqrt(Σ/N_elements): the mean of the squares, as the deviation of values about 0
+        sums = combine_sums(_gather_domains(component, out.tolist()), N_elements)
+        with decimal.localcontext() as ctx:
+            ctx.prec = 2*17
+            rms = float((decimal.Decimal(sums.sum)/N_elements).sqrt()) if sums.sum >= 0 \
+                else math.nan
+        return a**(3*w_eff - 2)*rms + p.light_speed*math.sqrt(component.w(a=a))/a
+    if quantity == 'momentum':
+        sums = [_grid_sums(component, J_dim, Vcell) for J_dim in component.J]
+        return np.array([s_.sum for s_ in sums]), np.array([s_.sigma for s_ in sums])
+    if quantity == 'ϱ':
+        sums = _grid_sums(component, component.ϱ)
+        return sums.mean, sums.sigma, sums.min
+    if quantity == 'mass':
+        return a**(-3*w_eff)*Vcell*_grid_sums(component, component.ϱ).sum
+    # 'discontinuity'
+    scalars = fluidscalar_names(component)
+    names, Δdiff_max_list, Δdiff_max_normalized_list = [], [], []
+    inv_h = 1/(p.boxsize/component.gridsize)
+    out = torch.empty(6, dtype=torch.float64, device=component.device)
+    for scalar_name, grid in scalars:
+        lo, hi = fluid._neighbour_layers(component, [grid], 1)
+        check(raw().cg_measure_discontinuity(
+            _measure_ctx(component), _ptr(grid), fluid._halo_ptr(lo), fluid._halo_ptr(hi),
+            component.gridsize, component.nxl, inv_h, _ptr(out)))
+        maxima = _gather_domains(component, out.tolist()).max(axis=0)
+        Δdiff_max, diff_max = maxima[:3], maxima[3:]
+        names.append(scalar_name)
+        Δdiff_max_list.append(Δdiff_max)
+        Δdiff_max_normalized_list.append(np.array(
+            [Δdiff_max[dim]/diff_max[dim] if Δdiff_max[dim] > 0 else 0 for dim in range(3)],
+            dtype=np.float64))
+    return names, Δdiff_max_list, Δdiff_max_normalized_list

@@ -11,7 +11,7 @@ REPO = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libconcept_gpu.so')
 SOURCES = ['cg_context.hip', 'cg_mesh_kernels.hip', 'cg_tiled_kernels.hip', 'cg_fft.hip', 'cg_rocfft.hip', 'cg_shortrange.hip', 'cg_shortrange_dense.hip', 'cg_rungs.hip',
-           'cg_particles.hip', 'cg_general.hip', 'cg_pp.hip', 'cg_analysis.hip', 'cg_render.hip', 'cg_fluid.hip', 'cg_bispec.hip', 'cg_lpt.hip', 'cg_noise.hip']
+           'cg_particles.hip', 'cg_general.hip', 'cg_pp.hip', 'cg_analysis.hip', 'cg_render.hip', 'cg_fluid.hip', 'cg_bispec.hip', 'cg_lpt.hip', 'cg_noise.hip', 'cg_measure.hip']
 # every header of csrc (a new one is in the staleness check without being listed), the C ABI last
 HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + [
     os.path.join(REPO, 'include', 'concept_gpu.h')]

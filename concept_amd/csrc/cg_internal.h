@@ -244,6 +244,9 @@ struct cg_ctx {
     // ---- fluid solver ----
     cg_buf<double> fluid_partial;        // cg_fluid_vmax: per-workgroup partial maxima
 
+    // ---- measure() ----
+    cg_buf<double> measure_partial;      // cg_measure_*: per-workgroup partial results
+
     // ---- bispectrum ----
     cg_buf<double> bispec_partial;       // cg_bispec_sums: per-workgroup partial sums
 

@@ -108,6 +108,78 @@ struct OpGreaterFrom0 {
     __device__ __forceinline__ double operator()(double a, double b) const { return b > a ? b : a; }
 };
 
+// the extremes of measure(): a NaN gets in and stays in (fmin and fmax would drop it)
+struct OpMinNan {
+    static __device__ __forceinline__ double identity() { return INFINITY; }
+    __device__ __forceinline__ double operator()(double a, double b) const {
+        return (b < a || b != b) ? b : a;
+    }
+};
+struct OpMaxNan {
+    static __device__ __forceinline__ double identity() { return 0.0; }
+    __device__ __forceinline__ double operator()(double a, double b) const {
+        return (b > a || b != b) ? b : a;
+    }
+};
+
+// Fold over the 64 lanes by xor butterfly, m = 32, 16, ..., 1, for an Op whose result does not
+// depend on the order of its two operands.  Every lane ends with the result.
+template <class Op>
+__device__ __forceinline__ double wave_fold_xor(double v) {
+    for (int m = 32; m >= 1; m >>= 1) v = Op()(v, __shfl_xor(v, m));
+    return v;
+}
+
+// ---- double-double: a value hi + lo with |lo| <= ulp(hi)/2, about 106 bits ----
+// The sums of measure() (momenta add up to about zero: a double-precision tree sum returns
+// round-off).  u = 2^-53 below.  The error bounds are those of Joldes, Muller and Popescu, "Tight
+// and rigorous error bounds for basic building blocks of double-word arithmetic", ACM TOMS 44(2),
+// 2017, and hold without underflow and overflow.  A NaN or an infinity among the operands ends
+// as a NaN or an infinity in hi.
+struct dd {
+    double hi, lo;
+};
+// a + b = s + e exactly (Knuth's TwoSum, 6 operations, any magnitudes)
+__device__ __forceinline__ dd two_sum(double a, double b) {
+#pragma clang fp contract(off)
+    const double s = a + b;
+    const double bb = s - a;
+    return dd{s, (a - (s - bb)) + (b - bb)};
+}
+// the same in 3 operations where |a| >= |b| or a = 0 (Dekker's Fast2Sum)
+__device__ __forceinline__ dd fast_two_sum(double a, double b) {
+#pragma clang fp contract(off)
+    const double s = a + b;
+    return dd{s, b - (s - a)};
+}
+// x + y for a double y: DWPlusFP (algorithm 4 of the paper), relative error <= 2u^2
+__device__ __forceinline__ dd dd_add_double(dd x, double y) {
+#pragma clang fp contract(off)
+    const dd s = two_sum(x.hi, y);
+    return fast_two_sum(s.hi, x.lo + s.lo);
+}
+// x + y: AccurateDWPlusDW (algorithm 6 of the paper), relative error <= 3u^2 + 13u^3.  The
+// result does not depend on the order of x and y: two_sum's two outputs do not.
+__device__ __forceinline__ dd dd_add(dd x, dd y) {
+#pragma clang fp contract(off)
+    const dd s = two_sum(x.hi, y.hi);
+    const dd t = two_sum(x.lo, y.lo);
+    const dd v = fast_two_sum(s.hi, s.lo + t.hi);
+    return fast_two_sum(v.hi, t.lo + v.lo);
+}
+// x*x = hi + lo exactly (no underflow of the low part)
+__device__ __forceinline__ dd dd_square(double x) {
+#pragma clang fp contract(off)
+    const double p = x * x;
+    return dd{p, fma(x, x, -p)};
+}
+// Sum over the 64 lanes by xor butterfly, as wave_sum_xor, with dd_add.  Every lane ends with
+// the sum.
+__device__ __forceinline__ dd wave_sum_xor_dd(dd v) {
+    for (int m = 32; m >= 1; m >>= 1) v = dd_add(v, dd{__shfl_xor(v.hi, m), __shfl_xor(v.lo, m)});
+    return v;
+}
+
 // Tree over the 256 threads of a workgroup in LDS: red[t] = v of thread t, then for
 // m = 128, 64, ..., 1 the threads t < m set red[t] = op(red[t], red[t + m]).
 // Every thread returns red[0]; a second call needs another red (or a barrier in between).

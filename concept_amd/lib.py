@@ -156,6 +156,9 @@ SYMBOLS = {
     'cg_fluid_vacuum_gather': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl]),
     'cg_fluid_vacuum_apply': (_int, [_vp, _vp, _vp, _i64]),
     'cg_fluid_vmax': (_int, [_vp, _vp, _vp, _vp, _i64, _dbl, _vp]),
+    'cg_measure_sums': (_int, [_vp, _vp, _i64, _i64, _i64, _int, _vp, _vp, _i64, _vp]),
+    'cg_measure_fluid_velocity': (_int, [_vp, _vp, _vp, _vp, _i64, _dbl, _vp]),
+    'cg_measure_discontinuity': (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _dbl, _vp]),
     'cg_fluid_pressure_sources': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _dbl, _dbl,
                                          _dbl]),
     'cg_lpt_potential': (_int, [_vp, _vp, _vp, _i64, _vp, _dbl]),

@@ -1133,6 +1133,25 @@ class Timeloop(RungStepper):
             loop.renders2D_written.extend(files)
         return self._dumper(self.params.render2D_times, output_dir, output_base, write)
 
+    def conservation_dumper(self):
+        """An on_dump callback that records what the run conserves: at every dump time it appends
+        to loop.measurements one record per component — its name, a, t, 'mass' and 'momentum'
+        (Σmom, σmom), and for a fluid 'ϱ' (ϱ_bar, σϱ, ϱ_min) — as analysis.measure gives them.
+        Nothing installs it: loop.on_dump = loop.conservation_dumper()."""
+        from . import analysis
+        self.measurements = []
+
+        def on_dump(loop, dump_time):
+            a = loop.cosmo.a
+            for c in loop.components:
+                record = {'component': c.name, 'a': a, 't': loop.cosmo.t,
+                          'mass': analysis.measure(c, 'mass', a),
+                          'momentum': analysis.measure(c, 'momentum', a)}
+                if c.representation == 'fluid':
+                    record['ϱ'] = analysis.measure(c, 'ϱ', a)
+                loop.measurements.append(record)
+        return on_dump
+
     # -- main.timeloop (main.py:102-471) ---------------------------------------------------
     def run(self):
         try:

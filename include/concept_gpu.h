@@ -834,6 +834,38 @@ int cg_fluid_vacuum_apply(cg_ctx *ctx, void *const *var /*HOST 4*/,
 int cg_fluid_vmax(cg_ctx *ctx, const double *rho /*DEV n*/, const double *P /*DEV n*/,
                   const void *const *J /*HOST 3*/, int64_t n, double inv_c2, double *out /*DEV 1*/);
 
+/* --- measure(): conservation and shock diagnostics (analysis.py:3860-4230) ------------------
+ * Fixed reduction trees and no atomics: the same input gives the same bits.  Scratch memory is
+ * the context's.
+ * cg_measure_sums: ncols (1 to 3) neighbouring columns of a strided array, column q of row p at
+ *   x[p*stride + offset + q] (a grid: stride 1; one column of the AoS mom: stride 3; its three
+ *   columns in one pass: stride 3, ncols 3).  Per column q, out[6q ..]: Σx as a double-double
+ *   (hi, lo), Σx² as a double-double, min x, max |x|.  hi + lo is within n 2^-100 Σ|x| of the exact
+ *   sum of the n values (Σx² likewise, the squares being exact).  No rows: 0, 0, 0, 0, +inf, 0.  A
+ *   NaN or an infinity among the values ends as a NaN or an infinity in hi, and a NaN in the
+ *   extremes.  start (or NULL) / count / nregions: the rows are those of the regions
+ *   [start[r], start[r] + count[r]), r < nregions, as for cg_measure_momentum_regions (count =
+ *   NULL: up to start[r + 1], start holding nregions + 1 entries); rows between regions are not
+ *   read, and n is not used.
+ * cg_measure_fluid_velocity: the same six numbers of v² = (Jx² + Jy² + Jz²)/(ϱ + inv_c2 𝒫)² over n
+ *   cells, each v² evaluated in double in the expression order of analysis.py:4009-4012:
+ *   out[0] + out[1] is their sum (cg_fluid_vmax has their maximum).
+ * cg_measure_discontinuity: one grid of nxl x gridsize x gridsize cells; f_lo / f_hi: the layer
+ *   below the first and above the last (both NULL: nxl = gridsize and the grid wraps around).  Per
+ *   cell and dimension d, fwd = inv_h*(f[+1_d] - f[0]) and bwd = inv_h*(f[0] - f[-1_d]) (the
+ *   order-1 branch of diff_domaingrid, mesh.py:4961-4965); out[d] = max |fwd - bwd|, out[3 + d] =
+ *   max(|fwd|, |bwd|) (analysis.py:4191-4206; the compares start from 0 and let no NaN in). */
+int cg_measure_sums(cg_ctx *ctx, const double *x /*DEV*/, int64_t n, int64_t stride,
+                    int64_t offset, int ncols, const uint32_t *start /*DEV or NULL*/,
+                    const uint32_t *count /*DEV or NULL*/, int64_t nregions,
+                    double *out /*DEV 6 ncols*/);
+int cg_measure_fluid_velocity(cg_ctx *ctx, const double *rho /*DEV n*/, const double *P /*DEV n*/,
+                              const void *const *J /*HOST 3*/, int64_t n, double inv_c2,
+                              double *out /*DEV 6*/);
+int cg_measure_discontinuity(cg_ctx *ctx, const double *f /*DEV*/, const double *f_lo,
+                             const double *f_hi, int64_t gridsize, int64_t nxl, double inv_h,
+                             double *out /*DEV 6*/);
+
 /* --- initial conditions: 1LPT / 2LPT particle realisation (ic.py:1199-1589, 2038-2280) ----
  * The k-space entries work on the contexts' current Fourier views, the real-space ones on the
  * owned layers of their meshes; meshes named together have one grid size and one domain.
